@@ -2,6 +2,7 @@
 """Benchmark of the scHPF CAVI hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5-shard] [--dtype f64|f32]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one CAVI iteration (the loop body of the reference's scHPF._fit,
 schpf/scHPF_.py:657-714) over the whole synthetic count matrix.  The default workload is
@@ -15,11 +16,17 @@ row-sharded over the ranks by the product's own nnz-balanced partition
 [bounds[r], bounds[r+1]), and every iteration does one RCCL all-reduce of the G*K + K
 gene-side sums.
 
-Prints ONE JSON line on rank 0, carrying the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  A plain run does only what that headline needs: set-up, warm-up, the K timed steps, the line.
+`--dump-outputs DIR` also writes the model the last timed step left (see dump_outputs).  `--full` adds
+  loss         : loss after the warm-up and after the timed steps, time of one loss evaluation
   roofline     : dominant kernel (the sweep), HIP-event timed, against THREE roofs -- algorithmic bytes vs HBM, the
                  essential FMAs vs the vector-FP peak of the dtype, the LDS bytes vs 256 B/clk/CU -- with the shader
                  clock measured under the kernel (sclk_mhz); `bound` names the nearest one
+  per_rank     : a row shard of C3 through the sharded driver beside 1/ranks of the whole matrix's iteration
+  convergence  : wall-clock of whole fits to convergence
   cpu_baseline : the CPU oracle in the reference's execution shape on this box's cores
+(--no-traffic, --no-cpu-baseline and --no-converge still leave out the counter passes, the CPU baselines and the fits).
 """
 import argparse
 import json
@@ -53,6 +60,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s 
 VALU_PEAK_TFLOPS = {"f64": 78.6, "f32": 157.3}
 MAX_CLOCK_MHZ = 2400            # MI355X_MICROARCH.md chip table: the clock the peaks above are quoted at
 LDS_BYTES_PER_CLK_PER_CU = 256  # same guide, LDS section: 64 dwords wide per clock
+DUMP_BYTES = 64_000_000         # --dump-outputs: at most this many bytes in all
 
 
 from benchlib.data import (SLAB_CONFIGS, SLAB_ROWS, planted_block, synthetic_block, synthetic_slabs,   # noqa: E402,F401
@@ -252,6 +260,34 @@ def cpu_baseline(X, K, dtype):
     }
 
 
+def dump_outputs(eng, out_dir, seed=0):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the variational shapes and
+    rates of xi, theta (cell side) and eta, beta (gene side) as the engine hands them out (get_gamma, model dtype) --
+    as out_dir/<name>_shape.npy and <name>_rate.npy.  If they hold more than DUMP_BYTES, one fixed sample of rows per
+    side (RandomState(seed), the same fraction on both sides) is written instead, its sorted row indices as
+    cell_rows.npy / gene_rows.npy (float64).  A rank of a sharded run holds, and writes, its own rows of the cell side."""
+    os.makedirs(out_dir, exist_ok=True)
+    sides = {"cell": ("xi", "theta"), "gene": ("eta", "beta")}
+    arrays = {}
+    for names in sides.values():
+        for name in names:
+            arrays[name + "_shape"], arrays[name + "_rate"] = eng.get_gamma(name)
+    rows = {"cell": arrays["xi_shape"].shape[0], "gene": arrays["eta_shape"].shape[0]}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        frac = DUMP_BYTES / float(total + 8 * sum(rows.values()))     # the float64 row indices count too
+        rng = np.random.RandomState(seed)
+        for side, names in sides.items():
+            n = rows[side]
+            keep = np.sort(rng.choice(n, max(1, int(n * frac)), replace=False))
+            for name in names:
+                for part in ("_shape", "_rate"):
+                    arrays[name + part] = arrays[name + part][keep]
+            arrays[side + "_rows"] = keep.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -286,6 +322,13 @@ def main():
     ap.add_argument("--fail-library-comm", action="store_true", help=argparse.SUPPRESS)   # tests: exercise the fall-back below
     ap.add_argument("--no-converge", action="store_true",
                     help="skip the wall-clock-to-convergence fits (second half of BASELINE.json's metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the loss evaluations, the roofline (kernel times of a second, "
+                         "eager pass, shader clock, rocprofv3 traffic passes), per_rank, the convergence fits and the CPU "
+                         "baselines.  Without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the model they left (xi / theta / eta / beta shapes and rates) "
+                         "as DIR/<name>.npy, at most 64 MB in all (a fixed sample of rows beyond that)")
     args = ap.parse_args()
     if args.pmc_child:
         _pmc_child(args.pmc_child, args.pmc_k, args.dtype, args.steps)
@@ -333,7 +376,6 @@ def main():
 
     N, G, density, K = CONFIGS[args.config]
     dtype = np.float64 if args.dtype == "f64" else np.float32
-    itemsize = np.dtype(dtype).itemsize
     # ONE matrix for every N: generator A with seed 42 (what BENCH's N = 1 line times).  With N > 1 every rank draws
     # it (deterministic; nothing but the communicator id travels between the ranks) and keeps its block of the
     # product's nnz-balanced row partition -- the split scHPF.fit(X, devices=[...]) makes.
@@ -475,19 +517,40 @@ def main():
     for _ in range(args.warmup):
         step()
     many = getattr(drv, "steps", None) if sharded else eng.steps   # sharded: a graph only with SCHPF_GRAPH_SHARDED=1
-    if use_graph:
-        many(args.steps)                # untimed: captures the K-iteration graph the timed call replays
-    loss_start = loss_fn()
+    # untimed calls of the timed call, so that it finds its graph captured: a graph holds an even number of iterations
+    # and is cached per parity of the iteration count at its start, and nothing is captured before one eager iteration
+    # (capi.hip steps) -- an odd K (K - 1 replayed + one eager) needs the graph of either parity, W = 0 one call more
+    untimed_calls = (1 + args.steps % 2 + (args.warmup == 0)) if use_graph else 0
+    for _ in range(untimed_calls):
+        many(args.steps)
+    if args.full:
+        loss_start = loss_fn()
     # shader clock under the sweep launches (schpf_profile_clock: workgroup 0 of every launch stamps the shader-cycle
     # and the constant-rate counters; it works inside a replayed graph too): once over the timed call itself, once
     # over the eager pass the kernel times come from
     if use_graph:
         fence()
-        eng.profile_clock()             # reset
+        if args.full:
+            eng.profile_clock()         # reset
         t0 = time.perf_counter()
         many(args.steps)                # EXACTLY K iterations, one library call (one hipGraph launch)
         fence()
         elapsed = time.perf_counter() - t0
+    else:
+        if args.full:                   # HIP events around every launch of the timed iterations: the kernel times
+            eng.profile(True)
+            eng.profile_read()
+        fence()
+        if args.full:
+            eng.profile_clock()         # reset
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+    if args.full and use_graph:
         sclk_timed = eng.profile_clock()
         eng.profile(True)               # kernel times for the roofline: a second, eager pass of K iterations
         eng.profile_read()
@@ -496,16 +559,7 @@ def main():
         prof = eng.profile_read()
         sclk_eager = eng.profile_clock()
         eng.profile(False)
-    else:
-        eng.profile(True)
-        eng.profile_read()
-        fence()
-        eng.profile_clock()             # reset
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        elapsed = time.perf_counter() - t0
+    elif args.full:
         prof = eng.profile_read()
         sclk_timed = sclk_eager = eng.profile_clock()
         eng.profile(False)
@@ -513,6 +567,66 @@ def main():
         el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         elapsed = float(el.item())
+
+    ms_per_step = elapsed / args.steps * 1e3
+    value = args.steps / elapsed
+    info = eng.plan_info()
+    out = {
+        "metric": "CAVI iterations/sec, 100kx20k K=20" if args.config == "c3"
+                  else "CAVI iterations/sec (%s)" % args.config,
+        "value": value, "unit": "iterations/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {
+            "workload": "%s: synthetic %d cells x %d genes, density %.3f (negative-binomial counts, "
+                        "RandomState(42%s), the same matrix for every N), nnz %d after summing duplicates, "
+                        "K=%d, one CAVI iteration per step (no loss evaluation inside the step)"
+                        % (args.config.upper(), N, G, density, " + slab: slabs of %d cells" % slab_rows if slab_rows else "",
+                           nnz_total, K),
+            "parallelism": ("cells row-sharded x%d by schpf_amd.sharded.row_partition (nnz-balanced contiguous row "
+                            "blocks; this rank: rows %d..%d, nnz %d), one RCCL all-reduce of G*K+K per iteration (%s)"
+                            % (world, my_rows[0], my_rows[1], nnz_local,
+                               "issued by the library" if args.comm == "library" else "torch.distributed"))
+                           if world > 1 else "single GPU",
+            "launch": ("one library call for the %d timed iterations (%s), after %d untimed calls of the same call"
+                       % (args.steps, "schpf_steps_sharded; a hipGraph with one rank or SCHPF_GRAPH_SHARDED=1" if sharded
+                          else "schpf_steps: one hipGraph replay", untimed_calls)
+                       + "; before the %d warm-up steps %d loss evaluations (read-only sweeps, %.1f s) bring the GPU out of its idle clocks"
+                       % (args.warmup, prewarm_evals, args.prewarm_s))
+                      if use_graph else "one library call per iteration, eager launches",
+            "plan": info,
+            "generation": generation,
+            **({"comm_fallback": "the library's RCCL communicator could not be set up (%s): torch.distributed "
+                                 "issues the all-reduce instead, one call per iteration" % comm_fallback}
+               if comm_fallback else {}),
+        },
+        "upload_and_plan_s": upload_s,
+    }
+    if args.full:
+        full_measurements(args, out, eng, X, nnz_total, N, G, K, dtype, density, world, rank, local_rank, sharded,
+                          use_graph, step, loss_fn, fence, prof, sclk_timed, sclk_eager, loss_start)
+    eng.close()
+    if sharded:
+        dist.barrier()
+        dist.destroy_process_group()
+    # RCCL prints its version banner through C stdio, which is flushed at exit when stdout is a
+    # pipe: flush it now so that the JSON line is the LAST line of stdout
+    import ctypes
+    ctypes.CDLL(None).fflush(None)
+    if rank == 0:
+        sys.stdout.write(json.dumps(out) + "\n")
+        sys.stdout.flush()
+
+
+def full_measurements(args, out, eng, X, nnz_total, N, G, K, dtype, density, world, rank, local_rank, sharded,
+                      use_graph, step, loss_fn, fence, prof, sclk_timed, sclk_eager, loss_start):
+    """--full: everything of the line beyond the headline figure, added to `out` after the timed steps."""
+    import torch
+    from schpf_amd import DeviceCAVI
+    itemsize = np.dtype(dtype).itemsize
+    n_local, nnz_local = X.shape[0], X.nnz
+    ms_per_step = out["ms_per_step"]
+    info = out["config"]["plan"]
 
     # loss evaluation (every check_freq = 10 iterations in a default fit), outside the timed region: the median of five,
     # each right behind an iteration as in a fit (a single sample of a 0.4 ms call read 0.38-0.46 on one build);
@@ -531,8 +645,6 @@ def main():
             loss_end = val
     loss_ms = float(np.median(loss_samples))
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = args.steps / elapsed
     b_iter = algorithmic_bytes(nnz_local, n_local, G, K, itemsize)
     sweeps = prof["cell_sweep"]["launches"] + prof["gene_sweep"]["launches"]
     sweep_ms = (prof["cell_sweep"]["ms"] + prof["gene_sweep"]["ms"]) / max(sweeps, 1)
@@ -540,7 +652,6 @@ def main():
     per_iter = max(1, int(round(sweeps / float(args.steps))))
     b_launch = b_iter / per_iter
     achieved = b_launch / (sweep_ms * 1e-3) / 1e9 if sweep_ms > 0 else 0.0
-    info = eng.plan_info()
     # The compute roof of the same launch.  Essential arithmetic of the two-pass form: per stored nonzero and
     # orientation K FMAs for the normaliser s = sum_k Et[i,k] Eb[g,k] and K FMAs for acc_k += (x / s) Eb[g,k]
     # (sweep_impl.h pipe_step) = 4 K FMAs = 8 K flop per nonzero over both orientations (the reciprocal, the
@@ -578,35 +689,7 @@ def main():
     # the counters were collected on the one-launch (dual) iteration of a single GPU
     traffic, traffic_src = static_traffic(args.config, args.dtype, info) if not sharded else (None, None)
 
-    out = {
-        "metric": "CAVI iterations/sec, 100kx20k K=20" if args.config == "c3"
-                  else "CAVI iterations/sec (%s)" % args.config,
-        "value": value, "unit": "iterations/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {
-            "workload": "%s: synthetic %d cells x %d genes, density %.3f (negative-binomial counts, "
-                        "RandomState(42%s), the same matrix for every N), nnz %d after summing duplicates, "
-                        "K=%d, one CAVI iteration per step (no loss evaluation inside the step)"
-                        % (args.config.upper(), N, G, density, " + slab: slabs of %d cells" % slab_rows if slab_rows else "",
-                           nnz_total, K),
-            "parallelism": ("cells row-sharded x%d by schpf_amd.sharded.row_partition (nnz-balanced contiguous row "
-                            "blocks; this rank: rows %d..%d, nnz %d), one RCCL all-reduce of G*K+K per iteration (%s)"
-                            % (world, my_rows[0], my_rows[1], nnz_local,
-                               "issued by the library" if args.comm == "library" else "torch.distributed"))
-                           if world > 1 else "single GPU",
-            "launch": ("one library call for the %d timed iterations (%s), after %d untimed iterations of the same call"
-                       % (args.steps, "schpf_steps_sharded; a hipGraph with one rank or SCHPF_GRAPH_SHARDED=1" if sharded
-                          else "schpf_steps: one hipGraph replay", args.steps)
-                       + "; before the %d warm-up steps %d loss evaluations (read-only sweeps, %.1f s) bring the GPU out of its idle clocks"
-                       % (args.warmup, prewarm_evals, args.prewarm_s))
-                      if use_graph else "one library call per iteration, eager launches",
-            "plan": info,
-            "generation": generation,
-            **({"comm_fallback": "the library's RCCL communicator could not be set up (%s): torch.distributed "
-                                 "issues the all-reduce instead, one call per iteration" % comm_fallback}
-               if comm_fallback else {}),
-        },
+    out.update({
         "roofline": {
             # the nearer roof of the two below; `achieved` / `peak` / `frac` keep SURVEY 8(d)'s definition
             # (algorithmic bytes per launch / launch time against the HBM peak) whichever one binds
@@ -667,8 +750,7 @@ def main():
                       "how": "chosen by the library's list-schedule model of the pass (capi.hip loss_tasks / loss_side)"},
         "loss_after_warmup": loss_start, "loss_after_steps": loss_end,
         "iterations_per_s_with_loss_every_10": 10.0 / (10 * ms_per_step * 1e-3 + loss_ms * 1e-3),
-        "upload_and_plan_s": upload_s,
-    }
+    })
     if rank == 0 and world == 1 and sharded and args.config in SHARD_OF and SHARD_OF[args.config][0] == "c3":
         # a rank's iteration beside its ideal: the WHOLE matrix on this GPU in the same process, divided by the ranks
         # (what perfect strong scaling without any exchange would give the rank)
@@ -716,17 +798,6 @@ def main():
                        "throughput matrix) / CPU iterations per second; loss checks and set-up not counted"}
     elif rank == 0:
         out["cpu_baseline"] = None
-    eng.close()
-    if sharded:
-        dist.barrier()
-        dist.destroy_process_group()
-    # RCCL prints its version banner through C stdio, which is flushed at exit when stdout is a
-    # pipe: flush it now so that the JSON line is the LAST line of stdout
-    import ctypes
-    ctypes.CDLL(None).fflush(None)
-    if rank == 0:
-        sys.stdout.write(json.dumps(out) + "\n")
-        sys.stdout.flush()
 
 
 if __name__ == "__main__":

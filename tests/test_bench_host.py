@@ -1,6 +1,8 @@
-"""Host-side pieces of bench.py that run without a GPU: the synthetic generator (generator A)
-and the row split of the N > 1 bench -- every rank draws the N = 1 matrix and keeps its block of the product's
-nnz-balanced partition."""
+"""Host-side pieces of bench.py that run without a GPU: the synthetic generator (generator A),
+the row split of the N > 1 bench -- every rank draws the N = 1 matrix and keeps its block of the product's
+nnz-balanced partition -- and the writer behind --dump-outputs."""
+import os
+
 import numpy as np
 import pytest
 from scipy.sparse import coo_matrix
@@ -83,3 +85,68 @@ def test_per_rank_draw_gives_the_blocks_of_the_whole_matrix(world):
         assert np.array_equal(facts["col_sums"], np.asarray(X.sum(0)).ravel())
         # 1 / world of the draws and at most three boundary slabs more
         assert facts["draws"] <= facts["draws_whole_matrix"] * (1.0 / world + 3.0 / facts["slabs_total"]) + 1
+
+
+class _FakeEngine:
+    """What dump_outputs reads of a DeviceCAVI: get_gamma(name) -> (shape, rate) in the model dtype."""
+
+    def __init__(self, N, G, K, dtype, seed=5):
+        rng = np.random.RandomState(seed)
+        dims = {"xi": (N,), "theta": (N, K), "eta": (G,), "beta": (G, K)}
+        self.state = {n: (rng.gamma(2.0, 1.0, d).astype(dtype), rng.gamma(3.0, 1.0, d).astype(dtype))
+                      for n, d in dims.items()}
+
+    def get_gamma(self, name):
+        s, r = self.state[name]
+        return s.copy(), r.copy()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_dump_outputs_writes_the_whole_model(tmp_path, dtype):
+    """bench.py --dump-outputs: below the size limit every array, bit for bit, in the model dtype."""
+    import bench
+    eng = _FakeEngine(300, 200, 7, dtype)
+    bench.dump_outputs(eng, str(tmp_path))
+    names = [f[:-4] for f in os.listdir(str(tmp_path))]
+    assert sorted(names) == sorted(n + p for n in ("xi", "theta", "eta", "beta") for p in ("_shape", "_rate"))
+    for n, (s, r) in eng.state.items():
+        for part, want in (("_shape", s), ("_rate", r)):
+            got = np.load(str(tmp_path / (n + part + ".npy")))
+            assert got.dtype == dtype and np.array_equal(got, want)
+
+
+def test_dump_outputs_samples_rows_beyond_the_limit(tmp_path, monkeypatch):
+    """Above the limit: one fixed, seeded sample of rows per side, the same from run to run, within the limit in
+    all (row indices included), with the indices written beside it."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    eng = _FakeEngine(3000, 1000, 9, np.float64)
+    bench.dump_outputs(eng, str(tmp_path / "a"))
+    bench.dump_outputs(eng, str(tmp_path / "b"))
+    names = [f[:-4] for f in os.listdir(str(tmp_path / "a"))]
+    assert "cell_rows" in names and "gene_rows" in names
+    total = 0
+    for name in names:
+        a, b = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 200_000
+    for side, (n, names_of_side) in {"cell": (3000, ("xi", "theta")), "gene": (1000, ("eta", "beta"))}.items():
+        rows = np.load(str(tmp_path / "a" / (side + "_rows.npy")))
+        assert 0 < rows.size < n and np.all(np.diff(rows) > 0) and rows[-1] < n
+        keep = rows.astype(np.int64)
+        for name in names_of_side:
+            s, r = eng.state[name]
+            assert np.array_equal(np.load(str(tmp_path / "a" / (name + "_shape.npy"))), s[keep])
+            assert np.array_equal(np.load(str(tmp_path / "a" / (name + "_rate.npy"))), r[keep])
+
+
+def test_bench_options():
+    """The options every benchmark run relies on, readable without a GPU (argparse exits before any device work)."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
+        assert opt in r.stdout

@@ -108,7 +108,7 @@ def test_bench_line_of_two_ranks_on_one_gpu():
     row blocks per rank, the rank-summed nnz, the MAX-over-ranks timing and rank 0's JSON line (the numbers
     are not a measurement: gloo stages the exchange buffer through the host)."""
     r = _torchrun(2, ["bench.py", "--gpus", "2", "--config", "c2", "--steps", "10", "--warmup", "3", "--comm", "torch",
-                      "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--no-converge", "--no-traffic"])
+                      "--backend", "gloo", "--same-gpu", "--full", "--no-cpu-baseline", "--no-converge", "--no-traffic"])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 10 and line["scaling"] == "strong"
@@ -125,7 +125,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "c2", "--steps", "10", "--warmup", "3",
-                        "--comm", "torch", "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--no-converge",
+                        "--comm", "torch", "--backend", "gloo", "--same-gpu", "--full", "--no-cpu-baseline", "--no-converge",
                         "--no-traffic"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -148,7 +148,7 @@ def test_bench_draws_c5_per_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "c5-small", "--steps", "6", "--warmup", "2",
-                        "--comm", "torch", "--backend", "gloo", "--same-gpu", "--no-cpu-baseline", "--no-converge",
+                        "--comm", "torch", "--backend", "gloo", "--same-gpu", "--full", "--no-cpu-baseline", "--no-converge",
                         "--no-traffic"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -181,7 +181,7 @@ def test_bench_line_over_ranks(world):
     finite rate and a loss that moved (world = 1: the same sharded driver with one rank)."""
     need_gpus(world)
     r = _torchrun(world, ["bench.py", "--gpus", str(world), "--config", "c2", "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline", "--no-converge", "--no-traffic"] + (["--force-sharded"] if world == 1 else []))
+                          "--full", "--no-cpu-baseline", "--no-converge", "--no-traffic"] + (["--force-sharded"] if world == 1 else []))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == world and line["steps"] == 20
@@ -196,7 +196,7 @@ def test_bench_falls_back_to_the_torch_collective(world):
     same protocol, and the line says so instead of the run ending without one."""
     need_gpus(world)
     r = _torchrun(world, ["bench.py", "--gpus", str(world), "--config", "c2", "--steps", "10", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-converge", "--no-traffic", "--fail-library-comm"]
+                          "--full", "--no-cpu-baseline", "--no-converge", "--no-traffic", "--fail-library-comm"]
                   + (["--force-sharded"] if world == 1 else []))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

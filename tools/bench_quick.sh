@@ -2,7 +2,7 @@
 # Quick bench lines on ONE box (no CPU baseline, no convergence fit, no counter passes): tools/bench_quick.sh <tag>
 tag=${1:-q}
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; O=gpurun_out
-B="--no-cpu-baseline --no-converge --no-traffic"
+B="--full --no-cpu-baseline --no-converge --no-traffic"
 python bench.py $B > $O/${tag}_bench_c3_f64.json 2> $O/${tag}_bench.err
 python bench.py --dtype f32 $B > $O/${tag}_bench_c3_f32.json 2>> $O/${tag}_bench.err
 python bench.py --config c5-shard --steps 30 --warmup 5 $B > $O/${tag}_bench_c5shard_f64.json 2>> $O/${tag}_bench.err

@@ -8,7 +8,7 @@ O=$R/gpurun_out/$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 name=$(echo $cfg | tr -d '-')_$dt
-BENCH="python $R/bench.py --config $cfg --dtype $dt --steps $steps --warmup 3 --no-cpu-baseline --no-converge --no-traffic"
+BENCH="python $R/bench.py --config $cfg --dtype $dt --steps $steps --warmup 3 --full --no-cpu-baseline --no-converge --no-traffic"
 w=$O/_work_$name
 rm -rf $w
 timeout 900 rocprofv3 --kernel-trace --stats -d $w -o st -- $BENCH > $O/bench_under_rocprof_$name.json 2> $w.log

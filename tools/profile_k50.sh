@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --config c5-shard --dtype $dt --steps 20 --warmup 3 --no-cpu-baseline --no-converge --no-traffic"
+BENCH="python $R/bench.py --config c5-shard --dtype $dt --steps 20 --warmup 3 --full --no-cpu-baseline --no-converge --no-traffic"
 rm -rf $O/${tag}_k50stats
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/${tag}_k50stats -o k50 -- $BENCH > $O/${tag}_bench_under_rocprof_c5shard_$dt.json 2> $O/${tag}_k50stats.log
 python $R/tools/rocpd_summary.py $(find $O/${tag}_k50stats -name "*.db" | head -1) > $O/${tag}_rocprofv3_kernel_stats_c5shard_$dt.txt 2>&1
@@ -31,7 +31,7 @@ for grp in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
   rm -rf $out
 done
 cd $R
-python bench.py --config c5-shard --dtype $dt --steps 60 --warmup 10 --no-cpu-baseline --no-converge --no-traffic > $O/${tag}_bench_c5shard_$dt.json 2> $O/${tag}_bench_c5shard_$dt.err
+python bench.py --config c5-shard --dtype $dt --steps 60 --warmup 10 --full --no-cpu-baseline --no-converge --no-traffic > $O/${tag}_bench_c5shard_$dt.json 2> $O/${tag}_bench_c5shard_$dt.err
 cat $O/${tag}_rocprofv3_kernel_stats_c5shard_$dt.txt | cut -c1-160 | head -14
 cat $O/${tag}_rocprofv3_pmc_traffic_c5shard_$dt.txt $O/${tag}_rocprofv3_pmc_sq_counters_c5shard_$dt.txt
 tail -1 $O/${tag}_bench_c5shard_$dt.json | cut -c1-600

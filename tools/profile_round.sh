@@ -13,9 +13,9 @@ if [ "$mode" = "full" ]; then
   timeout 2400 python -m pytest tests/ -x -q -m gpu --durations=15 > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -22 $O/pytest_gpu.log | cut -c1-200
   timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err; echo "driver-style rc $?"
 fi
-B="--no-cpu-baseline --no-converge --no-traffic"
-python bench.py --steps 100 --warmup 10 > $O/bench_c3_f64.json 2> $O/bench.err
-python bench.py --dtype f32 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_c3_f32.json 2>> $O/bench.err
+B="--full --no-cpu-baseline --no-converge --no-traffic"
+python bench.py --full --steps 100 --warmup 10 > $O/bench_c3_f64.json 2> $O/bench.err
+python bench.py --full --dtype f32 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_c3_f32.json 2>> $O/bench.err
 python bench.py --config c2 $B > $O/bench_c2_f64.json 2>> $O/bench.err
 python bench.py --config c2 --dtype f32 $B > $O/bench_c2_f32.json 2>> $O/bench.err
 python bench.py --config c5-shard --steps 60 --warmup 10 $B > $O/bench_c5shard_f64.json 2>> $O/bench.err
