@@ -19,6 +19,7 @@
 #include "../../include/schpf_hip.h"
 #include "kernels.h"
 #include "plan.h"
+#include "policy.h"
 
 namespace {
 
@@ -113,12 +114,6 @@ template <typename U, typename A> void upload(DevBuf &b, const std::vector<U, A>
     if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, st));
 }
 
-int env_int(const char *name, int dflt)
-{
-    const char *s = getenv(name);
-    return (s && *s) ? atoi(s) : dflt;
-}
-
 struct PlanDev {
     schpf::SweepPlanHost host;  // entries cleared after upload; order/mptr/cptr kept
     DevBuf entries, slice_off, slice_steps, chunk_major, chunk_natid, wave_slice, cptr, partials;
@@ -134,7 +129,6 @@ struct TileDev {
     DevBuf llh_block, llh_w0, llh_w1, llh_stage_end, llh_wave_off, llh_order;
     int64_t n_llh_tasks = 0;
     double llh_model = 0.0;     // modelled length of the loss pass on this plan, in step units (0: unknown)
-    int llh_parts = 1;          // sub-ranges per task the model chose for the loss pass
     DevBuf minor_of;            // balanced windows (plan.h): [n_blocks * n_virtual] table row staged at a window position, or empty
     int n_virtual = 0;
     DevBuf order_dev;           // device-built plans: (major, minor)-sorted position -> caller's COO position
@@ -285,6 +279,7 @@ struct schpf_ctx {
 namespace {
 
 template <typename T> struct Engine final : schpf_ctx {
+    const schpf::Tuning tuning = schpf::tuning_from_env();   // the switches, read once at schpf_create
     // variational parameters (C-contiguous, stride K)
     DevBuf xi_s, xi_r, th_s, th_r, eta_s, eta_r, be_s, be_r;
     // tables, stride KP, padding columns zero
@@ -384,7 +379,8 @@ template <typename T> struct Engine final : schpf_ctx {
             if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
                 cu_count = prop.multiProcessorCount;
         }
-        choose_config();
+        const schpf::Config cfg = schpf::choose_config(K, (int)sizeof(T), tuning);
+        want_tile = cfg.tile; LPC = cfg.LPC; NV = cfg.NV; KL = cfg.KL; KP = cfg.KP;
         const size_t s = sizeof(T);
         dual_queue.alloc(2 * sizeof(int), true, stream);
         clock_probe.alloc(8 * sizeof(unsigned long long), true, stream);
@@ -461,7 +457,7 @@ template <typename T> struct Engine final : schpf_ctx {
     void steps(unsigned flags_, int n) override
     {
         if (n < 0) throw std::invalid_argument("n must be >= 0");
-        const bool graphable = env_int("SCHPF_GRAPH", 1) && !prof.on && stream != nullptr && pending_init == 0 &&
+        const bool graphable = tuning.graph && !prof.on && stream != nullptr && pending_init == 0 &&
                                eager_since_upload && !dirty_theta && !dirty_beta && !(flags_ & SCHPF_SHARDED);
         int done = 0;
         if (graphable && n >= 2) {
@@ -505,7 +501,7 @@ template <typename T> struct Engine final : schpf_ctx {
         // communicator, which is all this build could ever run it with; with more ranks every rank must replay the same
         // graph, so there it stays opt-in (SCHPF_GRAPH_SHARDED=1) until tests/test_multigpu.py has seen two GPUs.
         int done = 0;
-        const bool graphable = env_int("SCHPF_GRAPH_SHARDED", comm_world == 1 ? 1 : 0) && !prof.on && stream != nullptr &&
+        const bool graphable = tuning.graph_sharded.value_or(comm_world == 1) && !prof.on && stream != nullptr &&
                                pending_init == 0 && eager_since_upload && !dirty_theta && !dirty_beta && !freeze;
         if (graphable && n >= 2) {
             const int even = n & ~1;
@@ -539,57 +535,6 @@ template <typename T> struct Engine final : schpf_ctx {
         (void)hipStreamSynchronize(stream);
         if (loss_host) (void)hipHostFree(loss_host);
         if (own_stream) (void)hipStreamDestroy(stream);
-    }
-
-    // Row layout of the tables the sweeps read: KP = NV * LPC * VEC values (VEC = values per 16 B);
-    // a group of LPC lanes shares one row, lane `sub` holding the 16-byte vectors q*LPC + sub.
-    //  * tile plan (LDS-staged): VALU work per nonzero has a fixed part (reciprocal, cross-lane
-    //    sum, addressing) that every lane of the group repeats, so rows are split over as FEW
-    //    lanes as the register budget allows: the smallest LPC with <= 112 row bytes per lane
-    //    (measured on C3: f64 K=20 -> LPC 2, f32 K=20 -> LPC 1; profiles/r01/explore*.log);
-    //  * gather plan (L2): the L1 path is charged per 64-byte sector touched, so the cost model
-    //    is accesses per nonzero = NV * max(1, LPC/4) and LPC = 4 usually wins.
-    void choose_config()
-    {
-        if (K < 1 || K > 256) throw std::invalid_argument("nfactors must be in [1, 256]");
-        const int vec = 16 / (int)sizeof(T);
-        const int nvec = (K + vec - 1) / vec;
-        static const int nv_ok[] = {1, 2, 3, 4, 5, 6, 7, 8, 10};
-        const char *pk = getenv("SCHPF_PLAN");
-        want_tile = (size_t)nvec * 16 <= 1024;          // at least ~150 rows per 152 KiB window
-        if (pk && !strcmp(pk, "gather")) want_tile = false;
-        if (pk && !strcmp(pk, "tile")) want_tile = true;
-        const int force_lpc = env_int("SCHPF_LPC", 0);
-        int best_lpc = 0, best_nv = 0, best_cost = 1 << 30;
-        static const int order_tile[] = {1, 2, 4, 8, 16};
-        static const int order_gather[] = {4, 8, 2, 16, 1};
-        for (int lpc : (want_tile ? order_tile : order_gather)) {
-            if (force_lpc && lpc != force_lpc) continue;
-            const int need = (nvec + lpc - 1) / lpc;
-            int nv = 0;
-            for (int v : nv_ok) if (v >= need) { nv = v; break; }
-            if (!nv) continue;
-            int cost;
-            if (want_tile && nv > 7) continue;                 // the tile sweeps are instantiated for <= 7 vectors
-            if (want_tile) cost = (nv * 16 <= 112 || force_lpc) ? 0 : 1 << 20;   // first that fits
-            else cost = nv * std::max(1, lpc / 4);
-            // only instantiated pairs (kernels.h): the planner's own choices always are, a forced LPC may not be
-            if (!(want_tile ? schpf::tile_combo_ok(nv, lpc) : schpf::gather_combo_ok(nv, lpc))) continue;
-            if (cost < best_cost) { best_cost = cost; best_lpc = lpc; best_nv = nv; }
-        }
-        if (!best_lpc) throw std::invalid_argument("SCHPF_LPC must be one of 1,2,4,8,16, fit nfactors and be an "
-                                                   "instantiated shape (kernels.h tile_combo_ok / gather_combo_ok)");
-        LPC = best_lpc; NV = best_nv; KL = NV * vec; KP = KL * LPC;
-    }
-
-    static int pick_windows(size_t table_bytes, const char *envname)
-    {
-        int w = env_int(envname, 0);
-        if (w > 0) return w;
-        const size_t budget = (size_t)env_int("SCHPF_L2_BUDGET_KB", 2048) * 1024;
-        w = 1;
-        while ((table_bytes + w - 1) / w > budget && w < 4096) w *= 2;
-        return w;
     }
 
     void build_plan(PlanDev &pd, int64_t nnz_, const int32_t *major, const int32_t *minor, const float *val,
@@ -627,93 +572,30 @@ template <typename T> struct Engine final : schpf_ctx {
         upload(td.entries, h.entries, stream);
         upload(td.steps, h.steps, stream);
         finish_tile(td);
-        if (env_int("SCHPF_VERBOSE", 0))
+        if (tuning.verbose)
             fprintf(stderr, "[schpf_hip]   tile plan %d x %d: host build %.3f s, H2D %.3f s (%.2f GB entries)\n",
                     h.n_major, h.n_minor, host_seconds, now_s() - t1, h.entries.size() * 4e-9);
         schpf::BigVec<uint32_t>().swap(h.entries);
     }
 
-    // Tasks of the loss pass.  The iteration's task ranges are chosen for the merged launch of both orientations and for
-    // few partial rows (C3 f64: ONE range per cell block = 196 tasks on 256 compute units -- a loss pass over them ran
-    // 0.42 ms where half a dual launch is 0.32); the loss pass keeps no partial rows, so every task's window range may be
-    // cut into `parts` sub-ranges (never below two windows / four sub-windows per sub-task: a first window costs a staging
-    // and the major rows).  `parts` is the count in 1..8 with the shortest modelled pass: the sub-tasks, longest first,
-    // on the resident workgroups (list schedule), a sub-task = its barrier-limited steps + two per window + a fixed cost.
-    // What decides is the last round: 784 equal tasks on 256 workgroups take four rounds, not 3.06 (measured: 0.46 ms
-    // against 0.41 for the gene-side plan's 640).  The modelled time also picks the plan (loss_side).  Needs the host
-    // copies of steps / task_wave_off.
+    // Tasks of the loss pass: the sub-ranges of the iteration's tasks that policy.cpp loss_cut chose, longest first
     void loss_tasks(TileDev &td)
     {
         auto &h = td.host;
         td.n_llh_tasks = 0;
-        td.llh_model = 0.0;
         for (DevBuf *b : {&td.llh_block, &td.llh_w0, &td.llh_w1, &td.llh_stage_end, &td.llh_wave_off, &td.llh_order}) b->release();
-        if (h.n_tasks <= 0 || h.steps.empty() || h.task_wave_off.empty()) return;
-        // a matrix that is replaced every iteration (minibatch engines: schpf_hint_transient, schpf_upload_rows) is planned the
-        // cheapest way, and batch engines never evaluate the loss themselves
-        if (transient || planning_batch_rows) return;
+        const schpf::LossCut cut = schpf::loss_cut(problem(), tuning, h);
+        td.llh_model = cut.model;
+        if (cut.parts <= 1) return;
         const int wpb = h.wpb, W = h.n_windows;
-        const size_t lds = h.ring > 1 ? (size_t)h.ring * h.slot16 * 16 : (size_t)h.win_rows * KP * sizeof(T);
-        const int resident = n_cu() * per_cu(lds);
-        const int min_windows = h.ring > 1 ? 4 : 2;   // sub-windows of the half-window schedule are half as long
-        const double task_cost = (double)env_int("SCHPF_LOSS_TASK_STEPS", 8);
-        // barrier-limited steps (+ 2) of every (block, window)
-        std::vector<int32_t> wwork((size_t)h.n_blocks * W);
-        for (int64_t b = 0; b < h.n_blocks; ++b)
-            for (int w = 0; w < W; ++w) {
-                int mx = 0;
-                for (int v = 0; v < wpb; ++v) mx = std::max<int>(mx, h.steps[((size_t)b * wpb + v) * W + w]);
-                wwork[(size_t)b * W + w] = (int32_t)schpf::tile_stored_steps(h, mx) + 2;
-            }
-        auto cut_points = [&](int64_t t, int parts, std::vector<int> &cuts) {   // sub-range starts of task t, + its end
-            const int a0 = h.task_w0[(size_t)t], a1 = h.task_w1[(size_t)t];
-            const int n = std::max(1, std::min(parts, (a1 - a0) / min_windows));
-            cuts.clear();
-            for (int p = 0; p <= n; ++p) cuts.push_back(a0 + (int)((int64_t)(a1 - a0) * p / n));
-        };
+        const std::vector<int32_t> &wwork = cut.window_work;
         std::vector<int> cuts;
-        std::vector<double> dur, load;
-        auto model = [&](int parts) {
-            dur.clear();
-            for (int64_t t = 0; t < h.n_tasks; ++t) {
-                cut_points(t, parts, cuts);
-                const int32_t *ww = wwork.data() + (size_t)h.task_block[(size_t)t] * W;
-                for (size_t p = 0; p + 1 < cuts.size(); ++p) {
-                    double d = task_cost;
-                    for (int w = cuts[p]; w < cuts[p + 1]; ++w) d += ww[w];
-                    dur.push_back(d);
-                }
-            }
-            std::sort(dur.begin(), dur.end(), std::greater<double>());
-            load.assign((size_t)resident, 0.0);
-            std::make_heap(load.begin(), load.end(), std::greater<double>());
-            for (double d : dur) {
-                std::pop_heap(load.begin(), load.end(), std::greater<double>());
-                load.back() += d;
-                std::push_heap(load.begin(), load.end(), std::greater<double>());
-            }
-            return *std::max_element(load.begin(), load.end());
-        };
-        int best_parts = 1;
-        const double uncut = model(1);
-        double best = uncut;
-        if (env_int("SCHPF_LOSS_SPLIT", 1))
-            for (int parts = 2; parts <= 8; ++parts) {
-                const double m = model(parts);
-                if (m < 0.97 * best) { best = m; best_parts = parts; }   // a cut has to pay for itself
-            }
-        td.llh_model = best;
-        if (env_int("SCHPF_VERBOSE", 0))
-            fprintf(stderr, "[schpf_hip]   loss pass on the %d x %d plan: %d sub-range(s) per task, modelled %.0f step units (uncut %.0f)\n",
-                    h.n_major, h.n_minor, best_parts, best, uncut);
-        td.llh_parts = best_parts;
-        if (best_parts <= 1) return;
         std::vector<int32_t> blk, w0s, w1s, ends, order;
         std::vector<int64_t> woff;
         std::vector<double> work;
         for (int64_t t = 0; t < h.n_tasks; ++t) {
             const int b = h.task_block[(size_t)t], a1 = h.task_w1[(size_t)t];
-            cut_points(t, best_parts, cuts);
+            schpf::loss_cut_points(h, t, cut.parts, cuts);
             std::vector<int64_t> off((size_t)wpb);
             for (int v = 0; v < wpb; ++v) off[(size_t)v] = h.task_wave_off[(size_t)t * wpb + v];
             for (size_t p = 0; p + 1 < cuts.size(); ++p) {
@@ -769,7 +651,7 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         const double t0 = now_s();
         int ranges[2] = {0, 0}, half[2] = {-1, -1};
-        if (!choose_ranges(row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
+        if (!schpf::choose_ranges(problem(), tuning, row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
         bool rc_sorted = true, cr_sorted = true;
         schpf::coo_order_flags(nnz, row, col, rc_sorted, cr_sorted);
         DevBuf d_val;
@@ -792,7 +674,7 @@ template <typename T> struct Engine final : schpf_ctx {
             rows_packed_ok = packed_ok;
             HIPCHK(hipStreamSynchronize(stream));
         }
-        if (env_int("SCHPF_VERBOSE", 0))
+        if (tuning.verbose)
             fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
                     "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
                     t1 - t0, early.seconds, now_s() - t1, (tcell.entries.bytes + tgene.entries.bytes) * 1e-9);
@@ -802,11 +684,11 @@ template <typename T> struct Engine final : schpf_ctx {
     void plans_from_device_coo(const DevBuf &d_row, const DevBuf &d_col, const DevBuf &d_val, bool rc_sorted,
                                bool cr_sorted, bool packed_ok, const int ranges[2], const int half[2])
     {
-        const schpf::TileShape sh_c = tile_shape(N, G, false, ranges[0], half[0]),
-                               sh_g = tile_shape(G, N, true, ranges[1], half[1]);
+        const schpf::TileShape sh_c = schpf::tile_shape(problem(), tuning, N, G, ranges[0], half[0]),
+                               sh_g = schpf::tile_shape(problem(), tuning, G, N, ranges[1], half[1]);
         // the two orientations are independent (the COO is only read): the gene side on a helper thread with a
         // stream of its own, so that the builders' host round trips (run pointers, step counts, allocations) and
-        // their short kernels overlap instead of adding up (SCHPF_PLAN_THREADS=1: one after the other)
+        // their short kernels overlap instead of adding up
         auto build_side = [&](int side, hipStream_t st) {
             TileDev &td = side == 0 ? tcell : tgene;
             void *e = nullptr, *s = nullptr, *o = nullptr;
@@ -834,7 +716,7 @@ template <typename T> struct Engine final : schpf_ctx {
                 } catch (const std::exception &e) {
                     (void)hipGetLastError();
                     balanced = false;
-                    if (env_int("SCHPF_VERBOSE", 0))
+                    if (tuning.verbose)
                         fprintf(stderr, "[schpf_hip]   balanced windows, side %d: not built (%s); windows by index\n", side, e.what());
                 }
                 if (balanced) {
@@ -844,7 +726,7 @@ template <typename T> struct Engine final : schpf_ctx {
                     n_minor_plan = geo.n_virtual;
                     presorted = false;
                 } else vminor.release();
-                if (env_int("SCHPF_VERBOSE", 0))
+                if (tuning.verbose)
                     fprintf(stderr, "[schpf_hip]   balanced windows, side %d: %d sections of %d windows, %.3f s\n", side,
                             geo.n_sections, geo.D, now_s() - tb);
             }
@@ -858,27 +740,22 @@ template <typename T> struct Engine final : schpf_ctx {
             td.entry_slots = (int64_t)(eb / 4) / (td.host.packed ? 1 : 2);
         };
         HIPCHK(hipStreamSynchronize(stream));   // the COO is on the device before either builder reads it
-        if (env_int("SCHPF_PLAN_THREADS", 2) >= 2) {
-            std::exception_ptr err;
-            std::thread helper([&] {
+        std::exception_ptr err;
+        std::thread helper([&] {
+            try {
+                HIPCHK(hipSetDevice(device));
+                hipStream_t st2 = nullptr;
+                HIPCHK(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
                 try {
-                    HIPCHK(hipSetDevice(device));
-                    hipStream_t st2 = nullptr;
-                    HIPCHK(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-                    try {
-                        build_side(1, st2);
-                        HIPCHK(hipStreamSynchronize(st2));
-                    } catch (...) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); throw; }
-                    (void)hipStreamDestroy(st2);
-                } catch (...) { err = std::current_exception(); }
-            });
-            try { build_side(0, stream); } catch (...) { helper.join(); throw; }
-            helper.join();
-            if (err) std::rethrow_exception(err);
-        } else {
-            build_side(0, stream);
-            build_side(1, stream);
-        }
+                    build_side(1, st2);
+                    HIPCHK(hipStreamSynchronize(st2));
+                } catch (...) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); throw; }
+                (void)hipStreamDestroy(st2);
+            } catch (...) { err = std::current_exception(); }
+        });
+        try { build_side(0, stream); } catch (...) { helper.join(); throw; }
+        helper.join();
+        if (err) std::rethrow_exception(err);
         finish_tile(tcell);
         finish_tile(tgene);
         build_dual_order();
@@ -930,182 +807,11 @@ template <typename T> struct Engine final : schpf_ctx {
         eager_since_upload = false;
     }
 
-    // Workgroup shape of the tile sweep.  One 1024-thread workgroup per CU with a 152 KiB window
-    // (fewest stagings, longest row segments => least sliced-ELL padding) unless that leaves fewer
-    // than 256 (block, window) pairs per orientation; then the workgroup is halved (64 KiB windows,
-    // two or more workgroups per CU) until there are, down to 256 threads.  Measured with the graph /
-    // persistent launches of round 2 (profiles/r02/explore_c2_shapes.log): C2 (10k x 5k) 256-thread
-    // workgroups 24.6 k -> 26.7 k it/s in f64, -4 % per iteration in f32 (128 threads: +5 %, hence the
-    // floor); a 1/8 shard of C3 keeps the large workgroup in f64 (525 pairs) and halves it in f32 (-3 %).
     int cu_count = 256;
-    int n_cu() const { return cu_count; }
-    // workgroups of a tile sweep that fit a compute unit at once.  Sized by the LOSS pass's LDS (window + the 1 KiB
-    // logarithm table behind it, run_sweep): the PHI and LLH launches of a plan must agree on the residency
-    static int per_cu(size_t window_lds_bytes) { return window_lds_bytes + 1024 > 80 * 1024 ? 1 : 2; }
-    void pick_workgroup(int n_major, int n_minor, int &wpb, int &lds_kb) const
+    schpf::Problem problem() const
     {
-        wpb = env_int("SCHPF_WPB", 0);
-        // <= 158 KiB: the loss pass adds a 1 KiB table behind the window and the kernels opt in to 159 KiB
-        lds_kb = std::min(env_int("SCHPF_LDS_KB", 0), 158);
-        const size_t row_bytes = (size_t)KP * sizeof(T);
-        if (!wpb) {
-            wpb = 16;
-            for (;;) {
-                const int kb = lds_kb ? lds_kb : (wpb >= 12 ? 152 : 64);
-                const int64_t wr = std::max<int64_t>(1, (int64_t)kb * 1024 / (int64_t)row_bytes);
-                const int64_t blocks = ((int64_t)n_major + (64 / LPC) * wpb - 1) / ((64 / LPC) * wpb);
-                const int64_t windows = ((int64_t)n_minor + wr - 1) / wr;
-                if (blocks * windows >= env_int("SCHPF_MIN_PAIRS", 256) || wpb <= 4) break;
-                wpb /= 2;
-            }
-        }
-        if (!lds_kb) lds_kb = wpb >= 12 ? 152 : 64;
-    }
-    // Task ranges of both orientations of the one-launch iteration from the list-schedule model of
-    // plan.h choose_task_ranges (big problems with the 1024-thread workgroup on both sides; knobs that fix
-    // task counts or schedules by hand switch it off).  Constants from C3 on an MI355X: a workgroup works
-    // through ~1.7e11 / (K sizeof(T)) nonzeros per second (K = 20: 1.06e9 f64, 2.1e9 f32; measured 1.07 /
-    // 1.9), a partial row is written and read back at ~3.5 TB/s, a task costs 3 us beside its nonzeros
-    // (SCHPF_TASK_US; swept 2-16: 2-4 pick one range per cell block and 18 per gene block at C3 f64, the
-    // fastest measured).  Against the former fixed counts (profiles/r02/explore_task_ranges.log), per
-    // iteration: C3 f64 (6, 13) -> (1, 18) ranges -2.4 %, C3 f32 (3, 13) -> (3, 11) -3.3 %, half of C3's
-    // cells -7.5 %, a quarter -3 %, the C5 share -1..2 % (f64) / -4 % (f32).
-    bool choose_ranges(const int32_t *row, const int32_t *col, int ranges[2], int half[2]) const
-    {
-        if (!env_int("SCHPF_RANGES", 1) || (!expect_sharded && !env_int("SCHPF_DUAL", 1))) return false;
-        for (const char *knob : {"SCHPF_TASKS", "SCHPF_TASKS_CELL", "SCHPF_TASKS_GENE"})
-            if (getenv(knob) && *getenv(knob)) return false;
-        const int half_env = env_int("SCHPF_HALF", -1);
-        if (half_env >= 2) return false;
-        const size_t row_bytes = (size_t)KP * sizeof(T);
-        const int n_maj[2] = {N, G}, n_min[2] = {G, N};
-        int64_t blocks[2], half_windows[2];
-        bool half_ok[2];
-        double partial_seconds[2];
-        for (int s = 0; s < 2; ++s) {
-            int wpb, lds_kb;
-            pick_workgroup(n_maj[s], n_min[s], wpb, lds_kb);
-            if (wpb < 12) return false;
-            const int64_t half_rows = ((int64_t)lds_kb * 512 - 64) / (int64_t)row_bytes;
-            if (half_rows < 1) return false;
-            blocks[s] = ((int64_t)n_maj[s] + (64 / LPC) * wpb - 1) / ((64 / LPC) * wpb);
-            half_windows[s] = ((int64_t)n_min[s] + half_rows - 1) / half_rows;
-            const double per_row = (double)nnz / std::max(1, n_maj[s]) * (double)half_rows / std::max(1, n_min[s]);
-            half_ok[s] = half_env != 0 && per_row >= 16.0 && !balance_now;
-            partial_seconds[s] = 2.0 * (double)n_maj[s] * (double)row_bytes / 3.5e12;
-        }
-        const int resident = n_cu();
-        // only where a launch is several rounds of workgroups (1/8 of C3: -4 % in one launch, +-0 in two): smaller
-        // problems keep the rules of tile_shape
-        if (blocks[0] * half_windows[0] + blocks[1] * half_windows[1] < env_int("SCHPF_RANGES_MIN", 6) * (int64_t)resident)
-            return false;
-        // where the nonzeros sit: a skewed matrix has heavy blocks (the planted benchmark matrix: one range per
-        // cell block -- the uniform model's choice -- doubles the iteration, its heaviest block runs last)
-        std::vector<double> share[2];
-        const int64_t stride = std::max<int64_t>(1, nnz / 4000000);   // ~4 M samples per orientation: a few ms
-        {   // the blocks the plans will cut: rows per block follow the workgroup (a forced SCHPF_WPB=12 has 12 waves)
-            int wpb, lds_kb;
-            pick_workgroup(N, G, wpb, lds_kb);
-            share[0] = schpf::block_shares(nnz, row, N, (64 / LPC) * wpb, stride);
-            pick_workgroup(G, N, wpb, lds_kb);
-            share[1] = schpf::block_shares(nnz, col, G, (64 / LPC) * wpb, stride);
-        }
-        const schpf::RangeChoice c = schpf::choose_task_ranges(blocks, half_windows, half_ok, share, (double)nnz, resident,
-                                                               1.7e11 / ((double)K * sizeof(T)), 1e-6 * env_int("SCHPF_TASK_US", 3),
-                                                               partial_seconds,
-                                                               expect_sharded ? 4 : 6, balance_now ? 1.0 : 1.12, 32, expect_sharded,
-                                                               env_int("SCHPF_TAPER", 30) / 100.0);
-        if (c.ranges[0] <= 0 || c.ranges[1] <= 0) return false;
-        for (int s = 0; s < 2; ++s) { ranges[s] = c.ranges[s]; half[s] = c.half[s] ? 1 : 0; }
-        // exploration: fix the ranges by hand, keep the model's schedules (tools/explore.py)
-        if (env_int("SCHPF_RANGES_CELL", 0) > 0) ranges[0] = env_int("SCHPF_RANGES_CELL", 0);
-        if (env_int("SCHPF_RANGES_GENE", 0) > 0) ranges[1] = env_int("SCHPF_RANGES_GENE", 0);
-        if (env_int("SCHPF_VERBOSE", 0))
-            fprintf(stderr, "[schpf_hip]   task ranges from the list-schedule model: cell %d (%s), gene %d (%s), %.3f ms\n",
-                    ranges[0], half[0] ? "half windows" : "windows", ranges[1], half[1] ? "half windows" : "windows",
-                    c.seconds * 1e3);
-        return true;
-    }
-    schpf::TileShape tile_shape(int n_major, int n_minor, bool gene_side = false, int ranges = 0,
-                                int force_half = -1) const
-    {
-        int wpb, lds_kb;
-        pick_workgroup(n_major, n_minor, wpb, lds_kb);
-        const size_t row_bytes = (size_t)KP * sizeof(T);
-        schpf::TileShape sh;
-        sh.lpc = LPC;
-        sh.waves_per_block = wpb;
-        sh.row_slots = (int)(row_bytes / 16);
-        sh.bank_order = env_int("SCHPF_BANK_ORDER", 2);   // 0 minor order, 1 per row, 2 jointly per LDS pass (plan.h)
-        sh.allow_packed = env_int("SCHPF_PACK", 1) != 0;
-        sh.taper = env_int("SCHPF_TAPER", 30) / 100.0;   // window ranges of unequal length (plan.h tile_range_starts), per cent
-        sh.win_rows = (int)std::max<size_t>(1, (size_t)lds_kb * 1024 / row_bytes);
-        // tasks per orientation: a few rounds of the 256 CUs for big problems; about one round when
-        // there are few (block, window) pairs (1/8 shard of C3: 1024 -> 256 tasks is 10 % faster:
-        // fewer partial rows to write and to sum, no ragged second round)
-        const int64_t full_rows = sh.ring > 1 ? (int64_t)sh.win_rows * (sh.ring - 1) : sh.win_rows;
-        const int64_t blocks = ((int64_t)n_major + (64 / LPC) * wpb - 1) / ((64 / LPC) * wpb);
-        const int64_t windows = ((int64_t)n_minor + full_rows - 1) / full_rows;
-        // ... and half as many for an orientation with few blocks (the gene side of C3: 40 blocks of 512
-        // genes): 1024 tasks there are 26 window ranges per block = 26 partial rows per gene to write and
-        // to sum; 512 measured -3.5 % sweep, -15 % update time (profiles/r02/explore_tasks_per_side.log)
-        int dflt = blocks * windows >= 2048 ? (wpb >= 12 ? 1024 : 2048) : 256;
-        if (dflt >= 1024 && blocks < 64) dflt /= 2;
-        sh.target_tasks = env_int("SCHPF_TASKS", dflt);
-        sh.target_tasks = env_int(gene_side ? "SCHPF_TASKS_GENE" : "SCHPF_TASKS_CELL", sh.target_tasks);
-        // Half-window schedule (plan.h): the window's LDS cut into two slots, refilled at the epoch boundary
-        // by the window kernel itself.  Chosen per orientation where it was measured to pay
-        // (profiles/r02/explore_half_window.log, explore_half_midsize.log):
-        //  * rows with many nonzeros per half window -- the lock-step loss is what it removes; with ~3 per
-        //    half window (C5) the second barrier per window costs more;
-        //  * the 1024-thread workgroup (64 KiB windows halved lose 5 %);
-        //  * tasks long enough to work ahead in: the horizon ends with the task and a task's first epoch
-        //    fills both slots.  >= 6 half windows per task in the one-launch iteration (C3 8 / 16: -2..3 %;
-        //    half of C3's cells 4 / 8: the cell side +1..4 % with it; 1/8: +2 %), >= 4 in the two-launch
-        //    iteration of a row shard (1/8 of C3: sweeps 2 x 70 -> 2 x 63 us).
-        // SCHPF_HALF = 0 / slots overrides.
-        // one-nonzero-at-a-time kernels (sweep_impl.h: rows wider than 96 bytes per lane in the 1024-thread workgroup --
-        // the rolling loop in float64, the plain loop in float32) count their steps in nonzeros wherever rows do not
-        // work ahead
-        const bool one_at_a_time = (size_t)KL * sizeof(T) > 96 && wpb >= 12;
-        sh.single = one_at_a_time && env_int("SCHPF_SINGLE", 1) != 0;
-        {
-            const int half_env = env_int("SCHPF_HALF", -1);
-            int n_slots = half_env >= 2 ? half_env : 0;
-            // balanced windows are whole windows (plan.h).  Decided for the upload, not per side: the library only
-            // balances matrices with < 24 nonzeros per row and whole window, i.e. < 12 per half window, where the rule
-            // below (>= 16) would not pick half windows either -- a side that then is NOT balanced (too small a
-            // workgroup, no memory for the scratch) gets the same whole index-cut windows it would have got without
-            // balancing.  Only a forced SCHPF_BALANCE=1 on a dense matrix can lose the half-window schedule this way.
-            if (balance_now && half_env < 2) n_slots = 0;
-            else if (force_half >= 0) n_slots = force_half ? 2 : 0;
-            else if (half_env < 0 && sh.ring <= 1 && wpb >= 12) {
-                const int64_t half_rows = ((int64_t)lds_kb * 512 - 64) / (int64_t)row_bytes;
-                if (half_rows >= 1) {
-                    const double per_row = (double)nnz / std::max(1, n_major) * (double)half_rows / std::max(1, n_minor);
-                    const int64_t half_windows = ((int64_t)n_minor + half_rows - 1) / half_rows;
-                    const int64_t per_task = half_windows * blocks / std::max(1, sh.target_tasks);   // plan.cpp: wpt
-                    if (per_row >= 16.0 && per_task >= (expect_sharded ? 4 : 6)) n_slots = 2;
-                }
-            }
-            if (n_slots >= 2 && sh.ring <= 1) {
-                const int slot_bytes = (int)((size_t)lds_kb * 1024 / (size_t)n_slots / 16 * 16);
-                const int64_t sub_rows = ((int64_t)slot_bytes - 64) / (int64_t)row_bytes;
-                if (sub_rows >= 1) {
-                    sh.ring = n_slots;
-                    sh.sync_stage = 1;
-                    sh.slot_bytes = slot_bytes;
-                    sh.win_rows = (int)sub_rows;
-                    sh.single = false;   // rows work ahead: pairs
-                }
-            }
-        }
-        // workgroups in flight: one 1024-thread (152 KiB) workgroup per CU, two of the smaller ones; both
-        // orientations share a launch unless the iteration is sharded (two launches, schpf_hint_sharded)
-        const int per_launch = n_cu() * (wpb >= 12 ? 1 : 2);
-        sh.slots = env_int("SCHPF_TASK_ROUNDING", 1) ? (expect_sharded ? per_launch : per_launch / 2) : 0;
-        sh.ranges = ranges;
-        return sh;
+        return {N, G, K, (int)sizeof(T), nnz, cu_count, LPC, NV, KL, KP, expect_sharded, transient, want_rows,
+                planning_batch_rows, balance_now};
     }
 
     // both orientations are built concurrently on the host (each with its own thread team),
@@ -1113,9 +819,9 @@ template <typename T> struct Engine final : schpf_ctx {
     void build_tiles(const int32_t *row, const int32_t *col, const float *val)
     {
         int ranges[2] = {0, 0}, half[2] = {-1, -1};
-        if (!choose_ranges(row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
-        const schpf::TileShape sh_c = tile_shape(N, G, false, ranges[0], half[0]),
-                               sh_g = tile_shape(G, N, true, ranges[1], half[1]);
+        if (!schpf::choose_ranges(problem(), tuning, row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
+        const schpf::TileShape sh_c = schpf::tile_shape(problem(), tuning, N, G, ranges[0], half[0]),
+                               sh_g = schpf::tile_shape(problem(), tuning, G, N, ranges[1], half[1]);
         std::exception_ptr err;
         double secs_gene = 0.0;
         // balanced windows: the builder runs on the block's virtual numbering of the minor rows (plan.h)
@@ -1165,29 +871,18 @@ template <typename T> struct Engine final : schpf_ctx {
         // plans agree on the workgroup shape: slots = all tasks of both plans, longest first
         dual_slots = 0;
         dual_order.release();
-        if (env_int("SCHPF_DUAL", 1) && tcell.threads == tgene.threads && tcell.packed == tgene.packed &&
+        if (tuning.dual && tcell.threads == tgene.threads && tcell.packed == tgene.packed &&
             (tcell.n_virtual != 0) == (tgene.n_virtual != 0)) {
             const auto &hc = tcell.host, &hg = tgene.host;
             std::vector<int32_t> ord;
-            const int n_xcd = env_int("SCHPF_XCD", 1);
-            if (n_xcd > 1 && n_cu() % n_xcd == 0) {
-                // same-range tasks on one XCD at a time (plan.h xcd_launch_order); one 152 KiB workgroup per
-                // compute unit, two of the smaller ones.  Opt-in (SCHPF_XCD=8): it does what it is meant to --
-                // L2 hits of the sweep 47 % -> 83 % at the C5 share, 49 % -> 54 % at C3 -- and the sweep is no
-                // faster for it (C5 2.48 vs 2.42 ms, C3 f32 +10 %: coarser tail): the window copy is bound by
-                // the CU's own LDS-DMA rate, not by where the rows come from (tools/micro/stage_bench.hip)
-                const schpf::TilePlanHost *both[2] = {&hc, &hg};
-                schpf::xcd_launch_order(both, 2, n_xcd, n_cu() / n_xcd * per_cu(tcell.lds_bytes), ord);
-            } else {
-                ord.reserve((size_t)(hc.n_tasks + hg.n_tasks));
-                size_t i = 0, j = 0;   // merge of two lists already sorted by decreasing work
-                while (i < hc.task_order.size() || j < hg.task_order.size()) {
-                    const bool take_cell = j >= hg.task_order.size() ||
-                        (i < hc.task_order.size() &&
-                         hc.task_work[(size_t)hc.task_order[i]] >= hg.task_work[(size_t)hg.task_order[j]]);
-                    if (take_cell) ord.push_back(hc.task_order[i++]);
-                    else ord.push_back(~hg.task_order[j++]);
-                }
+            ord.reserve((size_t)(hc.n_tasks + hg.n_tasks));
+            size_t i = 0, j = 0;   // merge of two lists already sorted by decreasing work
+            while (i < hc.task_order.size() || j < hg.task_order.size()) {
+                const bool take_cell = j >= hg.task_order.size() ||
+                    (i < hc.task_order.size() &&
+                     hc.task_work[(size_t)hc.task_order[i]] >= hg.task_work[(size_t)hg.task_order[j]]);
+                if (take_cell) ord.push_back(hc.task_order[i++]);
+                else ord.push_back(~hg.task_order[j++]);
             }
             dual_slots = (int64_t)ord.size();
             if (dual_slots > 0) { upload(dual_order, ord, stream); HIPCHK(hipStreamSynchronize(stream)); }
@@ -1211,7 +906,6 @@ template <typename T> struct Engine final : schpf_ctx {
 
     void upload_coo(int64_t nnz_, const int32_t *row, const int32_t *col, const void *val, int kind) override
     {
-        const bool verbose = env_int("SCHPF_VERBOSE", 0) != 0;
         const double t_start = now_s();
         if (nnz_ < 0 || nnz_ >= (int64_t)1 << 31) throw std::invalid_argument("nnz must be < 2^31");
         if (kind < SCHPF_VAL_I32 || kind > SCHPF_VAL_F64) throw std::invalid_argument("unknown value kind");
@@ -1219,21 +913,13 @@ template <typename T> struct Engine final : schpf_ctx {
         // (a re-upload onto a live engine would otherwise peak at the old plans + the new indices), and an upload
         // that fails leaves an engine without a matrix, not one with half of the old one
         forget_matrix();
-        // Balanced windows where the rows are sparse in a window (on average under 24 nonzeros per row and 152 KiB window,
-        // both orientations: the C5 share has 7): there the lock-step padding is 45 % of the executed step slots and the
-        // balancing takes a quarter of the sweep's compute away; at C3 (49 per row and window) the half-window schedule
-        // already fills 0.87-0.93 of the slots and the row-list indirection of the staging costs what the rest would
-        // return (profiles/r04/ab_balanced_windows.txt).  SCHPF_BALANCE=1 / 0 forces it on / off.
         {
-            const int forced = env_int("SCHPF_BALANCE", -1);
-            const double win = 152.0 * 1024.0 / ((double)KP * sizeof(T));
-            const double per_row_cell = (double)nnz_ / std::max(1, N) * std::min(1.0, win / std::max(1, G));
-            const double per_row_gene = (double)nnz_ / std::max(1, G) * std::min(1.0, win / std::max(1, N));
-            const bool sparse = per_row_cell < 24.0 && per_row_gene < 24.0 && (double)G > 2.0 * win && (double)N > 2.0 * win;
-            balance_now = (forced < 0 ? sparse : forced != 0) && want_tile && !want_rows && !transient;
+            schpf::Problem p = problem();
+            p.nnz = nnz_;
+            balance_now = want_tile && schpf::balance_windows(p, tuning);
         }
         EarlyIndexCopy early;
-        const bool device_plans = want_tile && env_int("SCHPF_DEVICE_PLAN", 1);
+        const bool device_plans = want_tile && tuning.device_plan;
         if (device_plans) early.start(device, nnz_, row, col);
         schpf::BigVec<float> v((size_t)nnz_);   // no serial zero-fill: written by the threaded pass below
         bool packed_ok = true;
@@ -1286,16 +972,6 @@ template <typename T> struct Engine final : schpf_ctx {
         upload(zero_col, zcol, stream);
         const double t_valid = now_s();
         nnz = nnz_;
-        const int cpw = 64 / LPC;
-        int chunk = env_int("SCHPF_CHUNK", 0);
-        if (!chunk) {
-            const int64_t target_waves = 16384;
-            int64_t c = nnz / (target_waves * cpw);
-            chunk = 16;
-            while (chunk * 2 <= c && chunk < 256) chunk *= 2;
-        }
-        if (chunk < 2) chunk = 2;
-        chunk &= ~1;
         use_tile = want_tile;
         int64_t n_out;
         if (use_tile) {
@@ -1303,8 +979,9 @@ template <typename T> struct Engine final : schpf_ctx {
             else build_tiles(row, col, v.data());
             n_out = std::max(tcell.n_wave_out, tgene.n_wave_out);   // the loss pass sweeps either plan (loss_side)
         } else {
-            const int wc = pick_windows((size_t)G * KP * sizeof(T), "SCHPF_WINDOWS_CELL");
-            const int wg = pick_windows((size_t)N * KP * sizeof(T), "SCHPF_WINDOWS_GENE");
+            const int wc = schpf::pick_windows((size_t)G * KP * sizeof(T));
+            const int wg = schpf::pick_windows((size_t)N * KP * sizeof(T));
+            const int chunk = schpf::gather_chunk_len(problem());
             build_plan(cell, nnz, row, col, v.data(), N, G, wc, chunk);
             build_plan(gene, nnz, col, row, v.data(), G, N, wg, chunk);
             n_out = cell.n_waves;
@@ -1327,7 +1004,7 @@ template <typename T> struct Engine final : schpf_ctx {
         pending_init = 0;
         drop_graph();
         eager_since_upload = false;
-        if (verbose)
+        if (tuning.verbose)
             fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads)\n",
                     (long long)nnz, t_valid - t_start, t_plans - t_valid, now_s() - t_plans, schpf::host_threads());
     }
@@ -1479,9 +1156,9 @@ template <typename T> struct Engine final : schpf_ctx {
                 a.task_stage_end = td.llh_stage_end.as<int>(); a.task_wave_off = td.llh_wave_off.as<int64_t>();
                 n_tasks = td.n_llh_tasks;
             }
-            if (mode != schpf::MODE_RANDOM && env_int("SCHPF_PERSISTENT", 1)) {   // see step_local
+            if (mode != schpf::MODE_RANDOM && tuning.persistent) {   // see step_local
                 a.queue = dual_queue.as<int>();
-                a.resident = n_cu() * per_cu(td.lds_bytes);
+                a.resident = cu_count * schpf::per_cu(td.lds_bytes);
                 a.task_order = cut ? td.llh_order.as<int>() : td.task_order.as<int>();
             } else if (cut) a.task_order = td.llh_order.as<int>();
             // the loss pass keeps a 1 KiB logarithm table behind the window (sweep_impl.h LlhAccumulator)
@@ -1587,9 +1264,9 @@ template <typename T> struct Engine final : schpf_ctx {
             const size_t lds = std::max(tcell.lds_bytes, tgene.lds_bytes);
             int *queue = nullptr;
             int resident = 0;
-            if (env_int("SCHPF_PERSISTENT", 1)) {
+            if (tuning.persistent) {
                 queue = dual_queue.as<int>();
-                resident = n_cu() * per_cu(lds);
+                resident = cu_count * schpf::per_cu(lds);
             }
             HIPCHK(schpf::launch_tile_sweep_dual<T>(ac, ag, dual_order.as<int>(), NV, LPC, tcell.packed ? 1 : 0,
                                                     dual_slots, tcell.threads, lds, queue, resident, stream));
@@ -1633,7 +1310,7 @@ template <typename T> struct Engine final : schpf_ctx {
         ScopedTimer tm(prof, stream, 3);
         const bool cells_first = flags_ & SCHPF_CELLS_FIRST;
         // default ordering on a small problem: no reduce launches (BASELINE C2: 2 of its 5 launches)
-        const bool fuse = !sharded && !freeze && !simultaneous && !cells_first && env_int("SCHPF_FUSE_SUMS", 1) &&
+        const bool fuse = !sharded && !freeze && !simultaneous && !cells_first && tuning.fuse_sums &&
                           (int64_t)upd_blocks(N) * K <= 16384 && (int64_t)upd_blocks(G) * K <= 16384;
         if (!fuse && sums_stale) {   // s_theta / s_beta from the partials the last fused iteration left
             HIPCHK(schpf::launch_colsum_reduce(colpart_cell.as<double>(), upd_blocks(N), K, s_theta.as<double>(),
@@ -1730,20 +1407,14 @@ template <typename T> struct Engine final : schpf_ctx {
         *nnz_out = nnz;
     }
 
-    // The loss pass sweeps ONE plan, either will do (both hold every nonzero; r = sum_k E[theta] E[beta] is symmetric).
-    // The cell-side plan unless it has too few tasks to fill the device and the gene-side plan has more: the task ranges
-    // are chosen for the iteration's merged launch, where C3 f64 gets one range per cell block = 196 tasks for 256
-    // compute units (loss pass 421 us on the cell plan; the gene plan's 640 tapered tasks: see DESIGN 9).
+    // which tile plan the loss pass sweeps (policy.cpp loss_side)
     int loss_side() const
     {
-        const int forced = env_int("SCHPF_LOSS_SIDE", -1);
-        if (forced == 0 || forced == 1) return use_tile ? forced : 0;
-        if (!use_tile || wave_out.bytes < (size_t)tgene.n_wave_out * sizeof(double)) return 0;
-        // the plan with the shorter modelled pass (loss_tasks); the gene side's steps are worth a little more: its windows
-        // are shorter (more stagings per nonzero than the model's two step units per window say)
-        if (tcell.llh_model > 0.0 && tgene.llh_model > 0.0) return tgene.llh_model * 1.05 < tcell.llh_model ? 1 : 0;
-        const int64_t resident = (int64_t)n_cu() * per_cu(tcell.lds_bytes);
-        return (tcell.n_tasks < 2 * resident && tgene.n_tasks > tcell.n_tasks) ? 1 : 0;
+        if (!use_tile) return 0;
+        const double model[2] = {tcell.llh_model, tgene.llh_model};
+        const int64_t tasks[2] = {tcell.n_tasks, tgene.n_tasks};
+        return schpf::loss_side(problem(), tuning, wave_out.bytes >= (size_t)tgene.n_wave_out * sizeof(double), model, tasks,
+                                tcell.lds_bytes);
     }
 
     void upload_info(int64_t info[4]) override
@@ -2284,22 +1955,23 @@ int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *mi
                             int32_t *out_pcount, int64_t stats[8])
 {
     return guarded([&] {
+        const schpf::Tuning tn = schpf::tuning_from_env();   // per call: tests change the switches between calls
         schpf::TilePlanHost P;
         schpf::TileShape sh;
         sh.lpc = lpc; sh.waves_per_block = waves_per_block; sh.win_rows = win_rows; sh.target_tasks = target_tasks;
-        sh.row_slots = env_int("SCHPF_DEBUG_ROW_SLOTS", 10);   // 160-byte table rows
+        sh.row_slots = tn.debug_row_slots;   // 160-byte table rows
         sh.ring = ring < 0 ? -ring : ring; sh.sync_stage = sh.ring > 1 ? 1 : 0; sh.slot_bytes = slot_bytes;
         // SCHPF_DEBUG_SINGLE=1: steps count nonzeros (plan.h; window schedule only)
-        sh.single = env_int("SCHPF_DEBUG_SINGLE", 0) != 0 && sh.ring <= 1;
-        sh.allow_packed = getenv("SCHPF_PACK") ? atoi(getenv("SCHPF_PACK")) != 0 : true;
-        sh.bank_order = env_int("SCHPF_BANK_ORDER", 2);
-        sh.taper = env_int("SCHPF_TAPER", 0) / 100.0;
+        sh.single = tn.debug_single && sh.ring <= 1;
+        sh.bank_order = tn.bank_order;
+        sh.taper = tn.taper.value_or(0) / 100.0;
+        sh.verbose = tn.verbose;
         if (sh.taper > 0.0) sh.slots = 1;   // tapered ranges are for orientations with more tasks than workgroups (plan.h)
         // SCHPF_DEBUG_BALANCE=1: balanced windows (plan.h) -- the plan is built on the blocks' virtual numbering of the
         // minor rows and every entry is mapped back through minor_of
         std::vector<int32_t> minor_of;
         schpf::BalanceGeometry geo;
-        const bool balanced = env_int("SCHPF_DEBUG_BALANCE", 0) != 0 && sh.ring <= 1;
+        const bool balanced = tn.debug_balance && sh.ring <= 1;
         if (balanced) {
             schpf::BigVec<int32_t> vminor;
             schpf::balance_windows_host(nnz, major, minor, n_major, n_minor, sh, vminor, minor_of, geo);

@@ -525,57 +525,6 @@ void tile_plan_begin(TilePlanHost &P, int64_t nnz, int n_major, int n_minor, con
     P.steps.assign((size_t)P.n_blocks * P.wpb * W, 0);
 }
 
-void xcd_launch_order(const TilePlanHost *const *plans, int n_plans, int n_xcd, int bundle, std::vector<int32_t> &order)
-{
-    struct Item { int32_t code; int64_t work; int64_t key; };
-    std::vector<Item> items;
-    for (int p = 0; p < n_plans; ++p) {
-        const TilePlanHost &P = *plans[p];
-        for (int64_t t = 0; t < P.n_tasks; ++t)
-            items.push_back({p == 0 ? (int32_t)t : ~(int32_t)t, P.task_work[(size_t)t],
-                             ((int64_t)p << 40) | (int64_t)P.task_w0[(size_t)t]});
-    }
-    const size_t n = items.size();
-    order.assign(n, 0);
-    if (n == 0) return;
-    n_xcd = std::max(1, n_xcd);
-    bundle = std::max(1, bundle);
-    // tasks of one range together, longest first
-    std::stable_sort(items.begin(), items.end(), [](const Item &x, const Item &y) {
-        return x.key != y.key ? x.key < y.key : x.work > y.work;
-    });
-    struct Bundle { size_t first, count; int64_t longest, total; };
-    std::vector<Bundle> bundles;
-    for (size_t i = 0; i < n;) {
-        size_t j = i;
-        int64_t total = 0;
-        while (j < n && items[j].key == items[i].key && j - i < (size_t)bundle) total += items[j++].work;
-        bundles.push_back({i, j - i, items[i].work, total});
-        i = j;
-    }
-    std::stable_sort(bundles.begin(), bundles.end(), [](const Bundle &x, const Bundle &y) { return x.longest > y.longest; });
-    std::vector<std::vector<int32_t>> queue((size_t)n_xcd);
-    std::vector<int64_t> load((size_t)n_xcd, 0);
-    for (const Bundle &b : bundles) {
-        int x = 0;
-        for (int c = 1; c < n_xcd; ++c)
-            if (load[(size_t)c] < load[(size_t)x]) x = c;
-        for (size_t i = b.first; i < b.first + b.count; ++i) queue[(size_t)x].push_back(items[i].code);
-        load[(size_t)x] += b.total;
-    }
-    // XCD x owns the slots x, x + n_xcd, ...: move the (short) tail tasks of over-full queues
-    auto slots_of = [&](int x) { return (n - (size_t)x + (size_t)n_xcd - 1) / (size_t)n_xcd; };
-    for (int x = 0; x < n_xcd; ++x)
-        while (queue[(size_t)x].size() > slots_of(x)) {
-            int y = 0;
-            while (queue[(size_t)y].size() >= slots_of(y)) ++y;     // exists: the sizes add up to n
-            queue[(size_t)y].push_back(queue[(size_t)x].back());
-            queue[(size_t)x].pop_back();
-        }
-    for (int x = 0; x < n_xcd; ++x)
-        for (size_t q = 0; q < queue[(size_t)x].size(); ++q) order[q * (size_t)n_xcd + (size_t)x] = queue[(size_t)x][q];
-}
-
 std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major, int rows_per_block, int64_t stride)
 {
     stride = std::max<int64_t>(1, stride);
@@ -831,7 +780,7 @@ static void ring_schedule_block(const TilePlanHost &P, int64_t b, CntBelow cnt_b
 void build_tile_plan(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val,
                      int n_major, int n_minor, const TileShape &shape, bool keep_order, TilePlanHost &P)
 {
-    const bool verbose = getenv("SCHPF_VERBOSE") && atoi(getenv("SCHPF_VERBOSE"));
+    const bool verbose = shape.verbose;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     BigVec<int32_t> order;
@@ -917,8 +866,8 @@ void build_tile_plan(int64_t nnz, const int32_t *major, const int32_t *minor, co
     const int64_t total_padded = tile_plan_offsets(P, wave_off);
     // packed entries (8 bytes per step: two 16-bit LDS positions + two 16-bit counts) when
     // every count fits 16 bits -- UMI counts do; otherwise 16 bytes per step (32-bit position, float)
-    bool packed = shape.allow_packed;
-    if (packed) {
+    bool packed = true;
+    {
         std::vector<int> big((size_t)nth + 1, 0);
         parallel_for(nnz, nth, [&](int64_t b, int64_t e, int t) {
             for (int64_t j = b; j < e; ++j) {

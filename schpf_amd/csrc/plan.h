@@ -191,8 +191,8 @@ struct TileShape {
     int ranges = 0;         // > 0: window ranges (tasks) per block, fixed by the caller (choose_task_ranges);
                             // target_tasks and the rounding by `slots` are then not consulted
     int bank_order = 1;
-    bool allow_packed = true;
     double taper = 0.0;     // > 0: window ranges of unequal length, (1 + taper) .. (1 - taper) x the mean (tile_range_starts)
+    bool verbose = false;   // build timings and a plan report on stderr (SCHPF_VERBOSE)
 };
 // How many window ranges (tasks per block) each orientation of a ONE-LAUNCH iteration should have.  The
 // merged launch runs its tasks longest first on `resident` workgroups that draw from one list, so the
@@ -217,18 +217,6 @@ RangeChoice choose_task_ranges(const int64_t blocks[2], const int64_t half_windo
                                double nnz, int resident, double nnz_per_second, double task_seconds,
                                const double partial_seconds[2], int min_half_per_task, double window_penalty,
                                int max_ranges, bool separate_launches, double taper = 0.0);
-
-// Launch order (slot -> task) of the tile sweep over one or two plans' tasks that keeps the tasks
-// reading the SAME window range of the minor table on ONE XCD at the same time: an XCD's 32 compute
-// units then stage the same table rows within a short time of each other and all but the first copy
-// of a window hit the XCD's own 4 MiB L2 (the tables do not fit it: C5 share 11-56 MB; measured there
-// 48 % L2 hits with the longest-first order).  Workgroup s is observed to run on XCD s % n_xcd
-// (MI355X_MICROARCH.md, dispatch): tasks of one (plan, range) are cut into bundles of `bundle` (the
-// workgroups an XCD holds at a time), bundles go longest first to the XCD with the least work so far
-// and XCD x's queue fills the slots x, x + n_xcd, ...  A wrong placement guess is slower, never wrong.
-// order[slot] = task of plans[0], or ~task of plans[1].
-void xcd_launch_order(const TilePlanHost *const *plans, int n_plans, int n_xcd, int bundle,
-                      std::vector<int32_t> &order);
 
 void build_tile_plan(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val,
                      int n_major, int n_minor, const TileShape &shape, bool keep_order, TilePlanHost &out);

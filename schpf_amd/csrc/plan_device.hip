@@ -514,7 +514,7 @@ void build_tile_plan_device(void *stream, int64_t nnz, const int32_t *d_major, c
         // ---- 5. host: offsets
         std::vector<int64_t> wave_off;
         const int64_t total_padded = tile_plan_offsets(P, wave_off);
-        P.packed = shape.allow_packed && packed_ok;
+        P.packed = packed_ok;
         g.packed = P.packed ? 1 : 0;
         const int epw = P.packed ? 2 : 4;
         const std::vector<int> pass_rank = tile_pass_rank(lpc, P.gpw);
@@ -572,7 +572,7 @@ void build_tile_plan_device(void *stream, int64_t nnz, const int32_t *d_major, c
         PD_CHECK(hipStreamSynchronize(st));
         P.mptr.swap(mptr);
         *out_order = order;
-        if (getenv("SCHPF_VERBOSE") && atoi(getenv("SCHPF_VERBOSE"))) tile_plan_report(P);
+        if (shape.verbose) tile_plan_report(P);
     } catch (...) {
         if (order) (void)hipFree(order);
         if (*out_entries) { (void)hipFree(*out_entries); *out_entries = nullptr; }
@@ -800,7 +800,7 @@ void balance_windows_device(void *stream, int64_t nnz, const int32_t *d_major, c
                                                        0, end_bit, st));
             PD_CHECK(hipStreamSynchronize(st));   // temp dies here
         }
-        const bool verbose = getenv("SCHPF_VERBOSE") && atoi(getenv("SCHPF_VERBOSE"));
+        const bool verbose = shape.verbose;
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_sorted = now();
         BalanceDev bd{gpb, win_rows, W, geo.n_sections, geo.D, n_minor, geo.n_virtual, minor_bits};

@@ -23,7 +23,7 @@ def plan_kind(request, monkeypatch):
     schedule the library picks ("tile", what ships), with the half-window schedule forced ("half":
     SCHPF_HALF=2), with balanced windows forced ("balanced": SCHPF_BALANCE=1 -- the library itself only
     balances sparse, wide problems like the C5 share), and the L2-gather plan (selected by the library
-    from SCHPF_PLAN at upload time).  A test that belongs to some of them narrows the list with
+    from SCHPF_PLAN when the engine is created).  A test that belongs to some of them narrows the list with
     `only_plans(...)` -- no ids that can only skip -- and the tests of the iteration itself add "balanced"
     (`every_plan`)."""
     monkeypatch.setenv("SCHPF_PLAN", "tile" if request.param in ("half", "balanced") else request.param)
@@ -378,26 +378,6 @@ def test_mass_conservation_at_headline_shape(amd, oracle, plan_kind):
     assert_allclose(loss, want, rtol=1e-11)
 
 
-@only_plans("tile", "half")
-def test_xcd_launch_order_changes_nothing_but_the_order(amd, oracle, plan_kind, monkeypatch):
-    """SCHPF_XCD=8 (plan.h xcd_launch_order: same-range tasks share an XCD) permutes the launch slots of
-    the merged sweep; every task still runs exactly once, so the iteration is bitwise the same."""
-    X = synthetic_counts(3000, 2500, 0.05, seed=11)
-    K, a, c = 20, 0.3, 0.3
-    bp, dp, st = random_state(oracle, X, K, np.float64, seed=3)
-    got = []
-    for xcd in ("1", "8"):
-        monkeypatch.setenv("SCHPF_XCD", xcd)
-        monkeypatch.setenv("SCHPF_TASKS", "300")
-        with load_engine(amd, X, K, np.float64, st, a, c, bp, dp) as eng:
-            for _ in range(2):
-                eng.step()
-            got.append((eng.get_gamma("theta"), eng.get_gamma("beta"), eng.plan_info()["n_chunks_cell"]))
-    assert got[0][2] > 8                                     # several tasks per XCD queue
-    for x, y in zip(got[0][:2], got[1][:2]):
-        assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
-
-
 @only_plans("tile", "half", "balanced")
 def test_persistent_dual_launch_equals_one_workgroup_per_task_bitwise(amd, oracle, plan_kind, monkeypatch):
     """The dual sweep launch as persistent workgroups that draw tasks from a device counter (default)
@@ -458,7 +438,7 @@ def test_matrix_without_stored_entries_keeps_the_priors(amd, oracle, dtype, plan
 def test_largest_supported_number_of_factors(amd, oracle, dtype, plan_kind):
     """K = 256, the most the update kernel's one-thread-per-(row, factor) mapping takes; 257 is refused.
     Rows of 2 KiB (float64) are beyond the LDS-staged plan's 1 KiB rows: the library takes the L2-gather plan for them
-    by itself (capi.hip choose_config), which is the plan forced here; float32 rows (1 KiB) run on either."""
+    by itself (policy.cpp choose_config), which is the plan forced here; float32 rows (1 KiB) run on either."""
     N, G, K, a, c = 90, 120, 256, 0.3, 0.3
     X = synthetic_counts(N, G, 0.15, seed=8)
     bp, dp, st = random_state(oracle, X, K, dtype, seed=12)
@@ -1043,7 +1023,7 @@ def test_dual_launch_equals_two_launches_bitwise(amd, oracle, dtype, plan_kind, 
 @pytest.mark.parametrize("dtype,K", [(np.float64, 20), (np.float32, 20), (np.float64, 50)])
 def test_loss_is_the_same_on_either_plan(amd, oracle, plan_kind, monkeypatch, dtype, K):
     """The loss pass sweeps ONE tile plan -- the cell-side one, or the gene-side one when the cell side has too few
-    tasks to fill the device (capi.hip loss_side): both hold every nonzero and r = sum_k E[theta] E[beta] is
+    tasks to fill the device (policy.cpp loss_side): both hold every nonzero and r = sum_k E[theta] E[beta] is
     symmetric, so the two must agree to summation order, with the oracle's loss (hpf_numba.py:24-51) and explicitly
     stored zeros (counted by the reference's loss) included."""
     from scipy.sparse import coo_matrix

@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """Kernel-tuning harness (GPU box): one synthetic matrix, many plan/kernel settings.
 
-    python tools/explore.py c3 "dtype=f64" "dtype=f64,SCHPF_LPC=1" "dtype=f32,SCHPF_CHUNK=64" ...
+    python tools/explore.py c3 "dtype=f64" "dtype=f64,SCHPF_HALF=0" "dtype=f32,SCHPF_TASKS=512" ...
 
-Each setting is a comma-separated list; keys starting with SCHPF_ are environment knobs
-read by the library at create/upload time, `dtype` selects the model precision.
+Each setting is a comma-separated list; keys starting with SCHPF_ are environment switches
+ read by the library when the engine is created, `dtype` selects the model precision.
 """
 import json
 import os
