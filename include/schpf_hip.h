@@ -173,6 +173,13 @@ int schpf_step_finish(schpf_ctx *ctx, unsigned flags);
  * mean negative llh = -(llh_sum - gammaln_sum) / nnz  (sum the three over ranks first). */
 int schpf_loss_terms(schpf_ctx *ctx, double *llh_sum, double *gammaln_sum, int64_t *nnz);
 
+/* The evidence lower bound of the current state, split into its terms:
+ * terms[0] data, [1] logfac, [2] rate, [3] cell, [4] gene;  ELBO = t0 - t1 - t2 + t3 + t4.
+ * ap, cp: the shape priors of xi / eta (the engine holds a, c, bp, dp from schpf_set_hypers).
+ * Over the local cells (a shard: sum data, logfac, rate, cell over the ranks; gene is replicated).
+ * A batch engine (schpf_upload_rows) fails, as schpf_loss_terms does.  Definition: DESIGN.md 11. */
+int schpf_elbo_terms(schpf_ctx *ctx, double ap, double cp, double terms[5]);
+
 int schpf_synchronize(schpf_ctx *ctx);
 
 /* Cells sharded over the GPUs of a node, the collective inside the library (RCCL over xGMI, bound

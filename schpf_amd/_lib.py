@@ -48,6 +48,7 @@ SIGNATURES = {
     "schpf_exchange_buffer": [_vp, ctypes.POINTER(_vp), _i64p],
     "schpf_step_finish": [_vp, ctypes.c_uint],
     "schpf_loss_terms": [_vp, _dblp, _dblp, _i64p],
+    "schpf_elbo_terms": [_vp, _dbl, _dbl, _dblp],
     "schpf_synchronize": [_vp],
     "schpf_hint_sharded": [_vp, _int],
     "schpf_hint_transient": [_vp, _int],

@@ -268,6 +268,7 @@ struct schpf_ctx {
     }
     virtual void exchange(void **p, int64_t *count) = 0;
     virtual void loss_terms(double *llh, double *gl, int64_t *nnz) = 0;
+    virtual void elbo_terms(double ap, double cp, double terms[5]) = 0;
     virtual void plan_info(int64_t info[16]) = 0;
     virtual void upload_info(int64_t info[4]) = 0;
     virtual void profile_clock(double *shader_mhz, int64_t *launches) = 0;
@@ -303,6 +304,8 @@ template <typename T> struct Engine final : schpf_ctx {
     double gammaln_sum = 0.0;
     int64_t n_rounded = 0, n_zero = 0;              // upload facts: values rounded to float32; stored zeros
     DevBuf zero_row, zero_col;                      // positions of explicitly stored zeros (loss only)
+    DevBuf count_row, count_col;                    // ELBO: sum of the stored counts of each cell / gene (double[N], [G])
+    DevBuf elbo_part, elbo_sums;                    // ELBO: Gamma-term block partials, their sums (elbo_terms)
     bool have_coo = false;
     bool dirty_theta = true, dirty_beta = true;
     int pending_init = 0;  // 0 none, 1 dense accumulators, 2 chunk partials
@@ -413,6 +416,7 @@ template <typename T> struct Engine final : schpf_ctx {
         dual_order.release(); dual_slots = 0;
         rows_ptr.release(); rows_col.release(); rows_val.release();
         zero_row.release(); zero_col.release();
+        count_row.release(); count_col.release();
         pending_init = 0;
         eager_since_upload = false;
     }
@@ -664,6 +668,7 @@ template <typename T> struct Engine final : schpf_ctx {
         // constant term of the loss, sum lgamma(x + 1) (hpf_numba.py:49-50), while the values are still resident:
         // no second trip of the values over PCIe
         gammaln_partial_sums(d_val.as<float>());
+        count_sums(d_val.as<float>());
         gammaln_on_device = true;
         if (want_rows) {   // the (row, col)-sorted copy minibatches gather their rows from
             rows_col.alloc((size_t)nnz * 4); rows_val.alloc((size_t)nnz * 4);
@@ -899,6 +904,30 @@ template <typename T> struct Engine final : schpf_ctx {
         HIPCHK(schpf::launch_sum_doubles(gammaln_part.as<double>(), nb, scalars.as<double>() + 1, stream));
     }
 
+    // ELBO shift terms (elbo_terms): the stored counts of every cell and every gene, summed over each plan's
+    // (major, minor)-sorted runs while the values are on the device -- once per upload, N + G doubles.  Its wall time
+    // (count_seconds) is part of the upload's and is reported by SCHPF_VERBOSE=1 (DESIGN.md 11 has the measurements)
+    double count_seconds = 0.0;
+    void count_sums(const float *d_values)
+    {
+        const double t0 = now_s();
+        for (int side = 0; side < 2; ++side) {
+            DevBuf scratch, mp;
+            const int *ord = nullptr;
+            if (!use_tile || !(side == 0 ? tcell : tgene).order_identity) {
+                const TileDev &td = side == 0 ? tcell : tgene;
+                ord = use_tile && td.order_dev.p ? td.order_dev.as<int>() : order_of(side, scratch);
+            }
+            upload(mp, use_tile ? (side == 0 ? tcell : tgene).host.mptr : (side == 0 ? cell : gene).host.mptr, stream);
+            DevBuf &out = side == 0 ? count_row : count_col;
+            const int n = side == 0 ? N : G;
+            out.alloc((size_t)n * sizeof(double));
+            HIPCHK(schpf::launch_count_sums(d_values, ord, mp.as<int64_t>(), n, out.as<double>(), stream));
+            HIPCHK(hipStreamSynchronize(stream));   // scratch and mp die with this scope
+        }
+        count_seconds = now_s() - t0;
+    }
+
     static double now_s()
     {
         return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -994,6 +1023,7 @@ template <typename T> struct Engine final : schpf_ctx {
         if (!gammaln_on_device) {          // host-built plans: the values go up once more for it
             upload(dv, v, stream);
             gammaln_partial_sums(dv.as<float>());
+            count_sums(dv.as<float>());
         }
         gammaln_on_device = false;
         HIPCHK(hipMemcpyAsync(&gammaln_sum, scalars.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost,
@@ -1005,8 +1035,10 @@ template <typename T> struct Engine final : schpf_ctx {
         drop_graph();
         eager_since_upload = false;
         if (tuning.verbose)
-            fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads)\n",
-                    (long long)nnz, t_valid - t_start, t_plans - t_valid, now_s() - t_plans, schpf::host_threads());
+            fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads); "
+                    "ELBO count sums %.4f s of it\n",
+                    (long long)nnz, t_valid - t_start, t_plans - t_valid, now_s() - t_plans, schpf::host_threads(),
+                    count_seconds);
     }
 
     DevBuf &shape_buf(int which)
@@ -1150,7 +1182,8 @@ template <typename T> struct Engine final : schpf_ctx {
             auto a = tile_args(td, tmaj, tmin, lmaj, lmin, cellside ? G : N);
             a.seed = seed; a.major_is_cell = cellside ? 1 : 0;
             int64_t n_tasks = td.n_tasks;
-            const bool cut = mode == schpf::MODE_LLH && td.n_llh_tasks > 0;   // the loss pass's finer tasks (loss_tasks)
+            const bool logs = mode == schpf::MODE_LLH || mode == schpf::MODE_ELBO;   // the ELBO pass is cut as the loss pass
+            const bool cut = logs && td.n_llh_tasks > 0;   // the loss pass's finer tasks (loss_tasks)
             if (cut) {
                 a.task_block = td.llh_block.as<int>(); a.task_w0 = td.llh_w0.as<int>(); a.task_w1 = td.llh_w1.as<int>();
                 a.task_stage_end = td.llh_stage_end.as<int>(); a.task_wave_off = td.llh_wave_off.as<int64_t>();
@@ -1163,7 +1196,8 @@ template <typename T> struct Engine final : schpf_ctx {
             } else if (cut) a.task_order = td.llh_order.as<int>();
             // the loss pass keeps a 1 KiB logarithm table behind the window (sweep_impl.h LlhAccumulator)
             a.llh_tab_off = (int)((td.lds_bytes + 15) & ~(size_t)15);
-            const size_t lds = mode == schpf::MODE_LLH ? (size_t)a.llh_tab_off + 1024 : td.lds_bytes;
+            const size_t lds = logs ? (size_t)a.llh_tab_off + 1024 : td.lds_bytes;
+            if (mode == schpf::MODE_ELBO) a.clock_probe = nullptr;   // schpf_profile_clock: the sweeps and the loss pass
             HIPCHK(schpf::launch_tile_sweep<T>(a, NV, LPC, mode, td.packed ? 1 : 0, n_tasks, td.threads, lds, stream));
         } else {
             PlanDev &pd = cellside ? cell : gene;
@@ -1405,6 +1439,48 @@ template <typename T> struct Engine final : schpf_ctx {
         *llh = n_zero > 0 ? h[0] - h[2] : h[0];
         *gl = gammaln_sum;
         *nnz_out = nnz;
+    }
+
+    // The evidence lower bound of the current state, terms {data, logfac, rate, cell, gene}:
+    //   data  = sum x log sum_k exp(Elt + Elb) = [MODE_ELBO sweep: sum x log s] + sum_i m_i r_i + sum_g m_g c_g
+    //   logfac = the loss's gammaln_sum;  rate = sum_k (sum_i E theta_ik)(sum_g E beta_gk)
+    //   cell / gene = the prior and entropy terms of (xi, theta) / (eta, beta)  (elbo_gamma_kernel)
+    // Reads the state only: its own scratch (the update kernels' column partials may be live, sums_stale), nothing cached.
+    void elbo_terms(double ap, double cp, double terms[5]) override
+    {
+        need_coo();
+        if (!have_loss_constants)
+            throw std::logic_error("this engine holds gathered batch rows (schpf_upload_rows): evaluate the loss on the source");
+        if (!(ap > 0 && cp > 0)) throw std::invalid_argument("ap and cp must be positive");
+        refresh_tables();
+        const int side = loss_side();
+        run_sweep(side, schpf::MODE_ELBO);
+        const int nbc = upd_blocks(N), nbg = upd_blocks(G), W = K + 2;
+        if (elbo_part.bytes < (size_t)std::max(nbc, nbg) * W * sizeof(double))
+            elbo_part.alloc((size_t)std::max(nbc, nbg) * W * sizeof(double));
+        if (!elbo_sums.p) elbo_sums.alloc((size_t)(2 * W + 1) * sizeof(double));
+        double *sums = elbo_sums.as<double>();
+        HIPCHK(schpf::launch_sum_doubles(wave_out.as<double>(),
+                                         use_tile ? (side ? tgene.n_wave_out : tcell.n_wave_out) : cell.n_waves,
+                                         sums + 2 * W, stream));
+        HIPCHK(schpf::launch_elbo_gamma<T>(th_s.as<T>(), th_r.as<T>(), xi_s.as<T>(), xi_r.as<T>(), th_log.as<T>(),
+                                           count_row.as<double>(), N, K, KP, a, ap, bp, elbo_part.as<double>(), nbc,
+                                           stream));
+        HIPCHK(schpf::launch_colsum_reduce(elbo_part.as<double>(), nbc, W, sums, nullptr, 0, stream));
+        HIPCHK(schpf::launch_elbo_gamma<T>(be_s.as<T>(), be_r.as<T>(), eta_s.as<T>(), eta_r.as<T>(), be_log.as<T>(),
+                                           count_col.as<double>(), G, K, KP, c, cp, dp, elbo_part.as<double>(), nbg,
+                                           stream));
+        HIPCHK(schpf::launch_colsum_reduce(elbo_part.as<double>(), nbg, W, sums + W, nullptr, 0, stream));
+        std::vector<double> h((size_t)(2 * W + 1));
+        HIPCHK(hipMemcpyAsync(h.data(), sums, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        double rate = 0.0;
+        for (int k = 0; k < K; ++k) rate += h[(size_t)k] * h[(size_t)(W + k)];
+        terms[0] = h[(size_t)(2 * W)] + h[(size_t)(K + 1)] + h[(size_t)(W + K + 1)];
+        terms[1] = gammaln_sum;
+        terms[2] = rate;
+        terms[3] = h[(size_t)K];
+        terms[4] = h[(size_t)(W + K)];
     }
 
     // which tile plan the loss pass sweeps (policy.cpp loss_side)
@@ -1781,6 +1857,12 @@ int schpf_steps(schpf_ctx *ctx, unsigned flags, int n)
 int schpf_loss_terms(schpf_ctx *ctx, double *llh_sum, double *gammaln_sum, int64_t *nnz)
 {
     CTX_CALL(ctx->loss_terms(llh_sum, gammaln_sum, nnz));
+}
+int schpf_elbo_terms(schpf_ctx *ctx, double ap, double cp, double terms[5])
+{
+    if (!ctx) return fail("ctx is NULL");
+    if (!terms) return fail("terms is NULL");
+    CTX_CALL(ctx->elbo_terms(ap, cp, terms));
 }
 int schpf_synchronize(schpf_ctx *ctx) { CTX_CALL(HIPCHK(hipStreamSynchronize(ctx->stream))); }
 

@@ -5,7 +5,7 @@
 
 namespace schpf {
 
-enum { MODE_PHI = 0, MODE_LLH = 1, MODE_RANDOM = 2 };
+enum { MODE_PHI = 0, MODE_LLH = 1, MODE_RANDOM = 2, MODE_ELBO = 3 };
 enum { SRC_STRIDED = 3 };
 enum { SRC_NONE = 0, SRC_PARTIALS = 1, SRC_DENSE = 2 };
 
@@ -16,12 +16,12 @@ template <typename T> struct SweepArgs {
     const int *chunk_major;     // [n_slices * CPW]
     const int *chunk_natid;     // [n_slices * CPW]
     const int *wave_slice;      // [n_waves]
-    const T *tab_major;         // [n_major, KP] exp-shifted E[log] (PHI) or E[x] (LLH)
+    const T *tab_major;         // [n_major, KP] exp-shifted E[log] (PHI, ELBO) or E[x] (LLH)
     const T *tab_minor;         // [n_minor, KP]
     const T *log_major;         // [n_major, KP] E[log x] (fallback only)
     const T *log_minor;         // [n_minor, KP]
     T *partials;                // [n_chunks, KP]
-    double *wave_out;           // [n_waves] (LLH)
+    double *wave_out;           // [n_waves] (LLH, ELBO)
     int K;
 };
 
@@ -40,13 +40,13 @@ template <typename T> struct TileArgs {
     const T *tab_minor;            // [n_minor, KP]  (staged window by window)
     const T *log_major, *log_minor;
     T *partials;                   // [n_tasks * gpb, KP]
-    double *wave_out;              // [n_tasks * wpb] (LLH)
+    double *wave_out;              // [n_tasks * wpb] (LLH, ELBO)
     int K, n_minor, n_windows, win_rows, wpb;
     // balanced windows (plan.h): block b stages window w from the table rows minor_of[b * n_virtual + w * win_rows + j]
     // (-1: none); n_minor is then n_virtual.  nullptr: windows are index ranges of the table
     const int *minor_of;
     int n_virtual;
-    int llh_tab_off;               // MODE_LLH: byte offset in LDS of the logarithm table (behind the window; LlhAccumulator::TABLE_BYTES)
+    int llh_tab_off;               // MODE_LLH / MODE_ELBO: byte offset in LDS of the logarithm table (behind the window; LlhAccumulator::TABLE_BYTES)
     int ring, slot_bytes;          // ring mode (plan.h): slots in the LDS ring (<= 1: window mode), bytes per slot
     int sync_stage;                // ring mode: half-window schedule (slots refilled at the epoch boundary)
     int single;                    // steps[] count nonzeros, (steps + 1) / 2 slots are stored (plan.h)
@@ -174,6 +174,17 @@ hipError_t launch_rate_update(const T *ps, const T *pr, const double *S, int n, 
 template <typename T>
 hipError_t launch_capacity_rate(const T *shape, const T *rate, int n, int K, double prior, T *out,
                                 hipStream_t st);
+// ELBO: per major row, the sum of its stored counts in the plan's (major, minor)-sorted order
+// (order == nullptr: the caller's COO is in that order already); one thread per row, fixed order
+hipError_t launch_count_sums(const float *val, const int *order, const int64_t *mptr, int n, double *out,
+                             hipStream_t st);
+// the Gamma terms of one side: per block b, part[b * (K + 2) + ...] = {the K column sums of E[x], the prior / entropy
+// terms of the loadings and of their capacities, sum_i m_i * counts_i} (m_i = max_k of the row of `log_tab`); reduced
+// by launch_colsum_reduce with K + 2 columns
+template <typename T>
+hipError_t launch_elbo_gamma(const T *shape, const T *rate, const T *cap_shape, const T *cap_rate, const T *log_tab,
+                             const double *counts, int n, int K, int KP, double prior, double cap_prior_shape,
+                             double cap_prior_rate, double *part, int nblocks, hipStream_t st);
 hipError_t launch_digamma_array(const double *x, int64_t n, double *out, hipStream_t st);
 hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStream_t st);
 

@@ -466,6 +466,80 @@ __global__ __launch_bounds__(256) void gammaln_array_kernel(const double *__rest
     if (i < n) out[i] = lgamma(x[i]);
 }
 
+// ------------------------------------------------------ ELBO
+// counts of each major row over its run of the plan's sorted order: one wavefront per row, lane l takes positions
+// l, l + 64, ..., then a fixed butterfly -- deterministic, no atomics
+__global__ __launch_bounds__(256) void count_sums_kernel(const float *__restrict__ val, const int *__restrict__ order,
+                                                         const int64_t *__restrict__ mptr, int n, double *__restrict__ out)
+{
+    const int row = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;   // wave-uniform
+    double s = 0.0;
+    for (int64_t j = mptr[row] + lane; j < mptr[row + 1]; j += 64) s += (double)val[order ? (int64_t)order[j] : j];
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (lane == 0) out[row] = s;
+}
+
+// entropy of Gamma(shape, rate) given psi(shape) (reference scHPF_.py:114-119)
+__device__ __forceinline__ double gamma_entropy(double s, double r, double psi_s)
+{
+    return s - log(r) + lgamma(s) + (1.0 - s) * psi_s;
+}
+// The Gamma terms of one side (loadings theta / beta with capacities xi / eta) of the ELBO, thread t of a block taking
+// factor k = t % K of rows r = t / K, r + rb, ... (rb = 256 / K rows per pass, as ratio_colsum_kernel):
+//   sum_ik [a L(cap_i) - lgamma(a) + (a - 1) L_ik - E(cap_i) E_ik + H_ik]
+//   + sum_i [ap log bp - lgamma(ap) + (ap - 1) L(cap_i) - bp E(cap_i) + H(cap_i)],
+// the column sums sum_i E_ik of the rate term and the shift sum_i m_i counts_i of the data term.  Everything in double
+// from the stored shape / rate (psi from special.h, lgamma from the device libm); block partials in fixed order.
+template <typename T>
+__global__ __launch_bounds__(256) void elbo_gamma_kernel(const T *__restrict__ shape, const T *__restrict__ rate,
+                                                         const T *__restrict__ cap_shape, const T *__restrict__ cap_rate,
+                                                         const T *__restrict__ log_tab, const double *__restrict__ counts,
+                                                         int n, int K, int KP, double prior, double cap_prior_shape,
+                                                         double cap_prior_rate, double *__restrict__ part)
+{
+    __shared__ double red[2][256];
+    __shared__ double col[256];
+    const int rb = 256 / K;
+    const int t = threadIdx.x, r = t / K, k = t - r * K;
+    const double lg_prior = lgamma(prior), lg_cap = lgamma(cap_prior_shape);
+    const double cap_const = cap_prior_shape * log(cap_prior_rate) - lg_cap;
+    double g = 0.0, shift = 0.0, cs = 0.0;
+    if (r < rb)
+        for (int row = blockIdx.x * rb + r; row < n; row += gridDim.x * rb) {
+            const double cs_ = (double)cap_shape[row], cr = (double)cap_rate[row];
+            const double cpsi = digamma(cs_);
+            const double cL = cpsi - log(cr), cE = cs_ / cr;
+            const double s = (double)shape[(size_t)row * K + k], rr = (double)rate[(size_t)row * K + k];
+            const double psi = digamma(s);
+            const double E = s / rr;
+            g += prior * cL - lg_prior + (prior - 1.0) * (psi - log(rr)) - cE * E + gamma_entropy(s, rr, psi);
+            cs += E;
+            if (k == 0) {
+                g += cap_const + (cap_prior_shape - 1.0) * cL - cap_prior_rate * cE + gamma_entropy(cs_, cr, cpsi);
+                const T *lr = log_tab + (size_t)row * KP;
+                T m = lr[0];
+                for (int j = 1; j < K; ++j) m = lr[j] > m ? lr[j] : m;
+                shift += (double)(float)m * counts[row];   // the exp table's shift (sweep_impl.h log_row_max)
+            }
+        }
+    red[0][t] = g;
+    red[1][t] = shift;
+    col[t] = cs;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if (t < m) { red[0][t] += red[0][t + m]; red[1][t] += red[1][t + m]; }
+        __syncthreads();
+    }
+    double *out = part + (size_t)blockIdx.x * (K + 2);
+    if (t < K) {
+        double c = 0.0;
+        for (int q = 0; q < rb; ++q) c += col[q * K + t];
+        out[t] = c;
+    }
+    if (t == 0) { out[K] = red[0][0]; out[K + 1] = red[1][0]; }
+}
+
 // ------------------------------------------------------------------------ launchers
 // never a zero-sized grid: every kernel bounds-checks, an empty problem launches one idle block
 static inline unsigned blocks_for(int64_t n) { return n > 0 ? (unsigned)((n + 255) / 256) : 1u; }
@@ -653,6 +727,23 @@ hipError_t launch_capacity_rate(const T *shape, const T *rate, int n, int K, dou
                        prior, out);
     return hipGetLastError();
 }
+hipError_t launch_count_sums(const float *val, const int *order, const int64_t *mptr, int n, double *out,
+                             hipStream_t st)
+{
+    hipLaunchKernelGGL(count_sums_kernel, dim3(n > 0 ? (unsigned)((n + 3) / 4) : 1u), dim3(256), 0, st, val, order, mptr, n,
+                       out);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_elbo_gamma(const T *shape, const T *rate, const T *cap_shape, const T *cap_rate, const T *log_tab,
+                             const double *counts, int n, int K, int KP, double prior, double cap_prior_shape,
+                             double cap_prior_rate, double *part, int nblocks, hipStream_t st)
+{
+    if (K < 1 || K > 256) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((elbo_gamma_kernel<T>), dim3((unsigned)nblocks), dim3(256), 0, st, shape, rate, cap_shape,
+                       cap_rate, log_tab, counts, n, K, KP, prior, cap_prior_shape, cap_prior_rate, part);
+    return hipGetLastError();
+}
 hipError_t launch_digamma_array(const double *x, int64_t n, double *out, hipStream_t st)
 {
     hipLaunchKernelGGL(digamma_array_kernel, dim3(blocks_for(n)), dim3(256), 0, st, x, n, out);
@@ -685,7 +776,9 @@ hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStre
     template hipError_t launch_ratio_colsum<T>(const T *, const T *, int, int, double *, int, hipStream_t);    \
     template hipError_t launch_rate_update<T>(const T *, const T *, const double *, int, int, T *,             \
                                               hipStream_t);                                                    \
-    template hipError_t launch_capacity_rate<T>(const T *, const T *, int, int, double, T *, hipStream_t);
+    template hipError_t launch_capacity_rate<T>(const T *, const T *, int, int, double, T *, hipStream_t);   \
+    template hipError_t launch_elbo_gamma<T>(const T *, const T *, const T *, const T *, const T *, const double *, \
+                                             int, int, int, double, double, double, double *, int, hipStream_t);
 SCHPF_INSTANTIATE(float)
 SCHPF_INSTANTIATE(double)
 

@@ -197,6 +197,7 @@ __device__ __forceinline__ T group_dot(const T (&x)[KL], const T (&y)[KL])
 // fast result -- no atomics, no double counting, still deterministic.  Deliberately register-
 // lean (tables are re-read from L2 three times per nonzero): it must not cost the hot loop
 // occupancy.  acc[] receives sum x * phi_k directly (no multiplication by Et afterwards).
+// Its max / sum half has a copy in log_domain_parts (the MODE_ELBO cold path; why a copy: see there): keep them in step.
 template <typename T, int NV, int LPC>
 __device__ __forceinline__ void slow_nonzero(const T *__restrict__ lt_row, const T *__restrict__ lm_row, int sub,
                                           int K, T x, T (&acc)[NV * Vec16<T>::N])
@@ -307,12 +308,133 @@ __device__ __noinline__ void slow_task_row(const void *__restrict__ entries, siz
     store_lane<T, NV, LPC>(out_row, sub, acc);
 }
 
+// Cold path of MODE_ELBO.  The fast form log s_ig of a nonzero whose product-form s underflowed is log 0 = -inf, but
+// its true value is finite: then the group's whole share of sum x * log s is recomputed here in the log domain,
+//   log s_ig = log sum_k exp(Elt[i,k] + Elb[g,k]) - m_i - m_g,   m = the shift of the row's exp table,
+// and replaces the fast result (as slow_chunk / slow_task_row do for MODE_PHI).  The update kernel shifts a row by its
+// largest stored E[log] rounded to float (kernels.hip gamma_update_kernel); m is recomputed from the stored E[log] row
+// the same way here and in elbo_gamma_kernel (the data term's shift terms), so the fast form, this one and the shifts
+// agree to the last bit -- in float32 the stored E[log] is itself float and m is simply its maximum.
+// The max / sum half of slow_nonzero: l_k = lt_row[k] + lm_row[k]; mx = max_k l_k and ss = sum_k exp(l_k - mx) over
+// the group (every lane gets both).  A copy, not a factoring: with slow_nonzero calling it, the phi sweeps' cold
+// paths were scheduled differently and, through their register use, 18 float64 phi kernels were allocated differently.
+template <typename T> struct LogDomainParts { T mx; double ss; };
+template <typename T, int NV, int LPC>
+__device__ __forceinline__ LogDomainParts<T> log_domain_parts(const T *__restrict__ lt_row, const T *__restrict__ lm_row,
+                                                              int sub, int K)
+{
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = Vec16<T>::N;
+    const V *__restrict__ pt = reinterpret_cast<const V *>(lt_row) + sub;
+    const V *__restrict__ pm = reinterpret_cast<const V *>(lm_row) + sub;
+    T mx = -INFINITY;
+#pragma unroll 1
+    for (int q = 0; q < NV; ++q) {
+        T a[VEC], b[VEC];
+        Vec16<T>::unpack(pt[q * LPC], a);
+        Vec16<T>::unpack(pm[q * LPC], b);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+            if ((q * LPC + sub) * VEC + v < K) { const T l = a[v] + b[v]; mx = l > mx ? l : mx; }
+    }
+    mx = group_max<T, LPC>(mx);
+    double ss = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < NV; ++q) {
+        T a[VEC], b[VEC];
+        Vec16<T>::unpack(pt[q * LPC], a);
+        Vec16<T>::unpack(pm[q * LPC], b);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+            if ((q * LPC + sub) * VEC + v < K) ss += exp((double)(a[v] + b[v] - mx));
+    }
+    ss = group_sum<double, LPC>(ss);
+    return {mx, ss};
+}
+template <typename T, int NV, int LPC>
+__device__ __forceinline__ T log_row_max(const T *__restrict__ row, int sub, int K)
+{
+    typedef typename Vec16<T>::type V;
+    constexpr int VEC = Vec16<T>::N;
+    const V *__restrict__ p = reinterpret_cast<const V *>(row) + sub;
+    T mx = -INFINITY;
+#pragma unroll 1
+    for (int q = 0; q < NV; ++q) {
+        T a[VEC];
+        Vec16<T>::unpack(p[q * LPC], a);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+            if ((q * LPC + sub) * VEC + v < K) mx = a[v] > mx ? a[v] : mx;
+    }
+    return group_max<T, LPC>(mx);
+}
+template <typename T, int NV, int LPC>
+__device__ __forceinline__ double slow_x_log_s(const T *__restrict__ lt_row, const T *__restrict__ lm_row, int sub,
+                                               int K, double m_major, double x)
+{
+    const LogDomainParts<T> ld = log_domain_parts<T, NV, LPC>(lt_row, lm_row, sub, K);
+    return x * (((double)ld.mx - m_major - (double)(float)log_row_max<T, NV, LPC>(lm_row, sub, K)) + log(ld.ss));
+}
+// the gather plan's chunk (every lane of the group returns the same sum)
+template <typename T, int NV, int LPC>
+__device__ __noinline__ double slow_chunk_elbo(const uint4 *__restrict__ ep, int steps, int stride,
+                                               const T *__restrict__ lt_row, const T *__restrict__ log_minor, int sub,
+                                               int K)
+{
+    constexpr int KP = NV * Vec16<T>::N * LPC;
+    const double mi = (double)(float)log_row_max<T, NV, LPC>(lt_row, sub, K);
+    double s = 0.0;
+#pragma unroll 1
+    for (int p = 0; p < steps; ++p) {
+        const uint4 ee = ep[(size_t)p * stride];
+        if (__uint_as_float(ee.y) > 0.f)
+            s += slow_x_log_s<T, NV, LPC>(lt_row, log_minor + (size_t)ee.x * KP, sub, K, mi, (double)__uint_as_float(ee.y));
+        if (__uint_as_float(ee.w) > 0.f)
+            s += slow_x_log_s<T, NV, LPC>(lt_row, log_minor + (size_t)ee.z * KP, sub, K, mi, (double)__uint_as_float(ee.w));
+    }
+    return s;
+}
+// the tile plan's row over the windows [w0, w1) of its task (the traversal of slow_task_row)
+template <typename T, int NV, int LPC, bool PACK>
+__device__ __noinline__ double slow_task_elbo(const void *__restrict__ entries, size_t pos, const uint16_t *__restrict__ st,
+                                              int w0, int w1, int win_rows, int ring, int slot16, int single, int stride,
+                                              const T *__restrict__ lt_row, const T *__restrict__ log_minor, int sub,
+                                              int K, const int *__restrict__ minor_of_block)
+{
+    typedef TileEntry<PACK> EF;
+    constexpr int KP = NV * Vec16<T>::N * LPC;
+    constexpr int ROW_SLOTS = KP * (int)sizeof(T) / 16;
+    const double mi = (double)(float)log_row_max<T, NV, LPC>(lt_row, sub, K);
+    double s = 0.0;
+#pragma unroll 1
+    for (int w = w0; w < w1; ++w) {
+        const int steps = single ? ((int)st[w] + 1) >> 1 : (int)st[w];
+#pragma unroll 1
+        for (int p = 0; p < steps; ++p) {
+            const typename EF::type ee = EF::load(entries, pos + (size_t)p * stride);
+#pragma unroll 1
+            for (int u = 0; u < 2; ++u) {
+                const float x = EF::val(ee, u);
+                if (x > 0.f) {
+                    int minor = entry_minor(EF::idx(ee, u), w, win_rows, ROW_SLOTS, ring, slot16);
+                    if (minor_of_block) minor = minor_of_block[minor];
+                    s += slow_x_log_s<T, NV, LPC>(lt_row, log_minor + (size_t)minor * KP, sub, K, mi, (double)x);
+                }
+            }
+        }
+        pos += (size_t)steps * stride;
+    }
+    return s;
+}
+
 // MODE_PHI : acc_k += (x / s) * Eb[minor,k];  partial row = acc_k * Et[major,k]  -- this
 //            chunk's share of sum x*phi_k (hpf_numba.py:97-112 fused with :152-155).
 //            If the normaliser s of any nonzero of the group underflows, the group's result is
 //            recomputed in the reference's own max-shifted log-domain form (slow_nonzero).
 // MODE_LLH : sum over the chunk of x*log(r) - r, r = sum_k E[theta]E[beta]
 //            (hpf_numba.py:43-50 minus the constant gammaln term); one double per wave.
+// MODE_ELBO: sum over the chunk of x*log(s), s the normaliser of MODE_PHI (exp-shifted tables): the data term of
+//            the ELBO less its shifts m_i + m_g; one double per wave.  Underflowed s: slow_chunk_elbo.
 template <typename T, int NV, int LPC, int MODE>
 __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
 {
@@ -324,7 +446,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
     const int slice = a.wave_slice[wave];
     const int lane = threadIdx.x & 63;
     if (slice < 0) {
-        if (MODE == MODE_LLH && lane == 0) a.wave_out[wave] = 0.0;
+        if ((MODE == MODE_LLH || MODE == MODE_ELBO) && lane == 0) a.wave_out[wave] = 0.0;
         return;
     }
     const int slot = lane / LPC;
@@ -361,13 +483,22 @@ __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
             any_bad |= (x0 > T(0) && !ok0) || (x1 > T(0) && !ok1);
 #pragma unroll
             for (int k = 0; k < KL; ++k) acc[k] = fma_t(w1, b1[k], fma_t(w0, b0[k], acc[k]));
-        } else {
+        } else if (MODE == MODE_LLH) {
             if (x0 > T(0)) llh += (double)x0 * log((double)s0) - (double)s0;
             if (x1 > T(0)) llh += (double)x1 * log((double)s1) - (double)s1;
+        } else {   // MODE_ELBO: an underflowed s is left to the cold path (slow_chunk_elbo)
+            const bool ok0 = s0 >= tiny, ok1 = s1 >= tiny;
+            any_bad |= (x0 > T(0) && !ok0) || (x1 > T(0) && !ok1);
+            if (x0 > T(0) && ok0) llh += (double)x0 * log((double)s0);
+            if (x1 > T(0) && ok1) llh += (double)x1 * log((double)s1);
         }
     }
 
-    if (MODE == MODE_LLH) {
+    if (MODE == MODE_LLH || MODE == MODE_ELBO) {
+        if constexpr (MODE == MODE_ELBO) {
+            if (__builtin_expect(any_bad && live, 0))   // group-uniform; rare
+                llh = slow_chunk_elbo<T, NV, LPC>(ep, steps, CPW, a.log_major + (size_t)major * KP, a.log_minor, sub, a.K);
+        }
         if (sub != 0) llh = 0.0;
         llh = wave_sum(llh);
         if (lane == 0) a.wave_out[wave] = llh;
@@ -515,6 +646,11 @@ struct LlhAccumulator {
     __device__ __forceinline__ void add(double x, double r, const double2 *tab)
     {
         rsum += r;
+        add_log(x, r, tab);
+    }
+    // sum += x * log(r) alone (MODE_ELBO)
+    __device__ __forceinline__ void add_log(double x, double r, const double2 *tab)
+    {
         if (!(r >= 2.3e-308 && r <= 1.7e308)) { sum += x * log(r); return; }   // zero, denormal, inf, NaN: divergent, rare
         const int e = __builtin_amdgcn_frexp_exp(r);
         const double m = __builtin_amdgcn_frexp_mant(r);                          // [0.5, 1)
@@ -570,11 +706,14 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
     for (int k = 0; k < KL; ++k) { tm[k] = T(0); acc[k] = T(0); }
     if (MODE != MODE_RANDOM && live) load_lane<T, NV, LPC>(a.tab_major + (size_t)major * KP, sub, tm);
     double llh = 0.0;
-    LlhAccumulator lacc;   // MODE_LLH
+    constexpr bool LOGS = MODE == MODE_LLH || MODE == MODE_ELBO;
+    LlhAccumulator lacc;   // MODE_LLH, MODE_ELBO
     // ... and its logarithm table, behind the window in LDS (a.llh_tab_off; the window loop's first barrier publishes it)
-    const double2 *llh_tab = reinterpret_cast<const double2 *>(lds_raw + (MODE == MODE_LLH ? a.llh_tab_off : 0));
-    if (MODE == MODE_LLH) LlhAccumulator::fill_table(reinterpret_cast<double2 *>(lds_raw + a.llh_tab_off), (int)threadIdx.x);
+    const double2 *llh_tab = reinterpret_cast<const double2 *>(lds_raw + (LOGS ? a.llh_tab_off : 0));
+    if (LOGS) LlhAccumulator::fill_table(reinterpret_cast<double2 *>(lds_raw + a.llh_tab_off), (int)threadIdx.x);
     bool any_bad = false;
+    // MODE_ELBO code below is `if constexpr` throughout and reads Vec16<T>::tiny() where it needs it: the other modes'
+    // lambdas then capture nothing new, and they compile to the instructions they compiled to before MODE_ELBO existed
     // narrow rows: two minor rows in registers (a 512-thread workgroup has twice the registers per lane)
     // (the loss pass keeps no accumulators, but pairing its wide rows -- K = 50: 112 bytes per lane -- spills 25-34
     // registers into the step loop: loss evaluation at the C5 share 1.30 -> 1.64 ms in f64, 0.49 -> 0.55 in f32; round 4)
@@ -775,6 +914,19 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
                             if (sub < 2 && xm > T(0)) lacc.add((double)xm, (double)sm, llh_tab);
                         }
                     }
+                    if constexpr (MODE == MODE_ELBO) {   // as MODE_LLH, x log s alone; an underflowed s is the cold path's
+                        const T tiny = Vec16<T>::tiny();
+                        const bool ok0 = s0 >= tiny, ok1 = s1 >= tiny;
+                        any_bad |= (x0 > T(0) && !ok0) || (x1 > T(0) && !ok1);
+                        if (LPC == 1) {
+                            if (x0 > T(0) && ok0) lacc.add_log((double)x0, (double)s0, llh_tab);
+                            if (x1 > T(0) && ok1) lacc.add_log((double)x1, (double)s1, llh_tab);
+                        } else {
+                            const T sm = (sub & 1) ? s1 : s0;
+                            const T xm = (sub & 1) ? x1 : x0;
+                            if (sub < 2 && xm > T(0) && sm >= tiny) lacc.add_log((double)xm, (double)sm, llh_tab);
+                        }
+                    }
                     __builtin_amdgcn_sched_barrier(0);
             };
             // whole turns of the ring run without a branch per step: with the four guarded steps in one loop
@@ -833,7 +985,11 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
 #pragma unroll
                     for (int v = 0; v < NV; ++v) Vec16<T>::unpack(np[v * LPC], &bA[v * VEC]);
                     // lane 0 of the group keeps the group's share
-                    if ((LPC == 1 || sub == 0) && x > T(0)) lacc.add((double)x, (double)s, llh_tab);
+                    if constexpr (MODE == MODE_ELBO) {
+                        const bool ok = s >= Vec16<T>::tiny();
+                        any_bad |= x > T(0) && !ok;
+                        if ((LPC == 1 || sub == 0) && x > T(0) && ok) lacc.add_log((double)x, (double)s, llh_tab);
+                    } else if ((LPC == 1 || sub == 0) && x > T(0)) lacc.add((double)x, (double)s, llh_tab);
                 }
             };
             auto roll_step = [&](auto I_) {
@@ -924,6 +1080,10 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
                                 const T q = fast_div(x, s);
 #pragma unroll
                                 for (int k = 0; k < KL; ++k) acc[k] = fma_t(q, b[k], acc[k]);
+                            } else if constexpr (MODE == MODE_ELBO) {
+                                const bool ok = s >= Vec16<T>::tiny();
+                                any_bad |= x > T(0) && !ok;
+                                if ((LPC == 1 || sub == 0) && x > T(0) && ok) lacc.add_log((double)x, (double)s, llh_tab);
                             } else {
                                 // lane 0 of the group keeps the group's share
                                 if ((LPC == 1 || sub == 0) && x > T(0)) lacc.add((double)x, (double)s, llh_tab);
@@ -944,10 +1104,19 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
         }
     }
 
-    if (MODE == MODE_LLH) {
+    if (LOGS) {
         llh += lacc.total();   // zero where nothing was added
         // which lanes hold a share: all (LPC 1), lanes 0-1 of a group (paired steps), lane 0 (else)
         if (LPC > 1 && !(PAIR ? sub < 2 : sub == 0)) llh = 0.0;
+        if constexpr (MODE == MODE_ELBO) {
+            if (__builtin_expect(any_bad && live, 0)) {   // group-uniform; rare: see slow_task_elbo
+                const double r = slow_task_elbo<T, NV, LPC, PACK>(
+                    a.entries, (size_t)a.task_wave_off[(size_t)task * a.wpb + wv] + grp, st, w0, w1, a.win_rows, a.ring,
+                    a.slot_bytes / 16, a.single, GPW, a.log_major + (size_t)major * KP, a.log_minor, sub, a.K,
+                    BAL ? a.minor_of + (size_t)blk * a.n_virtual : nullptr);
+                llh = sub == 0 ? r : 0.0;
+            }
+        }
         llh = wave_sum(llh);
         if (lane == 0) a.wave_out[(size_t)task * a.wpb + wv] = llh;
         return;
@@ -1092,6 +1261,9 @@ static hipError_t launch_tile_b(const TileArgs<T> &a_in, int mode, int64_t n_tas
             if (e == hipSuccess)
                 e = hipFuncSetAttribute((const void *)tile_sweep_kernel<T, NV, LPC, MODE_LLH, MAXT, PACK, BAL>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute((const void *)tile_sweep_kernel<T, NV, LPC, MODE_ELBO, MAXT, PACK, BAL>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
             if (e != hipSuccess) { raised = 0; return e; }
         }
     }
@@ -1099,6 +1271,8 @@ static hipError_t launch_tile_b(const TileArgs<T> &a_in, int mode, int64_t n_tas
         hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_PHI, MAXT, PACK, BAL>), grid, block, lds_bytes, st, a);
     else if (mode == MODE_LLH)
         hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_LLH, MAXT, PACK, BAL>), grid, block, lds_bytes, st, a);
+    else if (mode == MODE_ELBO)
+        hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_ELBO, MAXT, PACK, BAL>), grid, block, lds_bytes, st, a);
     else   // one-off: the 1024-thread bound serves every workgroup size (one instantiation instead of two)
         hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_RANDOM, 1024, PACK>), grid, block, 0, st, a);
     return hipGetLastError();
@@ -1163,8 +1337,10 @@ static hipError_t launch_sweep_t(const SweepArgs<T> &a, int mode, int64_t n_wave
     dim3 grid((unsigned)(n_waves / 4)), block(256);
     if (mode == MODE_PHI)
         hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_PHI>), grid, block, 0, st, a);
-    else
+    else if (mode == MODE_LLH)
         hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_LLH>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_ELBO>), grid, block, 0, st, a);
     return hipGetLastError();
 }
 template <typename T, int NV, int LPC>

@@ -27,6 +27,15 @@ def mean_negative(llh, gl, nnz):
     return -(llh - gl) / nnz if nnz else float("nan")
 
 
+ELBO_TERMS = ("data", "logfac", "rate", "cell", "gene")
+
+
+def elbo_dict(data, logfac, rate, cell, gene):
+    """The five terms of the ELBO and their total, data - logfac - rate + cell + gene."""
+    return {"data": data, "logfac": logfac, "rate": rate, "cell": cell, "gene": gene,
+            "elbo": data - logfac - rate + cell + gene}
+
+
 class DeviceCAVI(object):
     """CAVI state on one MI355X.
 
@@ -251,6 +260,17 @@ class DeviceCAVI(object):
     def mean_negative_pois_llh(self):
         llh, gl, nnz = self.loss_terms()
         return mean_negative(llh, gl, nnz)
+
+    def elbo_terms(self, ap, cp):
+        """The evidence lower bound of the current state over the local cells, by term:
+        {'data', 'logfac', 'rate', 'cell', 'gene', 'elbo'}, elbo = data - logfac - rate + cell + gene.
+        ap, cp: the shape priors of xi / eta (a, c, bp, dp are the engine's, set_hypers)."""
+        t = (ctypes.c_double * 5)()
+        _lib.check(self._lib.schpf_elbo_terms(self._h, float(ap), float(cp), t))
+        return elbo_dict(*t)
+
+    def elbo(self, ap, cp):
+        return self.elbo_terms(ap, cp)["elbo"]
 
     def synchronize(self):
         _lib.check(self._lib.schpf_synchronize(self._h))

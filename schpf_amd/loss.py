@@ -13,7 +13,7 @@ import numpy as np
 from .hpf_hip import compute_pois_llh
 
 __all__ = ["loss_function_for_data", "projection_loss_function", "pois_llh_pointwise",
-           "mean_negative_pois_llh"]
+           "mean_negative_pois_llh", "elbo"]
 
 
 def loss_function_for_data(loss_function, X):
@@ -96,3 +96,25 @@ def pois_llh_pointwise(X, *, theta, beta, single_process=False, **kwargs):
 def mean_negative_pois_llh(X, *, theta, beta, single_process=False, **kwargs):
     """Mean over the stored nonzeros of X of the negative Poisson log-likelihood."""
     return np.mean(-pois_llh_pointwise(X=X, theta=theta, beta=beta))
+
+
+def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=None, **kwargs):
+    """The evidence lower bound of the variational state (xi, eta, theta, beta) on X, with the responsibilities at
+    their optimum, evaluated on the GPU: X is uploaded, the state set and the ELBO computed.
+
+    terms=True returns the dict {'data', 'logfac', 'rate', 'cell', 'gene', 'elbo'}, else the total.  `device`: HIP
+    device ordinal, default $SCHPF_DEVICE or 0.
+    """
+    from .engine import DeviceCAVI   # late import, as in projection_loss_function
+    import os
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    if not hasattr(X, "row"):
+        X = X.tocoo()
+    with DeviceCAVI(X.shape[0], X.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
+        eng.upload(X)
+        eng.set_hypers(a, c, bp, dp)
+        for name, g in (("xi", xi), ("theta", theta), ("eta", eta), ("beta", beta)):
+            eng.set_gamma(name, g.vi_shape, g.vi_rate)
+        out = eng.elbo_terms(ap, cp)
+    return out if terms else out["elbo"]

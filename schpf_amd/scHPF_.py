@@ -290,22 +290,42 @@ class scHPF(BaseEstimator):
         beta = self.beta if beta is None else beta
         return ls.mean_negative_pois_llh(X=X, theta=theta, beta=beta)
 
+    def elbo(self, X, terms=False, device=None):
+        """The evidence lower bound of the fitted model on X, evaluated on the GPU (schpf_amd.loss.elbo)."""
+        return ls.elbo(X, a=self.a, ap=self.ap, bp=self.bp, c=self.c, cp=self.cp, dp=self.dp, xi=self.xi,
+                       eta=self.eta, theta=self.theta, beta=self.beta, terms=terms, device=device)
+
     # ---------------------------------------------------------------- fit/project
-    def fit(self, X, **kwargs):
-        """Fit the model to the cell x gene count matrix X (scHPF_.py:425-445)."""
-        (self.bp, self.dp, self.xi, self.eta, self.theta, self.beta, self.loss) = self._fit(X, **kwargs)
+    def fit(self, X, record_elbo=False, **kwargs):
+        """Fit the model to the cell x gene count matrix X (scHPF_.py:425-445).
+
+        record_elbo=True (an addition): the ELBO is also evaluated on the device at every loss check and kept as
+        `self.elbo_`, a list as long as `self.loss`.  The stop rule stays on the loss."""
+        elbos = [] if record_elbo else None
+        (self.bp, self.dp, self.xi, self.eta, self.theta, self.beta, self.loss) = self._fit(X, elbo_out=elbos, **kwargs)
+        self._set_elbo_record(elbos)
         return self
 
+    def _set_elbo_record(self, elbos):
+        """`elbo_` := the ELBO trace of the fit that just ran, or no `elbo_` at all when it recorded none (an earlier
+        fit's trace would no longer belong to the state)."""
+        if elbos is not None:
+            self.elbo_ = elbos
+        elif "elbo_" in self.__dict__:
+            del self.elbo_
+
     def project(self, X, recalc_bp=False, replace=False, min_iter=2, max_iter=50, check_freq=2,
-                **kwargs):
-        """Fit xi/theta of new cells against frozen eta/beta (scHPF_.py:448-503)."""
+                record_elbo=False, **kwargs):
+        """Fit xi/theta of new cells against frozen eta/beta (scHPF_.py:448-503).  record_elbo: as fit()."""
         if replace and recalc_bp:
             raise ValueError("Cannot replace `bp` with recalculated value")
         model = self if replace else deepcopy(self)
         if recalc_bp:
             model.bp = None
+        elbos = [] if record_elbo else None
         bp, _, xi, _, theta, _, loss = model._fit(X, min_iter=min_iter, max_iter=max_iter,
-                                                 check_freq=check_freq, freeze_genes=True, **kwargs)
+                                                 check_freq=check_freq, freeze_genes=True, elbo_out=elbos, **kwargs)
+        model._set_elbo_record(elbos)
         if replace:
             self.xi, self.theta = xi, theta
             return loss
@@ -316,7 +336,7 @@ class scHPF(BaseEstimator):
              max_iter=None, epsilon=None, check_freq=None, single_process=False,
              checkstep_function=None, verbose=None, batchsize=None,
              beta_theta_simultaneous=False, loss_smoothing=1, device=None, init="auto", engine=None,
-             devices=None):
+             devices=None, elbo_out=None):
         """The CAVI loop (scHPF_.py:526-780) on the GPU.
 
         Keyword arguments are the reference's.  `single_process` is accepted and
@@ -334,12 +354,16 @@ class scHPF(BaseEstimator):
         device too: the matrix goes up once and each batch's rows are gathered in HBM
         (_fit_minibatch); only when the whole matrix does not fit beside its plans are the
         batch's rows sliced on the host and uploaded per iteration, like the reference re-slices.
+        `elbo_out`, a list: the ELBO at every loss check is appended to it (fit / project record_elbo).
         Returns (bp, dp, xi, eta, theta, beta, loss) like the reference.
         """
         assert loss_smoothing > 0
         if not hasattr(X, "row"):
             X = X.tocoo()
         batched = batchsize is not None and 1 < batchsize <= X.shape[0]
+        if elbo_out is not None and batchsize is not None:
+            raise ValueError("record_elbo needs full-data iterations: a minibatch iteration (batchsize) is not "
+                             "coordinate ascent on the whole matrix")
         nfactors, (ncells, ngenes) = self.nfactors, X.shape
         a, ap, c, cp = self.a, self.ap, self.c, self.cp
 
@@ -436,6 +460,8 @@ class scHPF(BaseEstimator):
                         else:
                             curr = loss_function(a=a, ap=ap, bp=bp, c=c, cp=cp, dp=dp, xi=xi,
                                                  eta=eta, theta=theta, beta=beta)
+                    if elbo_out is not None:   # read-only evaluation of the state the loss saw
+                        elbo_out.append(eng.elbo(ap, cp))
                     curr, pct = monitor.record(curr)
                     if verbose:
                         print("[Iter. {0: >4}]  loss:{1:.6f}  pct:{2:.9f}".format(t, curr, pct))

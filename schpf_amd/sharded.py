@@ -22,7 +22,7 @@ import inspect
 
 import numpy as np
 
-from .engine import mean_negative
+from .engine import elbo_dict, mean_negative
 
 __all__ = ["row_partition", "take_rows", "ShardedCAVI", "exchange_tensor_of", "ThreadedShards", "NativeShard"]
 
@@ -278,6 +278,16 @@ class ThreadedShards(object):
         terms = self._each(lambda r: self.engines[r].loss_terms())   # same process: sum on the host
         llh = sum(t[0] for t in terms); gl = sum(t[1] for t in terms); nnz = sum(t[2] for t in terms)
         return mean_negative(llh, gl, nnz)
+
+    def elbo_terms(self, ap, cp):
+        """The ELBO of the whole matrix: data, logfac, rate and cell summed over the shards; gene (eta and beta are
+        replicated) from one shard."""
+        terms = self._each(lambda r: self.engines[r].elbo_terms(ap, cp))
+        tot = {k: sum(t[k] for t in terms) for k in ("data", "logfac", "rate", "cell")}
+        return elbo_dict(gene=terms[0]["gene"], **tot)
+
+    def elbo(self, ap, cp):
+        return self.elbo_terms(ap, cp)["elbo"]
 
     def close(self):
         engines, self.engines = getattr(self, "engines", []), []
