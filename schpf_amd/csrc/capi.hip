@@ -139,6 +139,23 @@ struct TileDev {
     bool packed = false;
 };
 
+// Everything the engine holds once per matrix axis.  Engine::side[0] is the cell axis (major = cell: xi, theta), side[1]
+// the gene axis (eta, beta) -- the numbering of run_sweep, loss_side, order_of and the policy.  The records live inside
+// the engine and never move: captured graphs bake the DevBuf::p pointers in.
+struct Side {
+    int n = 0;                         // rows of this axis: N / G
+    DevBuf cap_shape, cap_rate;        // xi / eta                            [n]
+    DevBuf shape, rate;                // theta / beta (C-contiguous)         [n, K]
+    DevBuf tab_exp, tab_e, tab_log;    // tables, padding columns zero        [n, KP]
+    DevBuf colpart;                    // the update kernel's column partials double[UPD_BLOCKS * K]
+    DevBuf count;                      // ELBO: sum of the stored counts of each row of this axis, double[n]
+    PlanDev plan;                      // gather plan with this axis as major
+    TileDev tile;                      // tile plan (LDS-staged sweep) with this axis as major
+    bool dirty = true;                 // the tables and column sums are older than the parameters
+    Side() = default;
+    Side(const Side &) = delete; Side &operator=(const Side &) = delete;
+};
+
 struct Profiler {
     bool on = false;
     struct Rec { int kind; hipEvent_t a, b; };
@@ -281,20 +298,14 @@ namespace {
 
 template <typename T> struct Engine final : schpf_ctx {
     const schpf::Tuning tuning = schpf::tuning_from_env();   // the switches, read once at schpf_create
-    // variational parameters (C-contiguous, stride K)
-    DevBuf xi_s, xi_r, th_s, th_r, eta_s, eta_r, be_s, be_r;
-    // tables, stride KP, padding columns zero
-    DevBuf th_exp, th_e, th_log, be_exp, be_e, be_log;
-    DevBuf exchange_buf;                            // [G*K + K] of T
-    DevBuf dense_cell;                              // [N*K] of T (t = 0 only)
-    DevBuf s_theta, s_beta, s_beta_next;            // double[K]
-    DevBuf colpart_cell, colpart_gene;              // double[UPD_BLOCKS * K]
+    Side side[2];                                   // 0: cells, 1: genes.  Below: what exists once, or for one axis only
+    DevBuf exchange_buf;                            // gene side: [G*K + K] of T, the sums a sharded fit all-reduces + K sums of E[theta]
+    DevBuf dense_cell;                              // cell side: [N*K] of T (t = 0 only; the genes' twin is the exchange buffer)
+    DevBuf s_theta, s_beta, s_beta_next;            // double[K] column sums of E[theta], E[beta]; beta's double-buffered (beta_parity)
     DevBuf wave_out, scalars;                       // llh per wave; scalars[0]=llh sum
     // the loss pass's two results land in pinned host memory that the device writes directly: the reduction kernels
     // store there, the host reads after the stream has drained -- no copy of 24 bytes out of pageable memory per check
     double *loss_host = nullptr;
-    PlanDev cell, gene;                             // gather plans: major = cell / major = gene
-    TileDev tcell, tgene;                           // tile plans (LDS-staged sweep)
     DevBuf dual_order;                              // merged launch order of both plans' tasks (or empty)
     DevBuf dual_queue;                              // persistent dual launch: {next slot, workgroups done}, self-zeroing
     DevBuf clock_probe;                             // 5 x u64: shader cycles, constant-rate ticks, 2 start stamps, launches (sweep_impl.h)
@@ -304,10 +315,8 @@ template <typename T> struct Engine final : schpf_ctx {
     double gammaln_sum = 0.0;
     int64_t n_rounded = 0, n_zero = 0;              // upload facts: values rounded to float32; stored zeros
     DevBuf zero_row, zero_col;                      // positions of explicitly stored zeros (loss only)
-    DevBuf count_row, count_col;                    // ELBO: sum of the stored counts of each cell / gene (double[N], [G])
     DevBuf elbo_part, elbo_sums;                    // ELBO: Gamma-term block partials, their sums (elbo_terms)
     bool have_coo = false;
-    bool dirty_theta = true, dirty_beta = true;
     int pending_init = 0;  // 0 none, 1 dense accumulators, 2 chunk partials
     // n iterations captured as one hipGraph (schpf_steps): the state is device-resident and nothing on
     // the host changes between two loss checks, so a fit replays one graph per check interval
@@ -327,7 +336,7 @@ template <typename T> struct Engine final : schpf_ctx {
     // its plans, the matrix once more as a (row, col)-sorted device copy; a batch engine's upload_rows(source,
     // rows) gathers its rows from there and builds its plans from device arrays -- no host slicing, no PCIe.
     bool want_rows = false, rows_packed_ok = true;
-    DevBuf rows_ptr, rows_col, rows_val;            // int64[N + 1], int32[nnz], float[nnz]; host copy of rows_ptr: tcell.host.mptr
+    DevBuf rows_ptr, rows_col, rows_val;            // int64[N + 1], int32[nnz], float[nnz]; host copy of rows_ptr: the cell tile plan's mptr
     bool have_loss_constants = true;                // false after upload_rows (no lgamma sum / stored-zero list for a batch)
     // balanced windows (plan.h): on for uploads of a whole matrix; off for an engine that keeps a (row, col)-sorted copy
     // (the plans' own order is then the virtual one) and for batch engines, which re-plan every iteration
@@ -335,6 +344,10 @@ template <typename T> struct Engine final : schpf_ctx {
     bool transient = false;             // schpf_hint_transient: the matrix is replaced every iteration, plan the cheapest way
     bool planning_batch_rows = false;   // inside schpf_upload_rows (gathered batch rows: no loss constants, no loss tasks)
     bool expect_sharded = false;        // schpf_hint_sharded: a rank of a sharded fit (gene-side sums leave for an all-reduce)
+    int cu_count = 256;
+    bool gammaln_on_device = false;     // the device plan builder has left sum lgamma(x + 1) in scalars[1] already
+    DevBuf gammaln_part;
+    double count_seconds = 0.0;         // wall time of count_sums: part of the upload's, reported by SCHPF_VERBOSE=1
     static constexpr int UPD_BLOCKS = 2048;
     static constexpr size_t TABLE_PAD = 256 * 1024;
 
@@ -387,17 +400,17 @@ template <typename T> struct Engine final : schpf_ctx {
         const size_t s = sizeof(T);
         dual_queue.alloc(2 * sizeof(int), true, stream);
         clock_probe.alloc(8 * sizeof(unsigned long long), true, stream);
-        xi_s.alloc((size_t)N * s); xi_r.alloc((size_t)N * s);
-        eta_s.alloc((size_t)G * s); eta_r.alloc((size_t)G * s);
-        th_s.alloc((size_t)N * K * s); th_r.alloc((size_t)N * K * s);
-        be_s.alloc((size_t)G * K * s); be_r.alloc((size_t)G * K * s);
-        // + TABLE_PAD zero bytes: slack behind the last row for whole-piece copies
-        for (DevBuf *b : {&th_exp, &th_e, &th_log}) b->alloc((size_t)N * KP * s + TABLE_PAD, true, stream);
-        for (DevBuf *b : {&be_exp, &be_e, &be_log}) b->alloc((size_t)G * KP * s + TABLE_PAD, true, stream);
+        side[0].n = N; side[1].n = G;
+        for (Side &sd : side) {
+            const size_t n = (size_t)sd.n;
+            sd.cap_shape.alloc(n * s); sd.cap_rate.alloc(n * s);
+            sd.shape.alloc(n * K * s); sd.rate.alloc(n * K * s);
+            // + TABLE_PAD zero bytes: slack behind the last row for whole-piece copies
+            for (DevBuf *b : {&sd.tab_exp, &sd.tab_e, &sd.tab_log}) b->alloc(n * KP * s + TABLE_PAD, true, stream);
+            sd.colpart.alloc((size_t)UPD_BLOCKS * K * sizeof(double));
+        }
         exchange_buf.alloc(((size_t)G * K + K) * s, true, stream);
         for (DevBuf *b : {&s_theta, &s_beta, &s_beta_next}) b->alloc((size_t)K * sizeof(double), true, stream);
-        colpart_cell.alloc((size_t)UPD_BLOCKS * K * sizeof(double));
-        colpart_gene.alloc((size_t)UPD_BLOCKS * K * sizeof(double));
         scalars.alloc(8 * sizeof(double), true, stream);
         if (hipHostMalloc((void **)&loss_host, 8 * sizeof(double), hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
@@ -405,6 +418,14 @@ template <typename T> struct Engine final : schpf_ctx {
         } else std::memset(loss_host, 0, 8 * sizeof(double));
     }
     void hypers_changed() override { drop_graph(); }
+    // the hyper-parameters stay where the C ABI sets them (schpf_ctx)
+    double prior_shape(int s) const { return s == 0 ? a : c; }
+    double cap_prior_rate(int s) const { return s == 0 ? bp : dp; }   // of the side's capacities (xi / eta)
+    // an iteration would do nothing that must happen only once: a stretch of them may be captured as a graph
+    bool steady() const
+    {
+        return !prof.on && stream != nullptr && pending_init == 0 && eager_since_upload && !side[0].dirty && !side[1].dirty;
+    }
     // the engine holds no count matrix any more: plans, row copy and captured graphs released; step / loss calls
     // raise until the next successful upload
     void forget_matrix()
@@ -412,11 +433,10 @@ template <typename T> struct Engine final : schpf_ctx {
         have_coo = false;
         drop_graph();
         HIPCHK(hipStreamSynchronize(stream));
-        cell = PlanDev(); gene = PlanDev(); tcell = TileDev(); tgene = TileDev();
+        for (Side &sd : side) { sd.plan = PlanDev(); sd.tile = TileDev(); sd.count.release(); }
         dual_order.release(); dual_slots = 0;
         rows_ptr.release(); rows_col.release(); rows_val.release();
         zero_row.release(); zero_col.release();
-        count_row.release(); count_col.release();
         pending_init = 0;
         eager_since_upload = false;
     }
@@ -461,8 +481,7 @@ template <typename T> struct Engine final : schpf_ctx {
     void steps(unsigned flags_, int n) override
     {
         if (n < 0) throw std::invalid_argument("n must be >= 0");
-        const bool graphable = tuning.graph && !prof.on && stream != nullptr && pending_init == 0 &&
-                               eager_since_upload && !dirty_theta && !dirty_beta && !(flags_ & SCHPF_SHARDED);
+        const bool graphable = tuning.graph && steady() && !(flags_ & SCHPF_SHARDED);
         int done = 0;
         if (graphable && n >= 2) {
             const int even = n & ~1;
@@ -505,8 +524,7 @@ template <typename T> struct Engine final : schpf_ctx {
         // communicator, which is all this build could ever run it with; with more ranks every rank must replay the same
         // graph, so there it stays opt-in (SCHPF_GRAPH_SHARDED=1) until tests/test_multigpu.py has seen two GPUs.
         int done = 0;
-        const bool graphable = tuning.graph_sharded.value_or(comm_world == 1) && !prof.on && stream != nullptr &&
-                               pending_init == 0 && eager_since_upload && !dirty_theta && !dirty_beta && !freeze;
+        const bool graphable = tuning.graph_sharded.value_or(comm_world == 1) && steady() && !freeze;
         if (graphable && n >= 2) {
             const int even = n & ~1;
             hipGraphExec_t exec = graph_for(base | 0x80000000u, even, iterate);
@@ -672,37 +690,40 @@ template <typename T> struct Engine final : schpf_ctx {
         gammaln_on_device = true;
         if (want_rows) {   // the (row, col)-sorted copy minibatches gather their rows from
             rows_col.alloc((size_t)nnz * 4); rows_val.alloc((size_t)nnz * 4);
-            HIPCHK(schpf::launch_gather_by_order(tcell.order_identity ? nullptr : tcell.order_dev.as<int>(),
+            const TileDev &tc = side[0].tile;   // the cell plan's order; rows_ptr's host copy stays tc.host.mptr
+            HIPCHK(schpf::launch_gather_by_order(tc.order_identity ? nullptr : tc.order_dev.as<int>(),
                                                  static_cast<const int *>(early.d_col.p), d_val.as<float>(), nnz, rows_col.as<int>(),
                                                  rows_val.as<float>(), stream));
-            upload(rows_ptr, tcell.host.mptr, stream);
+            upload(rows_ptr, tc.host.mptr, stream);
             rows_packed_ok = packed_ok;
             HIPCHK(hipStreamSynchronize(stream));
         }
         if (tuning.verbose)
             fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
                     "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
-                    t1 - t0, early.seconds, now_s() - t1, (tcell.entries.bytes + tgene.entries.bytes) * 1e-9);
+                    t1 - t0, early.seconds, now_s() - t1, (side[0].tile.entries.bytes + side[1].tile.entries.bytes) * 1e-9);
     }
 
     // both tile plans from a COO that is already in HBM
     void plans_from_device_coo(const DevBuf &d_row, const DevBuf &d_col, const DevBuf &d_val, bool rc_sorted,
                                bool cr_sorted, bool packed_ok, const int ranges[2], const int half[2])
     {
-        const schpf::TileShape sh_c = schpf::tile_shape(problem(), tuning, N, G, ranges[0], half[0]),
-                               sh_g = schpf::tile_shape(problem(), tuning, G, N, ranges[1], half[1]);
+        // per side: its index array is the major one, the other side's the minor one
+        const int32_t *const d_idx[2] = {d_row.as<int32_t>(), d_col.as<int32_t>()};
+        const bool sorted[2] = {rc_sorted, cr_sorted};
+        const schpf::TileShape shapes[2] = {tile_shape_of(0, ranges, half), tile_shape_of(1, ranges, half)};
         // the two orientations are independent (the COO is only read): the gene side on a helper thread with a
         // stream of its own, so that the builders' host round trips (run pointers, step counts, allocations) and
         // their short kernels overlap instead of adding up
-        auto build_side = [&](int side, hipStream_t st) {
-            TileDev &td = side == 0 ? tcell : tgene;
+        auto build_side = [&](int si, hipStream_t st) {
+            TileDev &td = side[si].tile;
             void *e = nullptr, *s = nullptr, *o = nullptr;
             size_t eb = 0;
-            bool presorted = side == 0 ? rc_sorted : cr_sorted;
-            const int32_t *d_major = side == 0 ? d_row.as<int32_t>() : d_col.as<int32_t>();
-            const int32_t *d_minor = side == 0 ? d_col.as<int32_t>() : d_row.as<int32_t>();
-            const schpf::TileShape &sh = side == 0 ? sh_c : sh_g;
-            int n_minor_plan = side == 0 ? G : N;
+            bool presorted = sorted[si];
+            const int32_t *d_major = d_idx[si], *d_minor = d_idx[1 - si];
+            const schpf::TileShape &sh = shapes[si];
+            const int n_major = side[si].n;
+            int n_minor_plan = side[1 - si].n;
             DevBuf vminor;
             td.minor_of.release(); td.n_virtual = 0;
             if (balance_now && sh.ring <= 1 && sh.waves_per_block >= 12) {   // the balanced kernels are 1024-thread ones
@@ -714,7 +735,7 @@ template <typename T> struct Engine final : schpf_ctx {
                 bool balanced = true;
                 try {
                     vminor.alloc((size_t)nnz * 4);
-                    schpf::balance_windows_device((void *)st, nnz, d_major, d_minor, side == 0 ? N : G, n_minor_plan, sh,
+                    schpf::balance_windows_device((void *)st, nnz, d_major, d_minor, n_major, n_minor_plan, sh,
                                                   vminor.as<int32_t>(), &mo, geo);
                 } catch (const std::invalid_argument &) {
                     throw;
@@ -722,7 +743,7 @@ template <typename T> struct Engine final : schpf_ctx {
                     (void)hipGetLastError();
                     balanced = false;
                     if (tuning.verbose)
-                        fprintf(stderr, "[schpf_hip]   balanced windows, side %d: not built (%s); windows by index\n", side, e.what());
+                        fprintf(stderr, "[schpf_hip]   balanced windows, side %d: not built (%s); windows by index\n", si, e.what());
                 }
                 if (balanced) {
                     td.minor_of.p = mo; td.minor_of.bytes = (size_t)geo.n_blocks * geo.n_virtual * 4;
@@ -732,11 +753,11 @@ template <typename T> struct Engine final : schpf_ctx {
                     presorted = false;
                 } else vminor.release();
                 if (tuning.verbose)
-                    fprintf(stderr, "[schpf_hip]   balanced windows, side %d: %d sections of %d windows, %.3f s\n", side,
+                    fprintf(stderr, "[schpf_hip]   balanced windows, side %d: %d sections of %d windows, %.3f s\n", si,
                             geo.n_sections, geo.D, now_s() - tb);
             }
             schpf::build_tile_plan_device((void *)st, nnz, d_major, d_minor, d_val.as<float>(),
-                                          presorted, packed_ok, side == 0 ? N : G, n_minor_plan,
+                                          presorted, packed_ok, n_major, n_minor_plan,
                                           sh, td.host, &e, &eb, &s, &o);
             td.entries.release(); td.entries.p = e; td.entries.bytes = eb;
             td.steps.release(); td.steps.p = s; td.steps.bytes = td.host.steps.size() * 2;
@@ -761,8 +782,7 @@ template <typename T> struct Engine final : schpf_ctx {
         try { build_side(0, stream); } catch (...) { helper.join(); throw; }
         helper.join();
         if (err) std::rethrow_exception(err);
-        finish_tile(tcell);
-        finish_tile(tgene);
+        for (Side &sd : side) finish_tile(sd.tile);
         build_dual_order();
     }
 
@@ -777,7 +797,7 @@ template <typename T> struct Engine final : schpf_ctx {
         if (src->G != G || src->K != K) throw std::invalid_argument("source and batch engine differ in genes or factors");
         if (n_rows != N) throw std::invalid_argument("n_rows must be the number of cells the batch engine was created with");
         if (!want_tile) throw std::invalid_argument("upload_rows needs the tile plan");
-        const std::vector<int64_t> &sp = src->tcell.host.mptr;
+        const std::vector<int64_t> &sp = src->side[0].tile.host.mptr;   // host copy of src->rows_ptr
         std::vector<int64_t> dp((size_t)n_rows + 1, 0);
         for (int i = 0; i < n_rows; ++i) {
             if (rows[i] < 0 || rows[i] >= src->N) throw std::invalid_argument("batch row out of range");
@@ -801,7 +821,7 @@ template <typename T> struct Engine final : schpf_ctx {
         try { plans_from_device_coo(d_row, d_col, d_val, true, false, src->rows_packed_ok, ranges, half); }
         catch (...) { planning_batch_rows = false; throw; }
         planning_batch_rows = false;
-        wave_out.alloc((size_t)std::max<int64_t>(tcell.n_wave_out, 1) * sizeof(double), true, stream);
+        wave_out.alloc((size_t)std::max<int64_t>(side[0].tile.n_wave_out, 1) * sizeof(double), true, stream);
         HIPCHK(hipStreamSynchronize(stream));
         n_rounded = 0; n_zero = 0;
         zero_row.release(); zero_col.release();
@@ -812,11 +832,14 @@ template <typename T> struct Engine final : schpf_ctx {
         eager_since_upload = false;
     }
 
-    int cu_count = 256;
     schpf::Problem problem() const
     {
         return {N, G, K, (int)sizeof(T), nnz, cu_count, LPC, NV, KL, KP, expect_sharded, transient, want_rows,
                 planning_batch_rows, balance_now};
+    }
+    schpf::TileShape tile_shape_of(int s, const int ranges[2], const int half[2]) const
+    {
+        return schpf::tile_shape(problem(), tuning, side[s].n, side[1 - s].n, ranges[s], half[s]);
     }
 
     // both orientations are built concurrently on the host (each with its own thread team),
@@ -825,47 +848,43 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         int ranges[2] = {0, 0}, half[2] = {-1, -1};
         if (!schpf::choose_ranges(problem(), tuning, row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
-        const schpf::TileShape sh_c = schpf::tile_shape(problem(), tuning, N, G, ranges[0], half[0]),
-                               sh_g = schpf::tile_shape(problem(), tuning, G, N, ranges[1], half[1]);
+        const int32_t *const idx[2] = {row, col};   // per side: its index array is the major one, the other's the minor one
+        const schpf::TileShape shapes[2] = {tile_shape_of(0, ranges, half), tile_shape_of(1, ranges, half)};
         std::exception_ptr err;
-        double secs_gene = 0.0;
+        double secs[2] = {0.0, 0.0};
         // balanced windows: the builder runs on the block's virtual numbering of the minor rows (plan.h)
-        std::vector<int32_t> mo_cell, mo_gene;
-        auto build_host = [&](const int32_t *major, const int32_t *minor, int n_major, int n_minor, const schpf::TileShape &sh,
-                              TileDev &td, std::vector<int32_t> &mo) {
+        std::vector<int32_t> mo[2];
+        auto build_host = [&](int s) {
+            const double t0 = now_s();
+            const int32_t *major = idx[s], *minor = idx[1 - s];
+            const int n_major = side[s].n, n_minor = side[1 - s].n;
+            const schpf::TileShape &sh = shapes[s];
+            TileDev &td = side[s].tile;
             td.n_virtual = 0;
             if (balance_now && sh.ring <= 1 && sh.waves_per_block >= 12) {
                 schpf::BigVec<int32_t> vminor;
                 schpf::BalanceGeometry geo;
-                schpf::balance_windows_host(nnz, major, minor, n_major, n_minor, sh, vminor, mo, geo);
+                schpf::balance_windows_host(nnz, major, minor, n_major, n_minor, sh, vminor, mo[s], geo);
                 td.n_virtual = geo.n_virtual;
                 schpf::build_tile_plan(nnz, major, vminor.data(), val, n_major, geo.n_virtual, sh, true, td.host);
             } else {
                 schpf::build_tile_plan(nnz, major, minor, val, n_major, n_minor, sh, true, td.host);
             }
+            secs[s] = now_s() - t0;
         };
-        std::thread side([&] {
-            try {
-                const double t0 = now_s();
-                build_host(col, row, G, N, sh_g, tgene, mo_gene);
-                secs_gene = now_s() - t0;
-            } catch (...) { err = std::current_exception(); }
+        std::thread helper([&] {   // the gene side
+            try { build_host(1); } catch (...) { err = std::current_exception(); }
         });
-        double secs_cell = 0.0;
-        try {
-            const double t0 = now_s();
-            build_host(row, col, N, G, sh_c, tcell, mo_cell);
-            secs_cell = now_s() - t0;
-        } catch (...) { side.join(); throw; }
-        side.join();
+        try { build_host(0); } catch (...) { helper.join(); throw; }
+        helper.join();
         if (err) std::rethrow_exception(err);
-        upload_tile(tcell, secs_cell);
-        upload_tile(tgene, secs_gene);
-        tcell.minor_of.release(); tgene.minor_of.release();
-        mo_cell.resize(mo_cell.size() + 16, -1);   // a list is copied in 16-byte pieces: slack behind the last one
-        mo_gene.resize(mo_gene.size() + 16, -1);
-        if (tcell.n_virtual) upload(tcell.minor_of, mo_cell, stream);
-        if (tgene.n_virtual) upload(tgene.minor_of, mo_gene, stream);
+        for (int s = 0; s < 2; ++s) upload_tile(side[s].tile, secs[s]);
+        for (int s = 0; s < 2; ++s) {
+            TileDev &td = side[s].tile;
+            td.minor_of.release();
+            mo[s].resize(mo[s].size() + 16, -1);   // a list is copied in 16-byte pieces: slack behind the last one
+            if (td.n_virtual) upload(td.minor_of, mo[s], stream);
+        }
         HIPCHK(hipStreamSynchronize(stream));
         build_dual_order();
     }
@@ -873,12 +892,13 @@ template <typename T> struct Engine final : schpf_ctx {
     void build_dual_order()
     {
         // Both sweeps of an iteration in one launch (kernels.h launch_tile_sweep_dual) when the two
-        // plans agree on the workgroup shape: slots = all tasks of both plans, longest first
+        // plans agree on the workgroup shape: slots = all tasks of both plans, longest first.  Not symmetric: the kernel
+        // takes (cell args, gene args) in that order and a slot names a cell task as `task`, a gene task as `~task`
         dual_slots = 0;
         dual_order.release();
-        if (tuning.dual && tcell.threads == tgene.threads && tcell.packed == tgene.packed &&
-            (tcell.n_virtual != 0) == (tgene.n_virtual != 0)) {
-            const auto &hc = tcell.host, &hg = tgene.host;
+        const TileDev &tc = side[0].tile, &tg = side[1].tile;
+        if (tuning.dual && tc.threads == tg.threads && tc.packed == tg.packed && (tc.n_virtual != 0) == (tg.n_virtual != 0)) {
+            const auto &hc = tc.host, &hg = tg.host;
             std::vector<int32_t> ord;
             ord.reserve((size_t)(hc.n_tasks + hg.n_tasks));
             size_t i = 0, j = 0;   // merge of two lists already sorted by decreasing work
@@ -894,8 +914,6 @@ template <typename T> struct Engine final : schpf_ctx {
         }
     }
 
-    bool gammaln_on_device = false;
-    DevBuf gammaln_part;
     void gammaln_partial_sums(const float *d_values)
     {
         const int nb = 512;
@@ -905,24 +923,18 @@ template <typename T> struct Engine final : schpf_ctx {
     }
 
     // ELBO shift terms (elbo_terms): the stored counts of every cell and every gene, summed over each plan's
-    // (major, minor)-sorted runs while the values are on the device -- once per upload, N + G doubles.  Its wall time
-    // (count_seconds) is part of the upload's and is reported by SCHPF_VERBOSE=1 (DESIGN.md 11 has the measurements)
-    double count_seconds = 0.0;
+    // (major, minor)-sorted runs while the values are on the device -- once per upload, N + G doubles (count_seconds)
     void count_sums(const float *d_values)
     {
         const double t0 = now_s();
-        for (int side = 0; side < 2; ++side) {
+        for (int s = 0; s < 2; ++s) {
+            Side &sd = side[s];
             DevBuf scratch, mp;
             const int *ord = nullptr;
-            if (!use_tile || !(side == 0 ? tcell : tgene).order_identity) {
-                const TileDev &td = side == 0 ? tcell : tgene;
-                ord = use_tile && td.order_dev.p ? td.order_dev.as<int>() : order_of(side, scratch);
-            }
-            upload(mp, use_tile ? (side == 0 ? tcell : tgene).host.mptr : (side == 0 ? cell : gene).host.mptr, stream);
-            DevBuf &out = side == 0 ? count_row : count_col;
-            const int n = side == 0 ? N : G;
-            out.alloc((size_t)n * sizeof(double));
-            HIPCHK(schpf::launch_count_sums(d_values, ord, mp.as<int64_t>(), n, out.as<double>(), stream));
+            if (!use_tile || !sd.tile.order_identity) ord = order_of(s, scratch);
+            upload(mp, major_ptr(s), stream);
+            sd.count.alloc((size_t)sd.n * sizeof(double));
+            HIPCHK(schpf::launch_count_sums(d_values, ord, mp.as<int64_t>(), sd.n, sd.count.as<double>(), stream));
             HIPCHK(hipStreamSynchronize(stream));   // scratch and mp die with this scope
         }
         count_seconds = now_s() - t0;
@@ -1006,14 +1018,14 @@ template <typename T> struct Engine final : schpf_ctx {
         if (use_tile) {
             if (device_plans) build_tiles_device(row, col, v.data(), packed_ok, early);
             else build_tiles(row, col, v.data());
-            n_out = std::max(tcell.n_wave_out, tgene.n_wave_out);   // the loss pass sweeps either plan (loss_side)
+            n_out = std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);   // the loss pass sweeps either plan (loss_side)
         } else {
-            const int wc = schpf::pick_windows((size_t)G * KP * sizeof(T));
-            const int wg = schpf::pick_windows((size_t)N * KP * sizeof(T));
+            const int32_t *const idx[2] = {row, col};
             const int chunk = schpf::gather_chunk_len(problem());
-            build_plan(cell, nnz, row, col, v.data(), N, G, wc, chunk);
-            build_plan(gene, nnz, col, row, v.data(), G, N, wg, chunk);
-            n_out = cell.n_waves;
+            for (int s = 0; s < 2; ++s)   // windows: by the size of the minor side's table
+                build_plan(side[s].plan, nnz, idx[s], idx[1 - s], v.data(), side[s].n, side[1 - s].n,
+                           schpf::pick_windows((size_t)side[1 - s].n * KP * sizeof(T)), chunk);
+            n_out = side[0].plan.n_waves;   // the gather loss pass always sweeps the cell plan (loss_side)
         }
         wave_out.alloc((size_t)std::max<int64_t>(n_out, 1) * sizeof(double), true, stream);
 
@@ -1041,47 +1053,34 @@ template <typename T> struct Engine final : schpf_ctx {
                     count_seconds);
     }
 
-    DevBuf &shape_buf(int which)
+    // SCHPF_XI / THETA / ETA / BETA -> the side's capacity (xi, eta) or loading (theta, beta) buffer
+    static int axis_of(int which) { return which == SCHPF_ETA || which == SCHPF_BETA; }
+    static bool is_loading(int which) { return which == SCHPF_THETA || which == SCHPF_BETA; }
+    DevBuf &state_buf(int which, bool rate)
     {
-        switch (which) {
-        case SCHPF_XI: return xi_s;
-        case SCHPF_THETA: return th_s;
-        case SCHPF_ETA: return eta_s;
-        case SCHPF_BETA: return be_s;
-        }
-        throw std::invalid_argument("which must be SCHPF_XI/THETA/ETA/BETA");
-    }
-    DevBuf &rate_buf(int which)
-    {
-        switch (which) {
-        case SCHPF_XI: return xi_r;
-        case SCHPF_THETA: return th_r;
-        case SCHPF_ETA: return eta_r;
-        case SCHPF_BETA: return be_r;
-        }
-        throw std::invalid_argument("which must be SCHPF_XI/THETA/ETA/BETA");
+        if (which < SCHPF_XI || which > SCHPF_BETA) throw std::invalid_argument("which must be SCHPF_XI/THETA/ETA/BETA");
+        Side &sd = side[axis_of(which)];
+        if (is_loading(which)) return rate ? sd.rate : sd.shape;
+        return rate ? sd.cap_rate : sd.cap_shape;
     }
     size_t state_bytes(int which) const
     {
-        const size_t n = (which == SCHPF_XI || which == SCHPF_THETA) ? (size_t)N : (size_t)G;
-        const size_t k = (which == SCHPF_THETA || which == SCHPF_BETA) ? (size_t)K : 1;
-        return n * k * sizeof(T);
+        return (size_t)side[axis_of(which)].n * (is_loading(which) ? (size_t)K : 1) * sizeof(T);
     }
     void set_state(int which, const void *shape, const void *rate) override
     {
         const size_t b = state_bytes(which);
-        if (shape) HIPCHK(hipMemcpyAsync(shape_buf(which).p, shape, b, hipMemcpyHostToDevice, stream));
-        if (rate) HIPCHK(hipMemcpyAsync(rate_buf(which).p, rate, b, hipMemcpyHostToDevice, stream));
+        if (shape) HIPCHK(hipMemcpyAsync(state_buf(which, false).p, shape, b, hipMemcpyHostToDevice, stream));
+        if (rate) HIPCHK(hipMemcpyAsync(state_buf(which, true).p, rate, b, hipMemcpyHostToDevice, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        if (which == SCHPF_THETA) dirty_theta = true;
-        if (which == SCHPF_BETA) dirty_beta = true;
+        if (is_loading(which)) side[axis_of(which)].dirty = true;
         // the graph reads the parameters through fixed pointers: still valid; only xi/eta shapes are constants
     }
     void get_state(int which, void *shape, void *rate) override
     {
         const size_t b = state_bytes(which);
-        if (shape) HIPCHK(hipMemcpyAsync(shape, shape_buf(which).p, b, hipMemcpyDeviceToHost, stream));
-        if (rate) HIPCHK(hipMemcpyAsync(rate, rate_buf(which).p, b, hipMemcpyDeviceToHost, stream));
+        if (shape) HIPCHK(hipMemcpyAsync(shape, state_buf(which, false).p, b, hipMemcpyDeviceToHost, stream));
+        if (rate) HIPCHK(hipMemcpyAsync(rate, state_buf(which, true).p, b, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
     }
 
@@ -1092,38 +1091,52 @@ template <typename T> struct Engine final : schpf_ctx {
         return std::max(1, std::min(groups, (int)UPD_BLOCKS));
     }
 
-    // (re)build E, E[log], exp-shifted tables and column sums from the stored parameters
+    // what every launch of the update kernel on a side is given: its parameters, tables and column partials
+    schpf::UpdateArgs<T> update_args(int s)
+    {
+        Side &sd = side[s];
+        schpf::UpdateArgs<T> u{};
+        u.n = sd.n; u.K = K; u.KP = KP; u.rows_per_block = rows_per_block();
+        u.shape = sd.shape.as<T>(); u.rate = sd.rate.as<T>();
+        u.tab_e = sd.tab_e.as<T>(); u.tab_log = sd.tab_log.as<T>(); u.tab_exp = sd.tab_exp.as<T>();
+        u.colsum_part = sd.colpart.as<double>();
+        return u;
+    }
+    // `out` := a side's column sums, from the block partials its update kernel left.  Not symmetric: only theta's are
+    // mirrored, in the model dtype (the f32 flag), into the exchange buffer's tail, which a sharded fit all-reduces
+    void reduce_colsums(int s, DevBuf &out)
+    {
+        void *mirror = s == 0 ? exchange_buf.as<T>() + (size_t)G * K : nullptr;
+        HIPCHK(schpf::launch_colsum_reduce(side[s].colpart.as<double>(), upd_blocks(side[s].n), K, out.as<double>(), mirror,
+                                           s == 0 && sizeof(T) == 4, stream));
+    }
+
+    // (re)build E, E[log], exp-shifted tables and column sums from the stored parameters: theta, then beta
     void refresh_tables()
     {
-        if (dirty_theta) {
-            schpf::UpdateArgs<T> u{};
-            u.n = N; u.K = K; u.KP = KP; u.rows_per_block = rows_per_block();
-            u.shape = th_s.as<T>(); u.rate = th_r.as<T>();
-            u.tab_e = th_e.as<T>(); u.tab_log = th_log.as<T>(); u.tab_exp = th_exp.as<T>();
-            u.colsum_part = colpart_cell.as<double>();
-            const int nb = upd_blocks(N);
-            HIPCHK(schpf::launch_gamma_update(u, schpf::SRC_NONE, nb, stream));
-            HIPCHK(schpf::launch_colsum_reduce(colpart_cell.as<double>(), nb, K, s_theta.as<double>(),
-                                               exchange_buf.as<T>() + (size_t)G * K, sizeof(T) == 4, stream));
-            dirty_theta = false;
-        }
-        if (dirty_beta) {
-            schpf::UpdateArgs<T> u{};
-            u.n = G; u.K = K; u.KP = KP; u.rows_per_block = rows_per_block();
-            u.shape = be_s.as<T>(); u.rate = be_r.as<T>();
-            u.tab_e = be_e.as<T>(); u.tab_log = be_log.as<T>(); u.tab_exp = be_exp.as<T>();
-            u.colsum_part = colpart_gene.as<double>();
-            const int nb = upd_blocks(G);
-            HIPCHK(schpf::launch_gamma_update(u, schpf::SRC_NONE, nb, stream));
-            HIPCHK(schpf::launch_colsum_reduce(colpart_gene.as<double>(), nb, K, s_beta.as<double>(), nullptr, 0,
-                                               stream));
-            dirty_beta = false;
+        for (int s = 0; s < 2; ++s) {
+            if (!side[s].dirty) continue;
+            HIPCHK(schpf::launch_gamma_update(update_args(s), schpf::SRC_NONE, upd_blocks(side[s].n), stream));
+            reduce_colsums(s, s == 0 ? s_theta : s_beta);   // s_beta: the current one of the double buffer
+            side[s].dirty = false;
         }
     }
 
-    schpf::SweepArgs<T> sweep_args(PlanDev &pd, const DevBuf &tab_major, const DevBuf &tab_minor,
-                                   const DevBuf &log_major, const DevBuf &log_minor)
+    // The tables a sweep of side s reads: major = the side's own, minor = the other side's.  MODE_LLH reads the E
+    // tables, every other mode the exp-shifted ones; the log tables are the same for all
+    template <typename A> void table_args(A &a, int s, int mode)
     {
+        const Side &mj = side[s], &mn = side[1 - s];
+        const bool llh = mode == schpf::MODE_LLH;
+        a.tab_major = (llh ? mj.tab_e : mj.tab_exp).template as<T>();
+        a.tab_minor = (llh ? mn.tab_e : mn.tab_exp).template as<T>();
+        a.log_major = mj.tab_log.template as<T>();
+        a.log_minor = mn.tab_log.template as<T>();
+    }
+
+    schpf::SweepArgs<T> sweep_args(int s, int mode)
+    {
+        PlanDev &pd = side[s].plan;
         schpf::SweepArgs<T> a{};
         a.entries = pd.entries.as<uint4>();
         a.slice_off = pd.slice_off.as<int64_t>();
@@ -1131,19 +1144,16 @@ template <typename T> struct Engine final : schpf_ctx {
         a.chunk_major = pd.chunk_major.as<int>();
         a.chunk_natid = pd.chunk_natid.as<int>();
         a.wave_slice = pd.wave_slice.as<int>();
-        a.tab_major = tab_major.as<T>();
-        a.tab_minor = tab_minor.as<T>();
-        a.log_major = log_major.as<T>();
-        a.log_minor = log_minor.as<T>();
+        table_args(a, s, mode);
         a.partials = pd.partials.as<T>();
         a.wave_out = wave_out.as<double>();
         a.K = K;
         return a;
     }
 
-    schpf::TileArgs<T> tile_args(TileDev &td, const DevBuf &tab_major, const DevBuf &tab_minor,
-                                 const DevBuf &log_major, const DevBuf &log_minor, int n_minor)
+    schpf::TileArgs<T> tile_args(int s, int mode)
     {
+        TileDev &td = side[s].tile;
         schpf::TileArgs<T> a{};
         a.entries = td.entries.p;
         a.steps = td.steps.as<uint16_t>();
@@ -1153,34 +1163,27 @@ template <typename T> struct Engine final : schpf_ctx {
         a.task_w1 = td.task_w1.as<int>();
         a.task_wave_off = td.task_wave_off.as<int64_t>();
         a.task_order = nullptr;   // natural order (plan.cpp)
-        a.tab_major = tab_major.as<T>();
-        a.tab_minor = tab_minor.as<T>();
-        a.log_major = log_major.as<T>();
-        a.log_minor = log_minor.as<T>();
+        table_args(a, s, mode);
         a.partials = td.partials.as<T>();
         a.wave_out = wave_out.as<double>();
-        a.K = K; a.n_minor = td.n_virtual ? td.n_virtual : n_minor; a.n_windows = td.host.n_windows; a.win_rows = td.host.win_rows;
+        a.K = K; a.n_minor = td.n_virtual ? td.n_virtual : side[1 - s].n; a.n_windows = td.host.n_windows; a.win_rows = td.host.win_rows;
         a.minor_of = td.n_virtual ? td.minor_of.as<int>() : nullptr;
         a.n_virtual = td.n_virtual;
         a.wpb = td.host.wpb;
         a.ring = td.host.ring; a.slot_bytes = td.host.slot16 * 16; a.sync_stage = td.host.sync_stage;
         a.single = td.host.single ? 1 : 0;
         a.clock_probe = clock_probe.as<unsigned long long>();
+        a.major_is_cell = s == 0 ? 1 : 0;
         return a;
     }
 
     // one sweep of either plan kind.  side 0: major = cell, side 1: major = gene.
-    void run_sweep(int side, int mode, uint64_t seed = 0)
+    void run_sweep(int s, int mode, uint64_t seed = 0)
     {
-        const bool cellside = side == 0;
-        const DevBuf &tmaj = mode == schpf::MODE_LLH ? (cellside ? th_e : be_e) : (cellside ? th_exp : be_exp);
-        const DevBuf &tmin = mode == schpf::MODE_LLH ? (cellside ? be_e : th_e) : (cellside ? be_exp : th_exp);
-        const DevBuf &lmaj = cellside ? th_log : be_log;
-        const DevBuf &lmin = cellside ? be_log : th_log;
         if (use_tile) {
-            TileDev &td = cellside ? tcell : tgene;
-            auto a = tile_args(td, tmaj, tmin, lmaj, lmin, cellside ? G : N);
-            a.seed = seed; a.major_is_cell = cellside ? 1 : 0;
+            TileDev &td = side[s].tile;
+            auto a = tile_args(s, mode);
+            a.seed = seed;
             int64_t n_tasks = td.n_tasks;
             const bool logs = mode == schpf::MODE_LLH || mode == schpf::MODE_ELBO;   // the ELBO pass is cut as the loss pass
             const bool cut = logs && td.n_llh_tasks > 0;   // the loss pass's finer tasks (loss_tasks)
@@ -1200,25 +1203,25 @@ template <typename T> struct Engine final : schpf_ctx {
             if (mode == schpf::MODE_ELBO) a.clock_probe = nullptr;   // schpf_profile_clock: the sweeps and the loss pass
             HIPCHK(schpf::launch_tile_sweep<T>(a, NV, LPC, mode, td.packed ? 1 : 0, n_tasks, td.threads, lds, stream));
         } else {
-            PlanDev &pd = cellside ? cell : gene;
-            auto a = sweep_args(pd, tmaj, tmin, lmaj, lmin);
+            PlanDev &pd = side[s].plan;
+            auto a = sweep_args(s, mode);
             if (mode == schpf::MODE_RANDOM)
-                HIPCHK(schpf::launch_random_phi<T>(a, NV, LPC, seed, cellside ? 1 : 0, pd.n_waves, stream));
+                HIPCHK(schpf::launch_random_phi<T>(a, NV, LPC, seed, s == 0 ? 1 : 0, pd.n_waves, stream));
             else
                 HIPCHK(schpf::launch_sweep<T>(a, NV, LPC, mode, pd.n_waves, stream));
         }
     }
 
     // where the update kernel finds a side's accumulated chunk/task partials
-    void partial_source(int side, schpf::UpdateArgs<T> &u, int &src)
+    void partial_source(int s, schpf::UpdateArgs<T> &u, int &src)
     {
         if (use_tile) {
-            TileDev &td = side == 0 ? tcell : tgene;
+            TileDev &td = side[s].tile;
             src = schpf::SRC_STRIDED;
             u.partials = td.partials.as<T>(); u.pfirst = td.pfirst.as<int>(); u.pcount = td.pcount.as<int>();
             u.pstride = td.host.pstride;
         } else {
-            PlanDev &pd = side == 0 ? cell : gene;
+            PlanDev &pd = side[s].plan;
             src = schpf::SRC_PARTIALS;
             u.partials = pd.partials.as<T>(); u.cptr = pd.cptr.as<int>();
         }
@@ -1228,12 +1231,22 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         if (!have_coo) throw std::logic_error("no count matrix uploaded (schpf_upload_coo)");
     }
+    void need_loss_constants() const
+    {
+        if (!have_loss_constants)
+            throw std::logic_error("this engine holds gathered batch rows (schpf_upload_rows): evaluate the loss on the source");
+    }
+    // run pointers of a side's (major, minor)-sorted order, on the host
+    const std::vector<int64_t> &major_ptr(int s) const { return use_tile ? side[s].tile.host.mptr : side[s].plan.host.mptr; }
+    // doubles a loss / ELBO pass over side s leaves in wave_out.  Not symmetric: gather plans only ever sweep the cell
+    // side for it (loss_side), so theirs is the cell plan's n_waves
+    int64_t n_wave_out(int s) const { return use_tile ? side[s].tile.n_wave_out : side[0].plan.n_waves; }
 
     // (major, minor)-sorted position -> position in the caller's COO, on the device
-    const int *order_of(int side, DevBuf &scratch)
+    const int *order_of(int s, DevBuf &scratch)
     {
-        if (!use_tile) { upload(scratch, side == 0 ? cell.host.order : gene.host.order, stream); return scratch.as<int>(); }
-        TileDev &td = side == 0 ? tcell : tgene;
+        if (!use_tile) { upload(scratch, side[s].plan.host.order, stream); return scratch.as<int>(); }
+        TileDev &td = side[s].tile;
         if (td.order_dev.p) return td.order_dev.as<int>();
         if (td.order_identity) {
             std::vector<int32_t> iota((size_t)nnz);
@@ -1253,16 +1266,15 @@ template <typename T> struct Engine final : schpf_ctx {
         dx.alloc((size_t)nnz * K * sizeof(double));
         HIPCHK(hipMemcpyAsync(dx.p, xphi, (size_t)nnz * K * sizeof(double), hipMemcpyHostToDevice, stream));
         dense_cell.alloc((size_t)N * K * sizeof(T));
-        const int *ord_c = order_of(0, ord);
-        upload(mp, use_tile ? tcell.host.mptr : cell.host.mptr, stream);
-        HIPCHK(schpf::launch_segment_sum<T>(dx.as<double>(), ord_c, mp.as<int64_t>(), N, K,
-                                            dense_cell.as<T>(), stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        const int *ord_g = order_of(1, ord);
-        upload(mp, use_tile ? tgene.host.mptr : gene.host.mptr, stream);
-        HIPCHK(schpf::launch_segment_sum<T>(dx.as<double>(), ord_g, mp.as<int64_t>(), G, K,
-                                            exchange_buf.as<T>(), stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        for (int s = 0; s < 2; ++s) {
+            const int *o = order_of(s, ord);
+            upload(mp, major_ptr(s), stream);
+            // Not symmetric: the cells' dense sums get a buffer of their own for this one iteration, the genes' go where
+            // a sharded fit's do, the exchange buffer (step_finish reads both as SRC_DENSE while pending_init == 1)
+            T *out = s == 0 ? dense_cell.as<T>() : exchange_buf.as<T>();
+            HIPCHK(schpf::launch_segment_sum<T>(dx.as<double>(), o, mp.as<int64_t>(), side[s].n, K, out, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
         pending_init = 1;
     }
 
@@ -1288,22 +1300,22 @@ template <typename T> struct Engine final : schpf_ctx {
         if (pending_init == 0 && use_tile && dual_slots > 0 && do_gene && do_cell && !freeze) {
             // both sweeps read the same old tables: one launch (timed as kind 0, see schpf_profile_read)
             ScopedTimer tm(prof, stream, 0);
-            auto ac = tile_args(tcell, th_exp, be_exp, th_log, be_log, G);
-            auto ag = tile_args(tgene, be_exp, th_exp, be_log, th_log, N);
-            ac.major_is_cell = 1; ag.major_is_cell = 0;
+            // Not symmetric: the kernel takes (cell args, gene args) in that order; dual_order names gene tasks as ~task
+            const TileDev &tc = side[0].tile, &tg = side[1].tile;
+            auto ac = tile_args(0, schpf::MODE_PHI), ag = tile_args(1, schpf::MODE_PHI);
             // persistent workgroups (SCHPF_PERSISTENT=0: one workgroup per slot): as many as the device holds at
             // once draw the slots of the longest-first list from a counter -- no workgroup teardown / launch
             // between the ~6 tasks of a compute unit and whoever is free takes the next task: C3 sweep
             // -2 % f64, -5 % f32, nothing at C2 / the C5 share (profiles/r02/explore_persistent.log)
-            const size_t lds = std::max(tcell.lds_bytes, tgene.lds_bytes);
+            const size_t lds = std::max(tc.lds_bytes, tg.lds_bytes);
             int *queue = nullptr;
             int resident = 0;
             if (tuning.persistent) {
                 queue = dual_queue.as<int>();
                 resident = cu_count * schpf::per_cu(lds);
             }
-            HIPCHK(schpf::launch_tile_sweep_dual<T>(ac, ag, dual_order.as<int>(), NV, LPC, tcell.packed ? 1 : 0,
-                                                    dual_slots, tcell.threads, lds, queue, resident, stream));
+            HIPCHK(schpf::launch_tile_sweep_dual<T>(ac, ag, dual_order.as<int>(), NV, LPC, tc.packed ? 1 : 0,
+                                                    dual_slots, tc.threads, lds, queue, resident, stream));
             tm.stop();
         } else if (pending_init == 0) {
             if (do_gene && !freeze) {
@@ -1318,13 +1330,14 @@ template <typename T> struct Engine final : schpf_ctx {
             }
         }
         if (sharded && !freeze && pending_init != 1 && do_gene) {
-            // fixed-order reduction of this rank's gene-side partials into the exchange buffer
+            // fixed-order reduction of this rank's gene-side partials into the exchange buffer (the cells stay on their rank)
+            const TileDev &tg = side[1].tile;
+            const PlanDev &pg = side[1].plan;
             if (use_tile)
-                HIPCHK(schpf::launch_combine_strided<T>(tgene.partials.as<T>(), tgene.pfirst.as<int>(),
-                                                        tgene.pcount.as<int>(), tgene.host.pstride, G, K, KP,
-                                                        exchange_buf.as<T>(), stream));
+                HIPCHK(schpf::launch_combine_strided<T>(tg.partials.as<T>(), tg.pfirst.as<int>(), tg.pcount.as<int>(),
+                                                        tg.host.pstride, G, K, KP, exchange_buf.as<T>(), stream));
             else
-                HIPCHK(schpf::launch_combine_partials<T>(gene.partials.as<T>(), gene.cptr.as<int>(), G, K, KP,
+                HIPCHK(schpf::launch_combine_partials<T>(pg.partials.as<T>(), pg.cptr.as<int>(), G, K, KP,
                                                          exchange_buf.as<T>(), stream));
         }
     }
@@ -1347,63 +1360,45 @@ template <typename T> struct Engine final : schpf_ctx {
         const bool fuse = !sharded && !freeze && !simultaneous && !cells_first && tuning.fuse_sums &&
                           (int64_t)upd_blocks(N) * K <= 16384 && (int64_t)upd_blocks(G) * K <= 16384;
         if (!fuse && sums_stale) {   // s_theta / s_beta from the partials the last fused iteration left
-            HIPCHK(schpf::launch_colsum_reduce(colpart_cell.as<double>(), upd_blocks(N), K, s_theta.as<double>(),
-                                               exchange_buf.as<T>() + (size_t)G * K, sizeof(T) == 4, stream));
-            HIPCHK(schpf::launch_colsum_reduce(colpart_gene.as<double>(), upd_blocks(G), K, s_beta.as<double>(), nullptr,
-                                               0, stream));
+            reduce_colsums(0, s_theta);
+            reduce_colsums(1, s_beta);
             sums_stale = false;
         }
-        // sharded: the all-reduced sum_i E[theta_ik] (old theta) is the tail of the exchange buffer; the
-        // gene update reads it from there (s_other_t)
-        auto gene_update = [&] {
-        if (!freeze) {  // gene block, scHPF_.py:697-704 (or :668-673 + :682-685)
-            schpf::UpdateArgs<T> u{};
-            u.n = G; u.K = K; u.KP = KP; u.rows_per_block = rows_per_block();
+        // One block of the iteration: the cell block is scHPF_.py:706-714 (or :675-680), the gene block :697-704 (or
+        // :668-673 + :682-685).  Where the two differ, `gene` says so.
+        auto update = [&](int s) {
+            const bool gene = s == 1;
+            if (gene && freeze) return;   // SCHPF_FREEZE_GENES: eta / beta stay as they are
+            Side &sd = side[s], &other = side[1 - s];
+            schpf::UpdateArgs<T> u = update_args(s);
             int src;
-            if (sharded || pending_init == 1) { src = schpf::SRC_DENSE; u.dense = exchange_buf.as<T>(); }
-            else partial_source(1, u, src);
-            u.prior_shape = c;
-            u.cap_shape = eta_s.as<T>(); u.cap_rate = eta_r.as<T>();
-            u.s_other = s_theta.as<double>();
-            if (sharded) u.s_other_t = exchange_buf.as<T>() + (size_t)G * K;
-            if (fuse) { u.s_other_part = colpart_cell.as<double>(); u.s_other_nb = upd_blocks(N); }
-            u.cap_prior_rate = dp;
-            u.shape = be_s.as<T>(); u.rate = be_r.as<T>(); u.cap_rate_out = eta_r.as<T>();
-            u.tab_e = be_e.as<T>(); u.tab_log = be_log.as<T>(); u.tab_exp = be_exp.as<T>();
-            u.colsum_part = colpart_gene.as<double>();
-            const int nb = upd_blocks(G);
-            HIPCHK(schpf::launch_gamma_update(u, src, nb, stream));
-            if (!fuse)
-                HIPCHK(schpf::launch_colsum_reduce(colpart_gene.as<double>(), nb, K, s_beta_next.as<double>(), nullptr,
-                                                   0, stream));
-        }
+            // dense sums instead of plan partials: right after init_phi_host (the cells' in dense_cell, the genes' in the
+            // exchange buffer) and, gene side only, in every sharded iteration (the all-reduced exchange buffer)
+            if (pending_init == 1 || (gene && sharded)) {
+                src = schpf::SRC_DENSE;
+                u.dense = gene ? exchange_buf.as<T>() : dense_cell.as<T>();
+            } else partial_source(s, u, src);
+            u.prior_shape = prior_shape(s);
+            u.cap_shape = sd.cap_shape.as<T>(); u.cap_rate = sd.cap_rate.as<T>();
+            if (gene) {
+                u.s_other = s_theta.as<double>();
+                // sharded: the all-reduced sum_i E[theta_ik] (old theta) is the tail of the exchange buffer; the
+                // gene update reads it from there (s_other_t)
+                if (sharded) u.s_other_t = exchange_buf.as<T>() + (size_t)G * K;
+            } else {
+                // theta.rate uses the beta just updated (scHPF_.py:711-713) unless the updates are
+                // simultaneous (:677-679) or the genes are frozen
+                u.s_other = (freeze || simultaneous || cells_first) ? s_beta.as<double>() : s_beta_next.as<double>();
+            }
+            if (fuse) { u.s_other_part = other.colpart.as<double>(); u.s_other_nb = upd_blocks(other.n); }
+            u.cap_prior_rate = cap_prior_rate(s);
+            u.cap_rate_out = sd.cap_rate.as<T>();
+            HIPCHK(schpf::launch_gamma_update(u, src, upd_blocks(sd.n), stream));
+            // the new beta's sums go to the other half of the double buffer: the cell update may still need the old ones
+            if (!fuse) reduce_colsums(s, gene ? s_beta_next : s_theta);
         };
-        auto cell_update = [&] {
-        {  // cell block, scHPF_.py:706-714 (or :675-680)
-            schpf::UpdateArgs<T> u{};
-            u.n = N; u.K = K; u.KP = KP; u.rows_per_block = rows_per_block();
-            int src;
-            if (pending_init == 1) { src = schpf::SRC_DENSE; u.dense = dense_cell.as<T>(); }
-            else partial_source(0, u, src);
-            u.prior_shape = a;
-            u.cap_shape = xi_s.as<T>(); u.cap_rate = xi_r.as<T>();
-            // theta.rate uses the beta just updated (scHPF_.py:711-713) unless the updates are
-            // simultaneous (:677-679) or the genes are frozen
-            u.s_other = (freeze || simultaneous || cells_first) ? s_beta.as<double>() : s_beta_next.as<double>();
-            if (fuse) { u.s_other_part = colpart_gene.as<double>(); u.s_other_nb = upd_blocks(G); }
-            u.cap_prior_rate = bp;
-            u.shape = th_s.as<T>(); u.rate = th_r.as<T>(); u.cap_rate_out = xi_r.as<T>();
-            u.tab_e = th_e.as<T>(); u.tab_log = th_log.as<T>(); u.tab_exp = th_exp.as<T>();
-            u.colsum_part = colpart_cell.as<double>();
-            const int nb = upd_blocks(N);
-            HIPCHK(schpf::launch_gamma_update(u, src, nb, stream));
-            if (!fuse)
-                HIPCHK(schpf::launch_colsum_reduce(colpart_cell.as<double>(), nb, K, s_theta.as<double>(),
-                                                   exchange_buf.as<T>() + (size_t)G * K, sizeof(T) == 4, stream));
-        }
-        };
-        if (cells_first) { cell_update(); gene_update(); }   // minibatch order: theta first, beta from the NEW theta
-        else { gene_update(); cell_update(); }
+        if (cells_first) { update(0); update(1); }   // minibatch order: theta first, beta from the NEW theta
+        else { update(1); update(0); }
         if (!freeze) { std::swap(s_beta.p, s_beta_next.p); beta_parity ^= 1; }
         if (fuse) sums_stale = true;
         if (pending_init == 1) dense_cell.release();
@@ -1415,22 +1410,19 @@ template <typename T> struct Engine final : schpf_ctx {
     void loss_terms(double *llh, double *gl, int64_t *nnz_out) override
     {
         need_coo();
-        if (!have_loss_constants)
-            throw std::logic_error("this engine holds gathered batch rows (schpf_upload_rows): evaluate the loss on the source");
+        need_loss_constants();
         refresh_tables();
         ScopedTimer tm(prof, stream, 2);
-        const int side = loss_side();
-        run_sweep(side, schpf::MODE_LLH);
+        const int ls = loss_side();
+        run_sweep(ls, schpf::MODE_LLH);
         double *res = loss_host ? loss_host : scalars.as<double>();   // pinned host memory is device-addressable as it is
-        HIPCHK(schpf::launch_sum_doubles(wave_out.as<double>(),
-                                         use_tile ? (side ? tgene.n_wave_out : tcell.n_wave_out) : cell.n_waves,
-                                         res, stream));
+        HIPCHK(schpf::launch_sum_doubles(wave_out.as<double>(), n_wave_out(ls), res, stream));
         // explicitly stored zeros look like padding to the sweeps (weight 0, which is what they
         // contribute to the shape updates, hpf_numba.py:97-112), but the reference's loss counts
         // them: x log r - r - lgamma(x+1) = -r (hpf_numba.py:43-50)
         if (n_zero > 0)
-            HIPCHK(schpf::launch_zero_rate_sum<T>(zero_row.as<int>(), zero_col.as<int>(), n_zero, th_e.as<T>(),
-                                                  be_e.as<T>(), K, KP, res + 2, stream));
+            HIPCHK(schpf::launch_zero_rate_sum<T>(zero_row.as<int>(), zero_col.as<int>(), n_zero, side[0].tab_e.as<T>(),
+                                                  side[1].tab_e.as<T>(), K, KP, res + 2, stream));
         tm.stop();
         double h[3] = {0.0, 0.0, 0.0};
         if (!loss_host) HIPCHK(hipMemcpyAsync(h, scalars.p, 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1449,28 +1441,25 @@ template <typename T> struct Engine final : schpf_ctx {
     void elbo_terms(double ap, double cp, double terms[5]) override
     {
         need_coo();
-        if (!have_loss_constants)
-            throw std::logic_error("this engine holds gathered batch rows (schpf_upload_rows): evaluate the loss on the source");
+        need_loss_constants();
         if (!(ap > 0 && cp > 0)) throw std::invalid_argument("ap and cp must be positive");
         refresh_tables();
-        const int side = loss_side();
-        run_sweep(side, schpf::MODE_ELBO);
-        const int nbc = upd_blocks(N), nbg = upd_blocks(G), W = K + 2;
-        if (elbo_part.bytes < (size_t)std::max(nbc, nbg) * W * sizeof(double))
-            elbo_part.alloc((size_t)std::max(nbc, nbg) * W * sizeof(double));
+        const int ls = loss_side();
+        run_sweep(ls, schpf::MODE_ELBO);
+        const int nb[2] = {upd_blocks(N), upd_blocks(G)}, W = K + 2;
+        if (elbo_part.bytes < (size_t)std::max(nb[0], nb[1]) * W * sizeof(double))
+            elbo_part.alloc((size_t)std::max(nb[0], nb[1]) * W * sizeof(double));
         if (!elbo_sums.p) elbo_sums.alloc((size_t)(2 * W + 1) * sizeof(double));
-        double *sums = elbo_sums.as<double>();
-        HIPCHK(schpf::launch_sum_doubles(wave_out.as<double>(),
-                                         use_tile ? (side ? tgene.n_wave_out : tcell.n_wave_out) : cell.n_waves,
-                                         sums + 2 * W, stream));
-        HIPCHK(schpf::launch_elbo_gamma<T>(th_s.as<T>(), th_r.as<T>(), xi_s.as<T>(), xi_r.as<T>(), th_log.as<T>(),
-                                           count_row.as<double>(), N, K, KP, a, ap, bp, elbo_part.as<double>(), nbc,
-                                           stream));
-        HIPCHK(schpf::launch_colsum_reduce(elbo_part.as<double>(), nbc, W, sums, nullptr, 0, stream));
-        HIPCHK(schpf::launch_elbo_gamma<T>(be_s.as<T>(), be_r.as<T>(), eta_s.as<T>(), eta_r.as<T>(), be_log.as<T>(),
-                                           count_col.as<double>(), G, K, KP, c, cp, dp, elbo_part.as<double>(), nbg,
-                                           stream));
-        HIPCHK(schpf::launch_colsum_reduce(elbo_part.as<double>(), nbg, W, sums + W, nullptr, 0, stream));
+        double *sums = elbo_sums.as<double>();   // [W of the cell side | W of the gene side | sweep sum]
+        HIPCHK(schpf::launch_sum_doubles(wave_out.as<double>(), n_wave_out(ls), sums + 2 * W, stream));
+        const double cap_prior_shape[2] = {ap, cp};
+        for (int s = 0; s < 2; ++s) {   // cells, then genes: both through the one elbo_part scratch
+            const Side &sd = side[s];
+            HIPCHK(schpf::launch_elbo_gamma<T>(sd.shape.as<T>(), sd.rate.as<T>(), sd.cap_shape.as<T>(), sd.cap_rate.as<T>(),
+                                               sd.tab_log.as<T>(), sd.count.as<double>(), sd.n, K, KP, prior_shape(s),
+                                               cap_prior_shape[s], cap_prior_rate(s), elbo_part.as<double>(), nb[s], stream));
+            HIPCHK(schpf::launch_colsum_reduce(elbo_part.as<double>(), nb[s], W, sums + s * W, nullptr, 0, stream));
+        }
         std::vector<double> h((size_t)(2 * W + 1));
         HIPCHK(hipMemcpyAsync(h.data(), sums, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
@@ -1487,16 +1476,18 @@ template <typename T> struct Engine final : schpf_ctx {
     int loss_side() const
     {
         if (!use_tile) return 0;
-        const double model[2] = {tcell.llh_model, tgene.llh_model};
-        const int64_t tasks[2] = {tcell.n_tasks, tgene.n_tasks};
-        return schpf::loss_side(problem(), tuning, wave_out.bytes >= (size_t)tgene.n_wave_out * sizeof(double), model, tasks,
-                                tcell.lds_bytes);
+        const TileDev &tc = side[0].tile, &tg = side[1].tile;
+        const double model[2] = {tc.llh_model, tg.llh_model};
+        const int64_t tasks[2] = {tc.n_tasks, tg.n_tasks};
+        // the policy's question about wave_out is whether the gene plan's pass fits; the LDS figure is the cell plan's
+        return schpf::loss_side(problem(), tuning, wave_out.bytes >= (size_t)tg.n_wave_out * sizeof(double), model, tasks,
+                                tc.lds_bytes);
     }
 
     void upload_info(int64_t info[4]) override
     {
         info[0] = nnz; info[1] = n_rounded; info[2] = n_zero;
-        info[3] = (use_tile ? (tcell.packed ? 1 : 0) : 0) | (rows_ptr.p ? 2 : 0);   // bit 1: a row-sorted copy is kept
+        info[3] = (use_tile ? (side[0].tile.packed ? 1 : 0) : 0) | (rows_ptr.p ? 2 : 0);   // bit 1: a row-sorted copy is kept
     }
 
     // Shader clock the chip sustained under the sweep launches since the last read (tile plans; 0 launches: unknown).
@@ -1518,10 +1509,11 @@ template <typename T> struct Engine final : schpf_ctx {
     // LDS bytes the tasks of a tile plan stage: every (sub-)window of a task's range exactly once -- the half-window
     // schedule fills all slots at the first epoch and afterwards only the slot the last epoch owned, never beyond the
     // task's last window (sweep_impl.h, the window loop)
-    int64_t staged_bytes(const TileDev &td, int n_minor) const
+    int64_t staged_bytes(int s) const
     {
+        const TileDev &td = side[s].tile;
         const schpf::TilePlanHost &P = td.host;
-        const int nm = td.n_virtual ? td.n_virtual : n_minor;
+        const int nm = td.n_virtual ? td.n_virtual : side[1 - s].n;
         int64_t rows = 0;
         for (size_t t = 0; t < P.task_w0.size(); ++t)
             for (int w = P.task_w0[t]; w < P.task_w1[t]; ++w) rows += std::max(0, std::min(P.win_rows, nm - w * P.win_rows));
@@ -1538,34 +1530,34 @@ template <typename T> struct Engine final : schpf_ctx {
         if (!use_tile || !have_coo) return;
         const int64_t row = (int64_t)KP * (int64_t)sizeof(T);
         info[0] = 2 * nnz * row;
-        info[1] = (tcell.entry_slots + tgene.entry_slots) * row;
-        info[2] = staged_bytes(tcell, G);
-        info[3] = staged_bytes(tgene, N);
-        info[4] = (tcell.entry_slots + tgene.entry_slots) * (tcell.packed ? 4 : 8);
-        info[5] = (tcell.host.n_partial_rows + tgene.host.n_partial_rows) * row;
+        const TileDev &tc = side[0].tile, &tg = side[1].tile;
+        info[1] = (tc.entry_slots + tg.entry_slots) * row;
+        info[2] = staged_bytes(0);
+        info[3] = staged_bytes(1);
+        info[4] = (tc.entry_slots + tg.entry_slots) * (tc.packed ? 4 : 8);
+        info[5] = (tc.host.n_partial_rows + tg.host.n_partial_rows) * row;
         // what the loss pass will sweep (loss_side, loss_tasks): so that a report can say which plan and cut the model chose
-        const int side = loss_side();
-        info[6] = side;
-        info[7] = (side ? tgene : tcell).n_llh_tasks > 0 ? (side ? tgene : tcell).n_llh_tasks : (side ? tgene : tcell).n_tasks;
+        const int ls = loss_side();
+        const TileDev &tl = side[ls].tile;
+        info[6] = ls;
+        info[7] = tl.n_llh_tasks > 0 ? tl.n_llh_tasks : tl.n_tasks;
     }
 
+    // per-side entries come in (cell, gene) pairs; [3], [14], [15] describe the cell plan
     void plan_info(int64_t info[16]) override
     {
         info[0] = KP; info[1] = KL; info[2] = LPC;
-        info[12] = use_tile ? tcell.host.ring : 0; info[13] = use_tile ? tgene.host.ring : 0;
-        info[14] = use_tile ? tcell.host.slot16 * 16 : 0; info[15] = use_tile ? tcell.host.wpb : 0;
-        if (use_tile) {
-            info[3] = -tcell.host.win_rows;            // negative: tile plan, rows per LDS window
-            info[4] = tcell.host.n_windows; info[5] = tgene.host.n_windows;
-            info[6] = tcell.host.n_partial_rows; info[7] = tgene.host.n_partial_rows;
-            info[8] = tcell.n_tasks; info[9] = tgene.n_tasks;
-            info[10] = tcell.entry_slots; info[11] = tgene.entry_slots;
-        } else {
-            info[3] = cell.host.chunk_len;
-            info[4] = cell.host.n_windows; info[5] = gene.host.n_windows;
-            info[6] = cell.n_chunks; info[7] = gene.n_chunks;
-            info[8] = cell.n_waves; info[9] = gene.n_waves;
-            info[10] = cell.entry_slots; info[11] = gene.entry_slots;
+        const TileDev &tc = side[0].tile;
+        info[3] = use_tile ? -tc.host.win_rows : side[0].plan.host.chunk_len;   // negative: tile plan, rows per LDS window
+        info[14] = use_tile ? tc.host.slot16 * 16 : 0; info[15] = use_tile ? tc.host.wpb : 0;
+        for (int s = 0; s < 2; ++s) {
+            const TileDev &td = side[s].tile;
+            const PlanDev &pd = side[s].plan;
+            info[4 + s] = use_tile ? td.host.n_windows : pd.host.n_windows;
+            info[6 + s] = use_tile ? td.host.n_partial_rows : pd.n_chunks;
+            info[8 + s] = use_tile ? td.n_tasks : pd.n_waves;
+            info[10 + s] = use_tile ? td.entry_slots : pd.entry_slots;
+            info[12 + s] = use_tile ? td.host.ring : 0;
         }
     }
 };
