@@ -1,118 +1,22 @@
 // C ABI of libschpf_hip.so (include/schpf_hip.h): context management, uploads, and the
 // ordering of kernel launches that makes one CAVI iteration (scHPF_.py:657-714).
-#include <hip/hip_runtime.h>
-
-#include <dlfcn.h>
-
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <stdexcept>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/schpf_hip.h"
+#include "common.h"
 #include "kernels.h"
-#include "plan.h"
 #include "policy.h"
+#include "rccl.h"
+
+using namespace schpf;
+
+thread_local std::string schpf::g_err;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char *fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
-
-struct HipError : std::runtime_error {
-    hipError_t code;
-    HipError(const std::string &what, hipError_t code_ = hipErrorUnknown) : std::runtime_error(what), code(code_) {}
-};
-
-#define HIPCHK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            char b_[512];                                                                    \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                     __FILE__, __LINE__);                                                    \
-            throw HipError(b_, e_);                                                          \
-        }                                                                                    \
-    } while (0)
-
-template <typename F> int guarded(F &&f)
-{
-    // status SCHPF_ERR_NO_MEMORY: the device (hipErrorOutOfMemory) or the host (std::bad_alloc while building plans) ran
-    // out of memory -- the one failure a caller may answer with a smaller layout; everything else is 1
-    try {
-        f();
-        return 0;
-    } catch (const HipError &e) {
-        g_err = e.what();
-        if (e.code == hipErrorOutOfMemory) (void)hipGetLastError();
-        return e.code == hipErrorOutOfMemory ? SCHPF_ERR_NO_MEMORY : 1;
-    } catch (const schpf::DeviceNoMemory &e) {
-        g_err = e.what();
-        return SCHPF_ERR_NO_MEMORY;
-    } catch (const std::bad_alloc &) {
-        g_err = "out of host memory (std::bad_alloc)";
-        return SCHPF_ERR_NO_MEMORY;
-    } catch (const std::exception &e) {
-        g_err = e.what();
-        return 1;
-    } catch (...) {
-        g_err = "unknown error";
-        return 1;
-    }
-}
-
-// RAII device buffer
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept
-    {
-        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    void alloc(size_t n, bool zero = false, hipStream_t st = nullptr)
-    {
-        release();
-        bytes = n ? n : 16;
-        HIPCHK(hipMalloc(&p, bytes));
-        if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, st));
-    }
-    template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
-};
-
-template <typename U, typename A> void upload(DevBuf &b, const std::vector<U, A> &v, hipStream_t st)
-{
-    b.alloc(v.size() * sizeof(U));
-    if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, st));
-}
 
 struct PlanDev {
     schpf::SweepPlanHost host;  // entries cleared after upload; order/mptr/cptr kept
@@ -120,20 +24,26 @@ struct PlanDev {
     int64_t n_waves = 0, n_chunks = 0, entry_slots = 0;
 };
 
+// The tasks a tile sweep launches, one entry per task.  stage_end: only sub-range tasks have one (kernels.h task_stage_end)
+struct TaskList {
+    DevBuf block, w0, w1, stage_end, wave_off;
+    DevBuf order;               // tasks by decreasing work: the slot list of a persistent single-side launch
+    int64_t n = 0;
+};
+
 struct TileDev {
     schpf::TilePlanHost host;   // entries/steps cleared after upload; order/mptr kept
-    DevBuf entries, steps, block_rows, task_block, task_w0, task_w1, task_wave_off, pfirst, pcount, partials;
-    DevBuf task_order;          // tasks by decreasing work: the slot list of a persistent single-side launch
+    DevBuf entries, steps, block_rows, pfirst, pcount, partials;
+    TaskList tasks;             // the iteration's
     // The loss pass (MODE_LLH) writes no partial rows, so its tasks may be cut finer than the iteration's: sub-ranges of
-    // the tasks' window ranges, enough of them for a few rounds of the device (Engine::loss_tasks)
-    DevBuf llh_block, llh_w0, llh_w1, llh_stage_end, llh_wave_off, llh_order;
-    int64_t n_llh_tasks = 0;
+    // the tasks' window ranges, enough of them for a few rounds of the device (Engine::loss_tasks); n = 0: not cut
+    TaskList llh;
     double llh_model = 0.0;     // modelled length of the loss pass on this plan, in step units (0: unknown)
     DevBuf minor_of;            // balanced windows (plan.h): [n_blocks * n_virtual] table row staged at a window position, or empty
     int n_virtual = 0;
     DevBuf order_dev;           // device-built plans: (major, minor)-sorted position -> caller's COO position
     bool order_identity = false; //                    ... or the input was already in that order
-    int64_t n_tasks = 0, entry_slots = 0, n_wave_out = 0;
+    int64_t entry_slots = 0, n_wave_out = 0;
     int threads = 512;
     size_t lds_bytes = 0;
     bool packed = false;
@@ -154,6 +64,19 @@ struct Side {
     bool dirty = true;                 // the tables and column sums are older than the parameters
     Side() = default;
     Side(const Side &) = delete; Side &operator=(const Side &) = delete;
+};
+
+// What one upload knows about itself.  Made by upload_coo / upload_rows, handed down the stages by reference, gone with
+// the call: nothing of it is parked in the engine.
+struct UploadJob {
+    int64_t nnz = 0;
+    bool balance = false;              // balanced windows for this matrix (policy.cpp balance_windows)
+    bool batch_rows = false;           // gathered batch rows (upload_rows): no loss constants, no loss tasks
+    bool packed_ok = true;             // every count fits the packed 16-bit entry format
+    bool sorted[2] = {true, true};     // the COO is already in (row, col) / (col, row) order
+    int ranges[2] = {0, 0}, half[2] = {-1, -1};   // task ranges per orientation (policy.cpp choose_ranges)
+    schpf::TileShape shape[2];
+    bool balanced[2] = {false, false}; // this orientation's plan is built on balanced windows
 };
 
 struct Profiler {
@@ -187,54 +110,6 @@ struct ScopedTimer {
     }
 };
 
-// ---- RCCL, bound at run time.  The library has no DT_NEEDED on RCCL for the reason it has none on
-// the HIP runtime (Makefile): a process must use ONE copy, and PyTorch bundles its own.  The copy
-// already in the process is taken when there is one (RTLD_NOLOAD), else $SCHPF_RCCL_PATH, else
-// the system's.  Only the handful of entry points the sharded iteration needs; the types are the
-// C ABI of rccl.h (ncclUniqueId = 128 opaque bytes, ncclFloat32 = 7, ncclFloat64 = 8, ncclSum = 0).
-struct RcclUniqueId { char internal[128]; };
-struct Rccl {
-    void *handle = nullptr;
-    int (*GetUniqueId)(RcclUniqueId *) = nullptr;
-    int (*CommInitRank)(void **, int, RcclUniqueId, int) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    int (*AllReduce)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(int) = nullptr;
-};
-Rccl load_rccl()
-{
-    Rccl r;
-    const char *env = getenv("SCHPF_RCCL_PATH");
-    const char *names[] = {"librccl.so", "librccl.so.1", env && *env ? env : nullptr, "librccl.so", "librccl.so.1",
-                           "/opt/rocm/lib/librccl.so"};
-    for (int i = 0; i < 6 && !r.handle; ++i) {
-        if (!names[i]) continue;
-        r.handle = dlopen(names[i], RTLD_NOW | RTLD_GLOBAL | (i < 2 ? RTLD_NOLOAD : 0));
-    }
-    if (!r.handle) throw std::runtime_error("cannot load RCCL (librccl.so): set SCHPF_RCCL_PATH");
-    auto sym = [&](const char *n) {
-        void *p = dlsym(r.handle, n);
-        if (!p) throw std::runtime_error(std::string("RCCL lacks ") + n);
-        return p;
-    };
-    r.GetUniqueId = reinterpret_cast<decltype(r.GetUniqueId)>(sym("ncclGetUniqueId"));
-    r.CommInitRank = reinterpret_cast<decltype(r.CommInitRank)>(sym("ncclCommInitRank"));
-    r.CommDestroy = reinterpret_cast<decltype(r.CommDestroy)>(sym("ncclCommDestroy"));
-    r.AllReduce = reinterpret_cast<decltype(r.AllReduce)>(sym("ncclAllReduce"));
-    r.GetErrorString = reinterpret_cast<decltype(r.GetErrorString)>(sym("ncclGetErrorString"));
-    return r;
-}
-Rccl &rccl()
-{
-    static Rccl r = load_rccl();   // thread-safe; a failed load throws and is tried again by the next caller
-    return r;
-}
-#define RCCLCHK(expr)                                                                                     \
-    do {                                                                                                  \
-        const int r_ = (expr);                                                                            \
-        if (r_ != 0) throw std::runtime_error(std::string(#expr " failed: ") + rccl().GetErrorString(r_)); \
-    } while (0)
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------
@@ -252,10 +127,6 @@ struct schpf_ctx {
     virtual void step_local(unsigned flags) = 0;
     virtual void step_finish(unsigned flags) = 0;
     virtual void steps(unsigned flags, int n) = 0;
-    virtual void hypers_changed() = 0;
-    virtual void hint_sharded(int on) = 0;
-    virtual void hint_transient(int on) = 0;
-    virtual void keep_rows(int on) = 0;
     virtual void upload_rows(schpf_ctx *source, const int32_t *rows, int n_rows) = 0;
     virtual void steps_sharded(unsigned flags, int n) = 0;
     virtual void loss_terms_all(double *llh, double *gl, int64_t *nnz) = 0;
@@ -290,8 +161,27 @@ struct schpf_ctx {
     virtual void upload_info(int64_t info[4]) = 0;
     virtual void profile_clock(double *shader_mhz, int64_t *launches) = 0;
     virtual void sweep_bytes(int64_t info[8]) = 0;
-    double a = 0.3, c = 0.3, bp = 1.0, dp = 1.0;
+    double a = 0.3, c = 0.3, bp = 1.0, dp = 1.0;   // kernel arguments of the captured launches: set_hypers drops the graphs
+    bool expect_sharded = false;        // schpf_hint_sharded: a rank of a sharded fit (gene-side sums leave for an all-reduce)
+    bool transient = false;             // schpf_hint_transient: the matrix is replaced every iteration, plan the cheapest way
+    bool want_rows = false;             // schpf_keep_rows: keep a (row, col)-sorted device copy for upload_rows
     Profiler prof;
+    // n iterations captured as one hipGraph (schpf_steps): the state is device-resident and nothing on
+    // the host changes between two loss checks, so a fit replays one graph per check interval
+    // The sum-of-beta buffers swap roles every iteration (beta_parity counts the swaps mod 2) and a
+    // capture bakes the pointers in, so a graph is keyed by (flags, n, parity at its start): one cached
+    // graph per parity.  A stretch with an odd count (check_freq = 5: graph of 4 + one eager iteration)
+    // starts its calls at alternating parities and alternates between the two.
+    struct CachedGraph { hipGraphExec_t exec = nullptr; unsigned flags = 0; int n = 0; };
+    CachedGraph graphs[2];
+    // what a captured graph bakes in has changed: hypers, the matrix, the communicator
+    void drop_graphs()
+    {
+        for (CachedGraph &g : graphs) {
+            if (g.exec) { (void)hipStreamSynchronize(stream); (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+            g.n = 0;
+        }
+    }
 };
 
 namespace {
@@ -318,15 +208,7 @@ template <typename T> struct Engine final : schpf_ctx {
     DevBuf elbo_part, elbo_sums;                    // ELBO: Gamma-term block partials, their sums (elbo_terms)
     bool have_coo = false;
     int pending_init = 0;  // 0 none, 1 dense accumulators, 2 chunk partials
-    // n iterations captured as one hipGraph (schpf_steps): the state is device-resident and nothing on
-    // the host changes between two loss checks, so a fit replays one graph per check interval
-    // The sum-of-beta buffers swap roles every iteration (beta_parity counts the swaps mod 2) and a
-    // capture bakes the pointers in, so a graph is keyed by (flags, n, parity at its start): one cached
-    // graph per parity.  A stretch with an odd count (check_freq = 5: graph of 4 + one eager iteration)
-    // starts its calls at alternating parities and alternates between the two.
-    struct CachedGraph { hipGraphExec_t exec = nullptr; unsigned flags = 0; int n = 0; };
-    CachedGraph graphs[2];
-    int beta_parity = 0;
+    int beta_parity = 0;               // swaps of the sum-of-beta buffers mod 2: which cached graph fits (schpf_ctx::graphs)
     bool eager_since_upload = false;   // one eager iteration has run on this plan (kernel attributes are set)
     // small problems: the update kernels sum the other side's per-block column sums themselves and the
     // two reduce launches of an iteration are skipped; s_theta / s_beta are then brought up to date
@@ -335,19 +217,11 @@ template <typename T> struct Engine final : schpf_ctx {
     // Minibatch CAVI without re-uploads (scHPF_.py:643-650): an engine that was told to keep_rows() holds, beside
     // its plans, the matrix once more as a (row, col)-sorted device copy; a batch engine's upload_rows(source,
     // rows) gathers its rows from there and builds its plans from device arrays -- no host slicing, no PCIe.
-    bool want_rows = false, rows_packed_ok = true;
+    bool rows_packed_ok = true;
     DevBuf rows_ptr, rows_col, rows_val;            // int64[N + 1], int32[nnz], float[nnz]; host copy of rows_ptr: the cell tile plan's mptr
     bool have_loss_constants = true;                // false after upload_rows (no lgamma sum / stored-zero list for a batch)
-    // balanced windows (plan.h): on for uploads of a whole matrix; off for an engine that keeps a (row, col)-sorted copy
-    // (the plans' own order is then the virtual one) and for batch engines, which re-plan every iteration
-    bool balance_now = false;
-    bool transient = false;             // schpf_hint_transient: the matrix is replaced every iteration, plan the cheapest way
-    bool planning_batch_rows = false;   // inside schpf_upload_rows (gathered batch rows: no loss constants, no loss tasks)
-    bool expect_sharded = false;        // schpf_hint_sharded: a rank of a sharded fit (gene-side sums leave for an all-reduce)
     int cu_count = 256;
-    bool gammaln_on_device = false;     // the device plan builder has left sum lgamma(x + 1) in scalars[1] already
     DevBuf gammaln_part;
-    double count_seconds = 0.0;         // wall time of count_sums: part of the upload's, reported by SCHPF_VERBOSE=1
     static constexpr int UPD_BLOCKS = 2048;
     static constexpr size_t TABLE_PAD = 256 * 1024;
 
@@ -417,7 +291,6 @@ template <typename T> struct Engine final : schpf_ctx {
             loss_host = nullptr;            // falls back to the copy out of `scalars`
         } else std::memset(loss_host, 0, 8 * sizeof(double));
     }
-    void hypers_changed() override { drop_graph(); }
     // the hyper-parameters stay where the C ABI sets them (schpf_ctx)
     double prior_shape(int s) const { return s == 0 ? a : c; }
     double cap_prior_rate(int s) const { return s == 0 ? bp : dp; }   // of the side's capacities (xi / eta)
@@ -431,7 +304,7 @@ template <typename T> struct Engine final : schpf_ctx {
     void forget_matrix()
     {
         have_coo = false;
-        drop_graph();
+        drop_graphs();
         HIPCHK(hipStreamSynchronize(stream));
         for (Side &sd : side) { sd.plan = PlanDev(); sd.tile = TileDev(); sd.count.release(); }
         dual_order.release(); dual_slots = 0;
@@ -439,16 +312,6 @@ template <typename T> struct Engine final : schpf_ctx {
         zero_row.release(); zero_col.release();
         pending_init = 0;
         eager_since_upload = false;
-    }
-    void hint_sharded(int on) override { expect_sharded = on != 0; }
-    void hint_transient(int on) override { transient = on != 0; }
-    void keep_rows(int on) override { want_rows = on != 0; }   // a, c, bp, dp are kernel arguments of the captured launches
-    void drop_graph()
-    {
-        for (CachedGraph &g : graphs) {
-            if (g.exec) { (void)hipStreamSynchronize(stream); (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-            g.n = 0;
-        }
     }
     // the graph of `count` (even) iterations issued by `body` for the current parity: cached or captured now
     template <typename F> hipGraphExec_t graph_for(unsigned key_flags, int count, F &&body)
@@ -474,6 +337,19 @@ template <typename T> struct Engine final : schpf_ctx {
         return g.exec;
     }
 
+    // One stretch of n iterations issued by body(count).  A graphable stretch replays its even part as the graph cached
+    // under `key` for the current parity (captured on first use); what is left runs eagerly
+    template <typename F> void stretch(unsigned key, int n, bool graphable, F &&body)
+    {
+        int done = 0;
+        if (graphable && n >= 2) {
+            done = n & ~1;
+            HIPCHK(hipGraphLaunch(graph_for(key, done, body), stream));
+        }
+        body(n - done);
+        if (n > 0) eager_since_upload = true;
+    }
+
     // n iterations of schpf_step.  From the second call on with the same (flags, n) they are one
     // graph launch: launch overhead is what bounds small matrices (BASELINE C2: five launches of
     // 5-25 us each per iteration).  The sum-of-beta buffers swap roles every iteration, so a graph
@@ -481,18 +357,9 @@ template <typename T> struct Engine final : schpf_ctx {
     void steps(unsigned flags_, int n) override
     {
         if (n < 0) throw std::invalid_argument("n must be >= 0");
-        const bool graphable = tuning.graph && steady() && !(flags_ & SCHPF_SHARDED);
-        int done = 0;
-        if (graphable && n >= 2) {
-            const int even = n & ~1;
-            hipGraphExec_t exec = graph_for(flags_, even, [&](int count) {
-                for (int i = 0; i < count; ++i) { step_local(flags_); step_finish(flags_); }
-            });
-            HIPCHK(hipGraphLaunch(exec, stream));
-            done = even;
-        }
-        for (; done < n; ++done) { step_local(flags_); step_finish(flags_); }
-        if (n > 0) eager_since_upload = true;
+        stretch(flags_, n, tuning.graph && steady() && !(flags_ & SCHPF_SHARDED), [&](int count) {
+            for (int i = 0; i < count; ++i) { step_local(flags_); step_finish(flags_); }
+        });
     }
 
     // n iterations with the cells sharded over the ranks of `comm` (sharded.py protocol, driven from
@@ -523,16 +390,7 @@ template <typename T> struct Engine final : schpf_ctx {
         // supports stream capture): 0.183 -> 0.168 ms per iteration of a 1/8 shard of C3.  The default for a one-rank
         // communicator, which is all this build could ever run it with; with more ranks every rank must replay the same
         // graph, so there it stays opt-in (SCHPF_GRAPH_SHARDED=1) until tests/test_multigpu.py has seen two GPUs.
-        int done = 0;
-        const bool graphable = tuning.graph_sharded.value_or(comm_world == 1) && steady() && !freeze;
-        if (graphable && n >= 2) {
-            const int even = n & ~1;
-            hipGraphExec_t exec = graph_for(base | 0x80000000u, even, iterate);
-            HIPCHK(hipGraphLaunch(exec, stream));
-            done = even;
-        }
-        iterate(n - done);
-        if (n > 0) eager_since_upload = true;
+        stretch(base | 0x80000000u, n, tuning.graph_sharded.value_or(comm_world == 1) && steady() && !freeze, iterate);
     }
 
     // loss terms summed over the ranks (three doubles through the same communicator)
@@ -553,7 +411,7 @@ template <typename T> struct Engine final : schpf_ctx {
 
     ~Engine() override
     {
-        drop_graph();
+        drop_graphs();
         (void)hipStreamSynchronize(stream);
         if (loss_host) (void)hipHostFree(loss_host);
         if (own_stream) (void)hipStreamDestroy(stream);
@@ -585,28 +443,12 @@ template <typename T> struct Engine final : schpf_ctx {
         std::vector<int32_t>().swap(h.slice_steps);
     }
 
-    // device half of a tile plan: upload the host-built arrays (td.host), allocate the partials
-    void upload_tile(TileDev &td, double host_seconds)
-    {
-        const double t1 = now_s();
-        auto &h = td.host;
-        td.entry_slots = (int64_t)h.entries.size() / (h.packed ? 1 : 2);
-        upload(td.entries, h.entries, stream);
-        upload(td.steps, h.steps, stream);
-        finish_tile(td);
-        if (tuning.verbose)
-            fprintf(stderr, "[schpf_hip]   tile plan %d x %d: host build %.3f s, H2D %.3f s (%.2f GB entries)\n",
-                    h.n_major, h.n_minor, host_seconds, now_s() - t1, h.entries.size() * 4e-9);
-        schpf::BigVec<uint32_t>().swap(h.entries);
-    }
-
     // Tasks of the loss pass: the sub-ranges of the iteration's tasks that policy.cpp loss_cut chose, longest first
-    void loss_tasks(TileDev &td)
+    void loss_tasks(TileDev &td, const UploadJob &job)
     {
         auto &h = td.host;
-        td.n_llh_tasks = 0;
-        for (DevBuf *b : {&td.llh_block, &td.llh_w0, &td.llh_w1, &td.llh_stage_end, &td.llh_wave_off, &td.llh_order}) b->release();
-        const schpf::LossCut cut = schpf::loss_cut(problem(), tuning, h);
+        td.llh = TaskList();
+        const schpf::LossCut cut = schpf::loss_cut(problem(job), tuning, h);
         td.llh_model = cut.model;
         if (cut.parts <= 1) return;
         const int wpb = h.wpb, W = h.n_windows;
@@ -635,29 +477,31 @@ template <typename T> struct Engine final : schpf_ctx {
         order.resize(blk.size());
         for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
         std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return work[(size_t)x] > work[(size_t)y]; });
-        td.n_llh_tasks = (int64_t)blk.size();
-        upload(td.llh_block, blk, stream); upload(td.llh_w0, w0s, stream); upload(td.llh_w1, w1s, stream);
-        upload(td.llh_stage_end, ends, stream); upload(td.llh_wave_off, woff, stream); upload(td.llh_order, order, stream);
+        TaskList &tl = td.llh;
+        tl.n = (int64_t)blk.size();
+        upload(tl.block, blk, stream); upload(tl.w0, w0s, stream); upload(tl.w1, w1s, stream);
+        upload(tl.stage_end, ends, stream); upload(tl.wave_off, woff, stream); upload(tl.order, order, stream);
         HIPCHK(hipStreamSynchronize(stream));
     }
 
     // the small arrays of a tile plan (its entries and steps are on the device already)
-    void finish_tile(TileDev &td)
+    void finish_tile(TileDev &td, const UploadJob &job)
     {
         auto &h = td.host;
         const int wpb = h.wpb;
-        td.n_tasks = h.n_tasks;
         td.threads = 64 * wpb;
         td.lds_bytes = h.ring > 1 ? (size_t)h.ring * h.slot16 * 16 : (size_t)h.win_rows * KP * sizeof(T);
         td.packed = h.packed;
-        loss_tasks(td);
-        td.n_wave_out = std::max<int64_t>(h.n_tasks, td.n_llh_tasks) * wpb;
+        loss_tasks(td, job);
+        TaskList &tl = td.tasks;
+        tl.n = h.n_tasks;
+        td.n_wave_out = std::max<int64_t>(tl.n, td.llh.n) * wpb;
         upload(td.block_rows, h.block_rows, stream);
-        upload(td.task_block, h.task_block, stream);
-        upload(td.task_w0, h.task_w0, stream);
-        upload(td.task_w1, h.task_w1, stream);
-        upload(td.task_wave_off, h.task_wave_off, stream);
-        upload(td.task_order, h.task_order, stream);
+        upload(tl.block, h.task_block, stream);
+        upload(tl.w0, h.task_w0, stream);
+        upload(tl.w1, h.task_w1, stream);
+        upload(tl.wave_off, h.task_wave_off, stream);
+        upload(tl.order, h.task_order, stream);
         upload(td.pfirst, h.pfirst, stream);
         upload(td.pcount, h.pcount, stream);
         td.partials.alloc((size_t)std::max<int64_t>(h.n_partial_rows, 1) * KP * sizeof(T), true, stream);
@@ -666,67 +510,50 @@ template <typename T> struct Engine final : schpf_ctx {
         std::vector<int64_t>().swap(h.task_wave_off);
     }
 
-    // Both tile plans built by device passes over the uploaded COO (plan_device.hip): same plans,
-    // bit for bit, as build_tiles(); SCHPF_DEVICE_PLAN=0 selects the host builder.
-    void build_tiles_device(const int32_t *row, const int32_t *col, const float *val, bool packed_ok,
-                            EarlyIndexCopy &early)
+    // What the policy is told: the engine, and of the matrix what this upload says
+    schpf::Problem problem(const UploadJob &job) const
     {
-        const double t0 = now_s();
-        int ranges[2] = {0, 0}, half[2] = {-1, -1};
-        if (!schpf::choose_ranges(problem(), tuning, row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
-        bool rc_sorted = true, cr_sorted = true;
-        schpf::coo_order_flags(nnz, row, col, rc_sorted, cr_sorted);
-        DevBuf d_val;
-        d_val.alloc((size_t)nnz * 4);
-        if (nnz > 0) HIPCHK(hipMemcpyAsync(d_val.p, val, (size_t)nnz * 4, hipMemcpyHostToDevice, stream));
-        early.join();                                  // the indices went up beside the validation pass
-        if (!early.error.empty()) throw HipError(early.error);
-        const double t1 = now_s();
-        plans_from_device_coo(early.d_row, early.d_col, d_val, rc_sorted, cr_sorted, packed_ok, ranges, half);
-        // constant term of the loss, sum lgamma(x + 1) (hpf_numba.py:49-50), while the values are still resident:
-        // no second trip of the values over PCIe
-        gammaln_partial_sums(d_val.as<float>());
-        count_sums(d_val.as<float>());
-        gammaln_on_device = true;
-        if (want_rows) {   // the (row, col)-sorted copy minibatches gather their rows from
-            rows_col.alloc((size_t)nnz * 4); rows_val.alloc((size_t)nnz * 4);
-            const TileDev &tc = side[0].tile;   // the cell plan's order; rows_ptr's host copy stays tc.host.mptr
-            HIPCHK(schpf::launch_gather_by_order(tc.order_identity ? nullptr : tc.order_dev.as<int>(),
-                                                 static_cast<const int *>(early.d_col.p), d_val.as<float>(), nnz, rows_col.as<int>(),
-                                                 rows_val.as<float>(), stream));
-            upload(rows_ptr, tc.host.mptr, stream);
-            rows_packed_ok = packed_ok;
-            HIPCHK(hipStreamSynchronize(stream));
+        return {N, G, K, (int)sizeof(T), job.nnz, cu_count, LPC, NV, KL, KP, expect_sharded, transient, want_rows,
+                job.batch_rows, job.balance};
+    }
+    // ... and after the upload (loss_side, sweep_bytes): the matrix the engine holds.  policy.cpp loss_side reads the
+    // engine's constants only, so the per-upload fields are simply unset
+    schpf::Problem problem() const { return problem(UploadJob{nnz}); }
+
+    // The shapes of both tile plans, once per upload, for whichever builder runs.  row / col: the COO on the host for
+    // the task-range model to sample; nullptr: no ranges (batch rows)
+    void plan_shapes(UploadJob &job, const int32_t *row, const int32_t *col) const
+    {
+        if (!row || !schpf::choose_ranges(problem(job), tuning, row, col, job.ranges, job.half)) {
+            job.ranges[0] = job.ranges[1] = 0;
+            job.half[0] = job.half[1] = -1;
         }
-        if (tuning.verbose)
-            fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
-                    "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
-                    t1 - t0, early.seconds, now_s() - t1, (side[0].tile.entries.bytes + side[1].tile.entries.bytes) * 1e-9);
+        for (int s = 0; s < 2; ++s) {
+            const schpf::TileShape &sh = job.shape[s] =
+                schpf::tile_shape(problem(job), tuning, side[s].n, side[1 - s].n, job.ranges[s], job.half[s]);
+            job.balanced[s] = job.balance && sh.ring <= 1 && sh.waves_per_block >= 12;   // the balanced kernels are 1024-thread ones
+        }
     }
 
-    // both tile plans from a COO that is already in HBM
-    void plans_from_device_coo(const DevBuf &d_row, const DevBuf &d_col, const DevBuf &d_val, bool rc_sorted,
-                               bool cr_sorted, bool packed_ok, const int ranges[2], const int half[2])
+    // Both tile plans built by device passes over a COO that is in HBM (plan_device.hip): same plans, bit for bit, as
+    // tiles_from_host_coo(); SCHPF_DEVICE_PLAN=0 selects the host builder for schpf_upload_coo.
+    void tiles_from_device_coo(const UploadJob &job, const DevBuf &d_row, const DevBuf &d_col, const DevBuf &d_val)
     {
         // per side: its index array is the major one, the other side's the minor one
         const int32_t *const d_idx[2] = {d_row.as<int32_t>(), d_col.as<int32_t>()};
-        const bool sorted[2] = {rc_sorted, cr_sorted};
-        const schpf::TileShape shapes[2] = {tile_shape_of(0, ranges, half), tile_shape_of(1, ranges, half)};
-        // the two orientations are independent (the COO is only read): the gene side on a helper thread with a
-        // stream of its own, so that the builders' host round trips (run pointers, step counts, allocations) and
-        // their short kernels overlap instead of adding up
+        const int64_t nz = job.nnz;
         auto build_side = [&](int si, hipStream_t st) {
             TileDev &td = side[si].tile;
             void *e = nullptr, *s = nullptr, *o = nullptr;
             size_t eb = 0;
-            bool presorted = sorted[si];
+            bool presorted = job.sorted[si];
             const int32_t *d_major = d_idx[si], *d_minor = d_idx[1 - si];
-            const schpf::TileShape &sh = shapes[si];
+            const schpf::TileShape &sh = job.shape[si];
             const int n_major = side[si].n;
             int n_minor_plan = side[1 - si].n;
             DevBuf vminor;
             td.minor_of.release(); td.n_virtual = 0;
-            if (balance_now && sh.ring <= 1 && sh.waves_per_block >= 12) {   // the balanced kernels are 1024-thread ones
+            if (job.balanced[si]) {
                 const double tb = now_s();
                 schpf::BalanceGeometry geo;
                 void *mo = nullptr;
@@ -734,8 +561,8 @@ template <typename T> struct Engine final : schpf_ctx {
                 // that leaves no room for that is planned by index instead (the shape is valid for either)
                 bool balanced = true;
                 try {
-                    vminor.alloc((size_t)nnz * 4);
-                    schpf::balance_windows_device((void *)st, nnz, d_major, d_minor, n_major, n_minor_plan, sh,
+                    vminor.alloc((size_t)nz * 4);
+                    schpf::balance_windows_device((void *)st, nz, d_major, d_minor, n_major, n_minor_plan, sh,
                                                   vminor.as<int32_t>(), &mo, geo);
                 } catch (const std::invalid_argument &) {
                     throw;
@@ -746,7 +573,7 @@ template <typename T> struct Engine final : schpf_ctx {
                         fprintf(stderr, "[schpf_hip]   balanced windows, side %d: not built (%s); windows by index\n", si, e.what());
                 }
                 if (balanced) {
-                    td.minor_of.p = mo; td.minor_of.bytes = (size_t)geo.n_blocks * geo.n_virtual * 4;
+                    td.minor_of.adopt(mo, (size_t)geo.n_blocks * geo.n_virtual * 4);
                     td.n_virtual = geo.n_virtual;
                     d_minor = vminor.as<int32_t>();
                     n_minor_plan = geo.n_virtual;
@@ -756,129 +583,63 @@ template <typename T> struct Engine final : schpf_ctx {
                     fprintf(stderr, "[schpf_hip]   balanced windows, side %d: %d sections of %d windows, %.3f s\n", si,
                             geo.n_sections, geo.D, now_s() - tb);
             }
-            schpf::build_tile_plan_device((void *)st, nnz, d_major, d_minor, d_val.as<float>(),
-                                          presorted, packed_ok, n_major, n_minor_plan,
+            schpf::build_tile_plan_device((void *)st, nz, d_major, d_minor, d_val.as<float>(),
+                                          presorted, job.packed_ok, n_major, n_minor_plan,
                                           sh, td.host, &e, &eb, &s, &o);
-            td.entries.release(); td.entries.p = e; td.entries.bytes = eb;
-            td.steps.release(); td.steps.p = s; td.steps.bytes = td.host.steps.size() * 2;
-            td.order_dev.release(); td.order_dev.p = o; td.order_dev.bytes = o ? (size_t)nnz * 4 : 0;
+            td.entries.adopt(e, eb);
+            td.steps.adopt(s, td.host.steps.size() * 2);
+            td.order_dev.adopt(o, o ? (size_t)nz * 4 : 0);
             td.order_identity = presorted;
             td.entry_slots = (int64_t)(eb / 4) / (td.host.packed ? 1 : 2);
         };
         HIPCHK(hipStreamSynchronize(stream));   // the COO is on the device before either builder reads it
-        std::exception_ptr err;
-        std::thread helper([&] {
-            try {
-                HIPCHK(hipSetDevice(device));
-                hipStream_t st2 = nullptr;
-                HIPCHK(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-                try {
-                    build_side(1, st2);
-                    HIPCHK(hipStreamSynchronize(st2));
-                } catch (...) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); throw; }
-                (void)hipStreamDestroy(st2);
-            } catch (...) { err = std::current_exception(); }
-        });
-        try { build_side(0, stream); } catch (...) { helper.join(); throw; }
-        helper.join();
-        if (err) std::rethrow_exception(err);
-        for (Side &sd : side) finish_tile(sd.tile);
+        // the two orientations are independent (the COO is only read): the gene side on a helper thread with a
+        // stream of its own, so that the builders' host round trips (run pointers, step counts, allocations) and
+        // their short kernels overlap instead of adding up
+        on_both_sides(device, stream, true, build_side);
+        for (Side &sd : side) finish_tile(sd.tile, job);
         build_dual_order();
     }
 
-    // This engine's matrix := the rows `rows` (in that order) of `source`'s, gathered on the device
-    void upload_rows(schpf_ctx *source_, const int32_t *rows, int n_rows) override
+    // Both tile plans from the host builder (plan.cpp): the two orientations concurrently (each with its own thread
+    // team), then uploaded one after the other on the context's stream
+    void tiles_from_host_coo(const UploadJob &job, const int32_t *row, const int32_t *col, const float *val)
     {
-        Engine<T> *src = dynamic_cast<Engine<T> *>(source_);
-        if (!src) throw std::invalid_argument("the source engine must have this engine's dtype");
-        if (!src->rows_ptr.p || !src->have_coo) throw std::logic_error("the source keeps no rows (schpf_keep_rows before its upload)");
-        if (src == this) throw std::invalid_argument("an engine cannot gather batch rows from itself");
-        if (src->device != device) throw std::invalid_argument("source and batch engine must be on one device");
-        if (src->G != G || src->K != K) throw std::invalid_argument("source and batch engine differ in genes or factors");
-        if (n_rows != N) throw std::invalid_argument("n_rows must be the number of cells the batch engine was created with");
-        if (!want_tile) throw std::invalid_argument("upload_rows needs the tile plan");
-        const std::vector<int64_t> &sp = src->side[0].tile.host.mptr;   // host copy of src->rows_ptr
-        std::vector<int64_t> dp((size_t)n_rows + 1, 0);
-        for (int i = 0; i < n_rows; ++i) {
-            if (rows[i] < 0 || rows[i] >= src->N) throw std::invalid_argument("batch row out of range");
-            dp[(size_t)i + 1] = dp[(size_t)i] + (sp[(size_t)rows[i] + 1] - sp[(size_t)rows[i]]);
-        }
-        forget_matrix();                  // a failed plan build must not leave have_coo set over empty plans
-        balance_now = false;              // a batch is planned every iteration: the cheapest build
-        nnz = dp[(size_t)n_rows];
-        std::vector<int32_t> rv(rows, rows + n_rows);
-        DevBuf d_rows, d_dp, d_row, d_col, d_val;
-        upload(d_rows, rv, stream);
-        upload(d_dp, dp, stream);
-        d_row.alloc((size_t)nnz * 4); d_col.alloc((size_t)nnz * 4); d_val.alloc((size_t)nnz * 4);
-        HIPCHK(schpf::launch_gather_rows(d_rows.as<int>(), n_rows, src->rows_ptr.as<int64_t>(), src->rows_col.as<int>(),
-                                         src->rows_val.as<float>(), d_dp.as<int64_t>(), d_row.as<int>(), d_col.as<int>(),
-                                         d_val.as<float>(), stream));
-        use_tile = true;
-        const int ranges[2] = {0, 0}, half[2] = {-1, -1};
-        // rows in batch order with their columns ascending: sorted by (row, col) already
-        planning_batch_rows = true;
-        try { plans_from_device_coo(d_row, d_col, d_val, true, false, src->rows_packed_ok, ranges, half); }
-        catch (...) { planning_batch_rows = false; throw; }
-        planning_batch_rows = false;
-        wave_out.alloc((size_t)std::max<int64_t>(side[0].tile.n_wave_out, 1) * sizeof(double), true, stream);
-        HIPCHK(hipStreamSynchronize(stream));
-        n_rounded = 0; n_zero = 0;
-        zero_row.release(); zero_col.release();
-        have_loss_constants = false;      // no lgamma sum, no stored-zero list: the loss is the source engine's business
-        have_coo = true;
-        pending_init = 0;
-        drop_graph();
-        eager_since_upload = false;
-    }
-
-    schpf::Problem problem() const
-    {
-        return {N, G, K, (int)sizeof(T), nnz, cu_count, LPC, NV, KL, KP, expect_sharded, transient, want_rows,
-                planning_batch_rows, balance_now};
-    }
-    schpf::TileShape tile_shape_of(int s, const int ranges[2], const int half[2]) const
-    {
-        return schpf::tile_shape(problem(), tuning, side[s].n, side[1 - s].n, ranges[s], half[s]);
-    }
-
-    // both orientations are built concurrently on the host (each with its own thread team),
-    // then uploaded one after the other on the context's stream
-    void build_tiles(const int32_t *row, const int32_t *col, const float *val)
-    {
-        int ranges[2] = {0, 0}, half[2] = {-1, -1};
-        if (!schpf::choose_ranges(problem(), tuning, row, col, ranges, half)) { ranges[0] = ranges[1] = 0; half[0] = half[1] = -1; }
         const int32_t *const idx[2] = {row, col};   // per side: its index array is the major one, the other's the minor one
-        const schpf::TileShape shapes[2] = {tile_shape_of(0, ranges, half), tile_shape_of(1, ranges, half)};
-        std::exception_ptr err;
         double secs[2] = {0.0, 0.0};
         // balanced windows: the builder runs on the block's virtual numbering of the minor rows (plan.h)
         std::vector<int32_t> mo[2];
-        auto build_host = [&](int s) {
+        on_both_sides(device, stream, false, [&](int s, hipStream_t) {
             const double t0 = now_s();
             const int32_t *major = idx[s], *minor = idx[1 - s];
             const int n_major = side[s].n, n_minor = side[1 - s].n;
-            const schpf::TileShape &sh = shapes[s];
+            const schpf::TileShape &sh = job.shape[s];
             TileDev &td = side[s].tile;
             td.n_virtual = 0;
-            if (balance_now && sh.ring <= 1 && sh.waves_per_block >= 12) {
+            if (job.balanced[s]) {
                 schpf::BigVec<int32_t> vminor;
                 schpf::BalanceGeometry geo;
-                schpf::balance_windows_host(nnz, major, minor, n_major, n_minor, sh, vminor, mo[s], geo);
+                schpf::balance_windows_host(job.nnz, major, minor, n_major, n_minor, sh, vminor, mo[s], geo);
                 td.n_virtual = geo.n_virtual;
-                schpf::build_tile_plan(nnz, major, vminor.data(), val, n_major, geo.n_virtual, sh, true, td.host);
+                schpf::build_tile_plan(job.nnz, major, vminor.data(), val, n_major, geo.n_virtual, sh, true, td.host);
             } else {
-                schpf::build_tile_plan(nnz, major, minor, val, n_major, n_minor, sh, true, td.host);
+                schpf::build_tile_plan(job.nnz, major, minor, val, n_major, n_minor, sh, true, td.host);
             }
             secs[s] = now_s() - t0;
-        };
-        std::thread helper([&] {   // the gene side
-            try { build_host(1); } catch (...) { err = std::current_exception(); }
         });
-        try { build_host(0); } catch (...) { helper.join(); throw; }
-        helper.join();
-        if (err) std::rethrow_exception(err);
-        for (int s = 0; s < 2; ++s) upload_tile(side[s].tile, secs[s]);
+        for (int s = 0; s < 2; ++s) {   // device half: upload the host-built arrays, allocate the partials
+            TileDev &td = side[s].tile;
+            const double t1 = now_s();
+            auto &h = td.host;
+            td.entry_slots = (int64_t)h.entries.size() / (h.packed ? 1 : 2);
+            upload(td.entries, h.entries, stream);
+            upload(td.steps, h.steps, stream);
+            finish_tile(td, job);
+            if (tuning.verbose)
+                fprintf(stderr, "[schpf_hip]   tile plan %d x %d: host build %.3f s, H2D %.3f s (%.2f GB entries)\n",
+                        h.n_major, h.n_minor, secs[s], now_s() - t1, h.entries.size() * 4e-9);
+            schpf::BigVec<uint32_t>().swap(h.entries);
+        }
         for (int s = 0; s < 2; ++s) {
             TileDev &td = side[s].tile;
             td.minor_of.release();
@@ -914,18 +675,16 @@ template <typename T> struct Engine final : schpf_ctx {
         }
     }
 
-    void gammaln_partial_sums(const float *d_values)
+    // The upload's constants, from the values on the device: sum lgamma(x + 1), the constant term of the loss
+    // (hpf_numba.py:49-50), into scalars[1]; and the ELBO shift terms (elbo_terms), the stored counts of every cell and
+    // every gene, summed over each plan's (major, minor)-sorted runs -- once per upload, N + G doubles.
+    // Returns the wall time of the count sums.
+    double loss_constants(const float *d_values)
     {
         const int nb = 512;
         if (!gammaln_part.p) gammaln_part.alloc(nb * sizeof(double));
         HIPCHK(schpf::launch_gammaln_sum(d_values, nnz, gammaln_part.as<double>(), nb, stream));
         HIPCHK(schpf::launch_sum_doubles(gammaln_part.as<double>(), nb, scalars.as<double>() + 1, stream));
-    }
-
-    // ELBO shift terms (elbo_terms): the stored counts of every cell and every gene, summed over each plan's
-    // (major, minor)-sorted runs while the values are on the device -- once per upload, N + G doubles (count_seconds)
-    void count_sums(const float *d_values)
-    {
         const double t0 = now_s();
         for (int s = 0; s < 2; ++s) {
             Side &sd = side[s];
@@ -937,12 +696,70 @@ template <typename T> struct Engine final : schpf_ctx {
             HIPCHK(schpf::launch_count_sums(d_values, ord, mp.as<int64_t>(), sd.n, sd.count.as<double>(), stream));
             HIPCHK(hipStreamSynchronize(stream));   // scratch and mp die with this scope
         }
-        count_seconds = now_s() - t0;
+        return now_s() - t0;
     }
 
     static double now_s()
     {
         return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    }
+
+    // The engine now holds the matrix whose plans were just built.  n_out: doubles a loss pass leaves in wave_out.
+    // loss_constants: false for gathered batch rows, whose loss is the source engine's business (no lgamma sum, no
+    // stored-zero list)
+    void holds_matrix(int64_t n_out, bool loss_constants)
+    {
+        wave_out.alloc((size_t)std::max<int64_t>(n_out, 1) * sizeof(double), true, stream);
+        HIPCHK(hipStreamSynchronize(stream));
+        if (!loss_constants) {
+            n_rounded = 0; n_zero = 0;
+            zero_row.release(); zero_col.release();
+        }
+        have_loss_constants = loss_constants;
+        have_coo = true;
+        pending_init = 0;
+        drop_graphs();
+        eager_since_upload = false;
+    }
+
+    // This engine's matrix := the rows `rows` (in that order) of `source`'s, gathered on the device
+    void upload_rows(schpf_ctx *source_, const int32_t *rows, int n_rows) override
+    {
+        Engine<T> *src = dynamic_cast<Engine<T> *>(source_);
+        if (!src) throw std::invalid_argument("the source engine must have this engine's dtype");
+        if (!src->rows_ptr.p || !src->have_coo) throw std::logic_error("the source keeps no rows (schpf_keep_rows before its upload)");
+        if (src == this) throw std::invalid_argument("an engine cannot gather batch rows from itself");
+        if (src->device != device) throw std::invalid_argument("source and batch engine must be on one device");
+        if (src->G != G || src->K != K) throw std::invalid_argument("source and batch engine differ in genes or factors");
+        if (n_rows != N) throw std::invalid_argument("n_rows must be the number of cells the batch engine was created with");
+        if (!want_tile) throw std::invalid_argument("upload_rows needs the tile plan");
+        const std::vector<int64_t> &sp = src->side[0].tile.host.mptr;   // host copy of src->rows_ptr
+        std::vector<int64_t> dp((size_t)n_rows + 1, 0);
+        for (int i = 0; i < n_rows; ++i) {
+            if (rows[i] < 0 || rows[i] >= src->N) throw std::invalid_argument("batch row out of range");
+            dp[(size_t)i + 1] = dp[(size_t)i] + (sp[(size_t)rows[i] + 1] - sp[(size_t)rows[i]]);
+        }
+        forget_matrix();                  // a failed plan build must not leave have_coo set over empty plans
+        // a batch is planned every iteration, the cheapest way: no balanced windows, no task ranges, no loss tasks.
+        // Its rows come in batch order with their columns ascending: sorted by (row, col) already
+        UploadJob job;
+        job.nnz = dp[(size_t)n_rows];
+        job.batch_rows = true;
+        job.packed_ok = src->rows_packed_ok;
+        job.sorted[1] = false;
+        nnz = job.nnz;
+        std::vector<int32_t> rv(rows, rows + n_rows);
+        DevBuf d_rows, d_dp, d_row, d_col, d_val;
+        upload(d_rows, rv, stream);
+        upload(d_dp, dp, stream);
+        d_row.alloc((size_t)nnz * 4); d_col.alloc((size_t)nnz * 4); d_val.alloc((size_t)nnz * 4);
+        HIPCHK(schpf::launch_gather_rows(d_rows.as<int>(), n_rows, src->rows_ptr.as<int64_t>(), src->rows_col.as<int>(),
+                                         src->rows_val.as<float>(), d_dp.as<int64_t>(), d_row.as<int>(), d_col.as<int>(),
+                                         d_val.as<float>(), stream));
+        use_tile = true;
+        plan_shapes(job, nullptr, nullptr);
+        tiles_from_device_coo(job, d_row, d_col, d_val);
+        holds_matrix(side[0].tile.n_wave_out, false);
     }
 
     void upload_coo(int64_t nnz_, const int32_t *row, const int32_t *col, const void *val, int kind) override
@@ -954,16 +771,15 @@ template <typename T> struct Engine final : schpf_ctx {
         // (a re-upload onto a live engine would otherwise peak at the old plans + the new indices), and an upload
         // that fails leaves an engine without a matrix, not one with half of the old one
         forget_matrix();
-        {
-            schpf::Problem p = problem();
-            p.nnz = nnz_;
-            balance_now = want_tile && schpf::balance_windows(p, tuning);
-        }
+        // balanced windows (plan.h): for uploads of a whole matrix; not for an engine that keeps a (row, col)-sorted copy
+        // (the plans' own order is then the virtual one) nor for one whose matrix is replaced every iteration
+        UploadJob job;
+        job.nnz = nnz_;
+        job.balance = want_tile && schpf::balance_windows(problem(job), tuning);
         EarlyIndexCopy early;
         const bool device_plans = want_tile && tuning.device_plan;
         if (device_plans) early.start(device, nnz_, row, col);
         schpf::BigVec<float> v((size_t)nnz_);   // no serial zero-fill: written by the threaded pass below
-        bool packed_ok = true;
         n_rounded = 0;
         std::vector<int32_t> zrow, zcol;         // explicitly stored zeros (rare): see zero_rate_sum()
         {   // validate + convert, in parallel slabs (first offending entry per slab is reported)
@@ -976,13 +792,7 @@ template <typename T> struct Engine final : schpf_ctx {
                 th.emplace_back([&, t] {
                     const int64_t b = nnz_ * t / nth, e = nnz_ * (t + 1) / nth;
                     for (int64_t i = b; i < e; ++i) {
-                        double d;
-                        switch (kind) {
-                        case SCHPF_VAL_I32: d = (double)((const int32_t *)val)[i]; break;
-                        case SCHPF_VAL_I64: d = (double)((const int64_t *)val)[i]; break;
-                        case SCHPF_VAL_F32: d = (double)((const float *)val)[i]; break;
-                        default: d = ((const double *)val)[i]; break;
-                        }
+                        const double d = read_count(val, kind, i);
                         const float f = (float)d;
                         // the reference takes any X.data (hpf_numba.py:98-112 only multiplies by it); what
                         // cannot be a Poisson observation at all (negative, NaN, inf) is refused
@@ -996,7 +806,7 @@ template <typename T> struct Engine final : schpf_ctx {
                     }
                 });
             for (auto &x : th) x.join();
-            for (int t = 0; t < nth; ++t) packed_ok = packed_ok && !wide[(size_t)t];
+            for (int t = 0; t < nth; ++t) job.packed_ok = job.packed_ok && !wide[(size_t)t];
             for (int t = 0; t < nth; ++t) {
                 if (bad_idx[(size_t)t] >= 0)
                     throw std::invalid_argument("COO index out of range at entry " + std::to_string(bad_idx[(size_t)t]));
@@ -1015,37 +825,50 @@ template <typename T> struct Engine final : schpf_ctx {
         nnz = nnz_;
         use_tile = want_tile;
         int64_t n_out;
+        DevBuf d_val;   // the values on the device: beside the indices for the device builder, afterwards for the others
         if (use_tile) {
-            if (device_plans) build_tiles_device(row, col, v.data(), packed_ok, early);
-            else build_tiles(row, col, v.data());
+            plan_shapes(job, row, col);
+            if (device_plans) {
+                schpf::coo_order_flags(nnz, row, col, job.sorted[0], job.sorted[1]);
+                d_val.alloc((size_t)nnz * 4);
+                if (nnz > 0) HIPCHK(hipMemcpyAsync(d_val.p, v.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, stream));
+                early.join();                                  // the indices went up beside the validation pass
+                if (!early.error.empty()) throw HipError(early.error);
+                const double t1 = now_s();
+                tiles_from_device_coo(job, early.d_row, early.d_col, d_val);
+                if (tuning.verbose)
+                    fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
+                            "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
+                            t1 - t_valid, early.seconds, now_s() - t1, (side[0].tile.entries.bytes + side[1].tile.entries.bytes) * 1e-9);
+            } else tiles_from_host_coo(job, row, col, v.data());
             n_out = std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);   // the loss pass sweeps either plan (loss_side)
         } else {
             const int32_t *const idx[2] = {row, col};
-            const int chunk = schpf::gather_chunk_len(problem());
+            const int chunk = schpf::gather_chunk_len(problem(job));
             for (int s = 0; s < 2; ++s)   // windows: by the size of the minor side's table
                 build_plan(side[s].plan, nnz, idx[s], idx[1 - s], v.data(), side[s].n, side[1 - s].n,
                            schpf::pick_windows((size_t)side[1 - s].n * KP * sizeof(T)), chunk);
             n_out = side[0].plan.n_waves;   // the gather loss pass always sweeps the cell plan (loss_side)
         }
-        wave_out.alloc((size_t)std::max<int64_t>(n_out, 1) * sizeof(double), true, stream);
-
         const double t_plans = now_s();
-        // constant term of the loss: sum lgamma(x + 1)   (hpf_numba.py:49-50)
-        DevBuf dv;
-        if (!gammaln_on_device) {          // host-built plans: the values go up once more for it
-            upload(dv, v, stream);
-            gammaln_partial_sums(dv.as<float>());
-            count_sums(dv.as<float>());
+        // the device builder's values are still resident: no second trip over PCIe.  Host-built plans: they go up now
+        if (!device_plans) upload(d_val, v, stream);
+        const double count_seconds = loss_constants(d_val.as<float>());
+        if (device_plans && want_rows) {   // the (row, col)-sorted copy minibatches gather their rows from
+            rows_col.alloc((size_t)nnz * 4); rows_val.alloc((size_t)nnz * 4);
+            const TileDev &tc = side[0].tile;   // the cell plan's order; rows_ptr's host copy stays tc.host.mptr
+            HIPCHK(schpf::launch_gather_by_order(tc.order_identity ? nullptr : tc.order_dev.as<int>(),
+                                                 static_cast<const int *>(early.d_col.p), d_val.as<float>(), nnz, rows_col.as<int>(),
+                                                 rows_val.as<float>(), stream));
+            upload(rows_ptr, tc.host.mptr, stream);
+            rows_packed_ok = job.packed_ok;
+            HIPCHK(hipStreamSynchronize(stream));
         }
-        gammaln_on_device = false;
         HIPCHK(hipMemcpyAsync(&gammaln_sum, scalars.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost,
                               stream));
         HIPCHK(hipStreamSynchronize(stream));
-        have_coo = true;
-        have_loss_constants = true;
-        pending_init = 0;
-        drop_graph();
-        eager_since_upload = false;
+        d_val.release();
+        holds_matrix(n_out, true);
         if (tuning.verbose)
             fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads); "
                     "ELBO count sums %.4f s of it\n",
@@ -1151,17 +974,19 @@ template <typename T> struct Engine final : schpf_ctx {
         return a;
     }
 
-    schpf::TileArgs<T> tile_args(int s, int mode)
+    // tl: the side's task list the launch walks (TileDev::tasks, or llh for a cut loss pass)
+    schpf::TileArgs<T> tile_args(int s, int mode, const TaskList &tl)
     {
         TileDev &td = side[s].tile;
         schpf::TileArgs<T> a{};
         a.entries = td.entries.p;
         a.steps = td.steps.as<uint16_t>();
         a.block_rows = td.block_rows.as<int>();
-        a.task_block = td.task_block.as<int>();
-        a.task_w0 = td.task_w0.as<int>();
-        a.task_w1 = td.task_w1.as<int>();
-        a.task_wave_off = td.task_wave_off.as<int64_t>();
+        a.task_block = tl.block.as<int>();
+        a.task_w0 = tl.w0.as<int>();
+        a.task_w1 = tl.w1.as<int>();
+        a.task_stage_end = tl.stage_end.as<int>();   // nullptr for the iteration's tasks
+        a.task_wave_off = tl.wave_off.as<int64_t>();
         a.task_order = nullptr;   // natural order (plan.cpp)
         table_args(a, s, mode);
         a.partials = td.partials.as<T>();
@@ -1182,26 +1007,22 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         if (use_tile) {
             TileDev &td = side[s].tile;
-            auto a = tile_args(s, mode);
-            a.seed = seed;
-            int64_t n_tasks = td.n_tasks;
             const bool logs = mode == schpf::MODE_LLH || mode == schpf::MODE_ELBO;   // the ELBO pass is cut as the loss pass
-            const bool cut = logs && td.n_llh_tasks > 0;   // the loss pass's finer tasks (loss_tasks)
-            if (cut) {
-                a.task_block = td.llh_block.as<int>(); a.task_w0 = td.llh_w0.as<int>(); a.task_w1 = td.llh_w1.as<int>();
-                a.task_stage_end = td.llh_stage_end.as<int>(); a.task_wave_off = td.llh_wave_off.as<int64_t>();
-                n_tasks = td.n_llh_tasks;
-            }
-            if (mode != schpf::MODE_RANDOM && tuning.persistent) {   // see step_local
+            const bool cut = logs && td.llh.n > 0;   // the loss pass's finer tasks (loss_tasks)
+            const TaskList &tl = cut ? td.llh : td.tasks;
+            auto a = tile_args(s, mode, tl);
+            a.seed = seed;
+            const bool persistent = mode != schpf::MODE_RANDOM && tuning.persistent;   // see step_local
+            if (persistent) {
                 a.queue = dual_queue.as<int>();
                 a.resident = cu_count * schpf::per_cu(td.lds_bytes);
-                a.task_order = cut ? td.llh_order.as<int>() : td.task_order.as<int>();
-            } else if (cut) a.task_order = td.llh_order.as<int>();
+            }
+            if (persistent || cut) a.task_order = tl.order.as<int>();
             // the loss pass keeps a 1 KiB logarithm table behind the window (sweep_impl.h LlhAccumulator)
             a.llh_tab_off = (int)((td.lds_bytes + 15) & ~(size_t)15);
             const size_t lds = logs ? (size_t)a.llh_tab_off + 1024 : td.lds_bytes;
             if (mode == schpf::MODE_ELBO) a.clock_probe = nullptr;   // schpf_profile_clock: the sweeps and the loss pass
-            HIPCHK(schpf::launch_tile_sweep<T>(a, NV, LPC, mode, td.packed ? 1 : 0, n_tasks, td.threads, lds, stream));
+            HIPCHK(schpf::launch_tile_sweep<T>(a, NV, LPC, mode, td.packed ? 1 : 0, tl.n, td.threads, lds, stream));
         } else {
             PlanDev &pd = side[s].plan;
             auto a = sweep_args(s, mode);
@@ -1302,7 +1123,7 @@ template <typename T> struct Engine final : schpf_ctx {
             ScopedTimer tm(prof, stream, 0);
             // Not symmetric: the kernel takes (cell args, gene args) in that order; dual_order names gene tasks as ~task
             const TileDev &tc = side[0].tile, &tg = side[1].tile;
-            auto ac = tile_args(0, schpf::MODE_PHI), ag = tile_args(1, schpf::MODE_PHI);
+            auto ac = tile_args(0, schpf::MODE_PHI, tc.tasks), ag = tile_args(1, schpf::MODE_PHI, tg.tasks);
             // persistent workgroups (SCHPF_PERSISTENT=0: one workgroup per slot): as many as the device holds at
             // once draw the slots of the longest-first list from a counter -- no workgroup teardown / launch
             // between the ~6 tasks of a compute unit and whoever is free takes the next task: C3 sweep
@@ -1478,7 +1299,7 @@ template <typename T> struct Engine final : schpf_ctx {
         if (!use_tile) return 0;
         const TileDev &tc = side[0].tile, &tg = side[1].tile;
         const double model[2] = {tc.llh_model, tg.llh_model};
-        const int64_t tasks[2] = {tc.n_tasks, tg.n_tasks};
+        const int64_t tasks[2] = {tc.tasks.n, tg.tasks.n};
         // the policy's question about wave_out is whether the gene plan's pass fits; the LDS figure is the cell plan's
         return schpf::loss_side(problem(), tuning, wave_out.bytes >= (size_t)tg.n_wave_out * sizeof(double), model, tasks,
                                 tc.lds_bytes);
@@ -1540,7 +1361,7 @@ template <typename T> struct Engine final : schpf_ctx {
         const int ls = loss_side();
         const TileDev &tl = side[ls].tile;
         info[6] = ls;
-        info[7] = tl.n_llh_tasks > 0 ? tl.n_llh_tasks : tl.n_tasks;
+        info[7] = tl.llh.n > 0 ? tl.llh.n : tl.tasks.n;
     }
 
     // per-side entries come in (cell, gene) pairs; [3], [14], [15] describe the cell plan
@@ -1555,167 +1376,16 @@ template <typename T> struct Engine final : schpf_ctx {
             const PlanDev &pd = side[s].plan;
             info[4 + s] = use_tile ? td.host.n_windows : pd.host.n_windows;
             info[6 + s] = use_tile ? td.host.n_partial_rows : pd.n_chunks;
-            info[8 + s] = use_tile ? td.n_tasks : pd.n_waves;
+            info[8 + s] = use_tile ? td.tasks.n : pd.n_waves;
             info[10 + s] = use_tile ? td.entry_slots : pd.entry_slots;
             info[12 + s] = use_tile ? td.host.ring : 0;
         }
     }
 };
 
-// ------------------------------------------------------------- stateless helpers
-struct TempStream {
-    hipStream_t st = nullptr;
-    TempStream() { HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
-    ~TempStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
-};
-
-template <typename U> void h2d(DevBuf &b, const void *src, size_t count, hipStream_t st)
-{
-    b.alloc(count * sizeof(U));
-    if (count) HIPCHK(hipMemcpyAsync(b.p, src, count * sizeof(U), hipMemcpyHostToDevice, st));
-}
-void d2h(void *dst, const DevBuf &b, size_t bytes, hipStream_t st)
-{
-    if (bytes) HIPCHK(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-}
-
-void check_indices(int64_t nnz, const int32_t *ix, int n, const char *what)
-{
-    for (int64_t i = 0; i < nnz; ++i)
-        if (ix[i] < 0 || ix[i] >= n) throw std::invalid_argument(std::string(what) + " index out of range");
-}
-
-template <typename T>
-void xphi_or_llh(bool want_llh, int64_t nnz, int N, int G, int K, const void *x, const int32_t *row,
-                 const int32_t *col, const void *ths, const void *thr, const void *bes, const void *ber, void *out)
-{
-    check_indices(nnz, row, N, "row");
-    check_indices(nnz, col, G, "col");
-    TempStream ts;
-    DevBuf dx, dr, dc, a, b, c, d, tt, tb, o;
-    h2d<T>(dx, x, (size_t)nnz, ts.st);
-    h2d<int32_t>(dr, row, (size_t)nnz, ts.st);
-    h2d<int32_t>(dc, col, (size_t)nnz, ts.st);
-    h2d<T>(a, ths, (size_t)N * K, ts.st); h2d<T>(b, thr, (size_t)N * K, ts.st);
-    h2d<T>(c, bes, (size_t)G * K, ts.st); h2d<T>(d, ber, (size_t)G * K, ts.st);
-    tt.alloc((size_t)N * K * sizeof(T)); tb.alloc((size_t)G * K * sizeof(T));
-    if (want_llh) {
-        HIPCHK(schpf::launch_ratio<T>(a.as<T>(), b.as<T>(), (int64_t)N * K, tt.as<T>(), ts.st));
-        HIPCHK(schpf::launch_ratio<T>(c.as<T>(), d.as<T>(), (int64_t)G * K, tb.as<T>(), ts.st));
-        o.alloc((size_t)nnz * sizeof(T));
-        HIPCHK(schpf::launch_llh_coo<T>(dx.as<T>(), dr.as<int>(), dc.as<int>(), tt.as<T>(), tb.as<T>(), nnz, K,
-                                        o.as<T>(), ts.st));
-        d2h(out, o, (size_t)nnz * sizeof(T), ts.st);
-    } else {
-        HIPCHK(schpf::launch_elog<T>(a.as<T>(), b.as<T>(), (int64_t)N * K, tt.as<T>(), ts.st));
-        HIPCHK(schpf::launch_elog<T>(c.as<T>(), d.as<T>(), (int64_t)G * K, tb.as<T>(), ts.st));
-        o.alloc((size_t)nnz * K * sizeof(T));
-        HIPCHK(schpf::launch_xphi_coo<T>(dx.as<T>(), dr.as<int>(), dc.as<int>(), tt.as<T>(), tb.as<T>(), nnz, K,
-                                         o.as<T>(), ts.st));
-        d2h(out, o, (size_t)nnz * K * sizeof(T), ts.st);
-    }
-}
-
-template <typename T>
-void shape_update(int64_t nnz, int K, const void *xphi, const int32_t *keep, int nkeep, double prior, void *out)
-{
-    check_indices(nnz, keep, nkeep, "keep");
-    schpf::BigVec<int32_t> order;
-    std::vector<int64_t> ptr;
-    schpf::counting_sort_positions(nnz, keep, nkeep, order, ptr);
-    TempStream ts;
-    DevBuf dx, dord, dptr, o;
-    h2d<T>(dx, xphi, (size_t)nnz * K, ts.st);
-    upload(dord, order, ts.st);
-    upload(dptr, ptr, ts.st);
-    o.alloc((size_t)nkeep * K * sizeof(T));
-    HIPCHK(schpf::launch_shape_update<T>(dx.as<T>(), dord.as<int>(), dptr.as<int64_t>(), nkeep, K, prior,
-                                         o.as<T>(), ts.st));
-    d2h(out, o, (size_t)nkeep * K * sizeof(T), ts.st);
-}
-
-template <typename T>
-void rate_update(int n, int m, int K, const void *ps, const void *pr, const void *os, const void *orr, void *out)
-{
-    if (K < 1 || K > 256) throw std::invalid_argument("nfactors must be in [1, 256]");
-    TempStream ts;
-    DevBuf a, b, c, d, part, S, o;
-    h2d<T>(a, ps, (size_t)n, ts.st); h2d<T>(b, pr, (size_t)n, ts.st);
-    h2d<T>(c, os, (size_t)m * K, ts.st); h2d<T>(d, orr, (size_t)m * K, ts.st);
-    const int rb = 256 / K;
-    const int nb = std::max(1, std::min((m + rb - 1) / rb, 512));
-    part.alloc((size_t)nb * K * sizeof(double));
-    S.alloc((size_t)K * sizeof(double));
-    HIPCHK(schpf::launch_ratio_colsum<T>(c.as<T>(), d.as<T>(), m, K, part.as<double>(), nb, ts.st));
-    HIPCHK(schpf::launch_colsum_reduce(part.as<double>(), nb, K, S.as<double>(), nullptr, 0, ts.st));
-    o.alloc((size_t)n * K * sizeof(T));
-    HIPCHK(schpf::launch_rate_update<T>(a.as<T>(), b.as<T>(), S.as<double>(), n, K, o.as<T>(), ts.st));
-    d2h(out, o, (size_t)n * K * sizeof(T), ts.st);
-}
-
-template <typename T> void capacity_rate(int n, int K, const void *shape, const void *rate, double prior, void *out)
-{
-    TempStream ts;
-    DevBuf a, b, o;
-    h2d<T>(a, shape, (size_t)n * K, ts.st); h2d<T>(b, rate, (size_t)n * K, ts.st);
-    o.alloc((size_t)n * sizeof(T));
-    HIPCHK(schpf::launch_capacity_rate<T>(a.as<T>(), b.as<T>(), n, K, prior, o.as<T>(), ts.st));
-    d2h(out, o, (size_t)n * sizeof(T), ts.st);
-}
-
-void special_array(bool gammaln, int64_t n, const double *x, double *out)
-{
-    TempStream ts;
-    DevBuf a, o;
-    h2d<double>(a, x, (size_t)n, ts.st);
-    o.alloc((size_t)n * sizeof(double));
-    if (gammaln) HIPCHK(schpf::launch_gammaln_array(a.as<double>(), n, o.as<double>(), ts.st));
-    else HIPCHK(schpf::launch_digamma_array(a.as<double>(), n, o.as<double>(), ts.st));
-    d2h(out, o, (size_t)n * sizeof(double), ts.st);
-}
-
-bool bad_dtype(int dtype) { return dtype != SCHPF_F32 && dtype != SCHPF_F64; }
-
 }  // namespace
 
 // ------------------------------------------------------------------------- C ABI
-// SCHPF_BACKTRACE=1 (debugging aid, read when the library is loaded): a SIGSEGV / SIGBUS / SIGABRT prints the native call
-// stack (glibc backtrace: module + offset per frame, resolvable with addr2line against this .so) before the previous
-// handler -- Python's faulthandler under pytest -- runs.  The GPU boxes have no debugger.
-#include <execinfo.h>
-#include <signal.h>
-#include <unistd.h>
-namespace {
-struct sigaction g_prev_segv, g_prev_bus, g_prev_abrt;
-void crash_trace(int sig, siginfo_t *info, void *uctx)
-{
-    void *frames[64];
-    const int n = backtrace(frames, 64);
-    const char msg[] = "[schpf_hip] fatal signal, native stack:\n";
-    (void)!write(2, msg, sizeof msg - 1);
-    backtrace_symbols_fd(frames, n, 2);
-    struct sigaction *prev = sig == SIGSEGV ? &g_prev_segv : sig == SIGBUS ? &g_prev_bus : &g_prev_abrt;
-    sigaction(sig, prev, nullptr);          // hand over: the previous handler (or the default action) sees the re-raised signal
-    raise(sig);
-    (void)info; (void)uctx;
-}
-struct CrashTraceInstaller {
-    CrashTraceInstaller()
-    {
-        const char *e = getenv("SCHPF_BACKTRACE");
-        if (!e || !*e || *e == '0') return;
-        struct sigaction sa;
-        std::memset(&sa, 0, sizeof sa);
-        sa.sa_sigaction = crash_trace;
-        sa.sa_flags = SA_SIGINFO | SA_ONSTACK;
-        sigaction(SIGSEGV, &sa, &g_prev_segv);
-        sigaction(SIGBUS, &sa, &g_prev_bus);
-        sigaction(SIGABRT, &sa, &g_prev_abrt);
-    }
-} g_crash_trace_installer;
-}  // namespace
-
 extern "C" {
 
 const char *schpf_last_error(void) { return g_err.c_str(); }
@@ -1731,56 +1401,6 @@ int schpf_device_count(int *count)
         hipError_t e = hipGetDeviceCount(&n);
         if (e != hipSuccess) { (void)hipGetLastError(); n = 0; }
         *count = n;
-    });
-}
-
-int schpf_digamma(int64_t n, const double *x, double *out) { return guarded([&] { special_array(false, n, x, out); }); }
-int schpf_gammaln(int64_t n, const double *x, double *out) { return guarded([&] { special_array(true, n, x, out); }); }
-
-int schpf_xphi(int dtype, int64_t nnz, int N, int G, int K, const void *x, const int32_t *row, const int32_t *col,
-               const void *ths, const void *thr, const void *bes, const void *ber, void *out)
-{
-    if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
-    return guarded([&] {
-        if (dtype == SCHPF_F64) xphi_or_llh<double>(false, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out);
-        else xphi_or_llh<float>(false, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out);
-    });
-}
-int schpf_pois_llh_pointwise(int dtype, int64_t nnz, int N, int G, int K, const void *x, const int32_t *row,
-                             const int32_t *col, const void *ths, const void *thr, const void *bes,
-                             const void *ber, void *out)
-{
-    if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
-    return guarded([&] {
-        if (dtype == SCHPF_F64) xphi_or_llh<double>(true, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out);
-        else xphi_or_llh<float>(true, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out);
-    });
-}
-int schpf_shape_update(int dtype, int64_t nnz, int K, const void *xphi, const int32_t *keep, int nkeep,
-                       double prior, void *out)
-{
-    if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
-    return guarded([&] {
-        if (dtype == SCHPF_F64) shape_update<double>(nnz, K, xphi, keep, nkeep, prior, out);
-        else shape_update<float>(nnz, K, xphi, keep, nkeep, prior, out);
-    });
-}
-int schpf_rate_update(int dtype, int n, int m, int K, const void *ps, const void *pr, const void *os,
-                      const void *orr, void *out)
-{
-    if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
-    return guarded([&] {
-        if (dtype == SCHPF_F64) rate_update<double>(n, m, K, ps, pr, os, orr, out);
-        else rate_update<float>(n, m, K, ps, pr, os, orr, out);
-    });
-}
-int schpf_capacity_rate_update(int dtype, int n, int K, const void *shape, const void *rate, double prior,
-                               void *out)
-{
-    if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
-    return guarded([&] {
-        if (dtype == SCHPF_F64) capacity_rate<double>(n, K, shape, rate, prior, out);
-        else capacity_rate<float>(n, K, shape, rate, prior, out);
     });
 }
 
@@ -1818,7 +1438,7 @@ int schpf_upload_coo(schpf_ctx *ctx, int64_t nnz, const int32_t *row, const int3
 int schpf_set_hypers(schpf_ctx *ctx, double a, double c, double bp, double dp)
 {
     if (!(a > 0 && c > 0 && bp > 0 && dp > 0)) return fail("hyperparameters must be positive");
-    CTX_CALL(ctx->a = a; ctx->c = c; ctx->bp = bp; ctx->dp = dp; ctx->hypers_changed());
+    CTX_CALL(ctx->a = a; ctx->c = c; ctx->bp = bp; ctx->dp = dp; ctx->drop_graphs());
 }
 int schpf_set_state(schpf_ctx *ctx, int which, const void *shape, const void *rate)
 {
@@ -1871,13 +1491,13 @@ int schpf_comm_init(schpf_ctx *ctx, const void *unique_id128, int rank, int worl
 {
     if (!unique_id128) return fail("unique_id is NULL");
     // a cached hipGraph of a sharded stretch holds an all-reduce bound to the communicator it was captured with: every
-    // cached graph goes before the communicator does (hypers_changed() is "drop the captured graphs")
-    CTX_CALL(ctx->hypers_changed(); ctx->comm_init(unique_id128, rank, world));
+    // cached graph goes before the communicator does
+    CTX_CALL(ctx->drop_graphs(); ctx->comm_init(unique_id128, rank, world));
 }
-int schpf_comm_destroy(schpf_ctx *ctx) { CTX_CALL(ctx->hypers_changed(); ctx->comm_destroy()); }
-int schpf_hint_sharded(schpf_ctx *ctx, int on) { CTX_CALL(ctx->hint_sharded(on)); }
-int schpf_hint_transient(schpf_ctx *ctx, int on) { CTX_CALL(ctx->hint_transient(on)); }
-int schpf_keep_rows(schpf_ctx *ctx, int on) { CTX_CALL(ctx->keep_rows(on)); }
+int schpf_comm_destroy(schpf_ctx *ctx) { CTX_CALL(ctx->drop_graphs(); ctx->comm_destroy()); }
+int schpf_hint_sharded(schpf_ctx *ctx, int on) { CTX_CALL(ctx->expect_sharded = on != 0); }
+int schpf_hint_transient(schpf_ctx *ctx, int on) { CTX_CALL(ctx->transient = on != 0); }
+int schpf_keep_rows(schpf_ctx *ctx, int on) { CTX_CALL(ctx->want_rows = on != 0); }
 int schpf_upload_rows(schpf_ctx *ctx, schpf_ctx *source, const int32_t *rows, int n_rows)
 {
     if (!source) return fail("source is NULL");
@@ -1935,197 +1555,4 @@ int schpf_upload_info(schpf_ctx *ctx, int64_t info[4])
     if (!info) return fail("output pointer is NULL");
     CTX_CALL(ctx->upload_info(info));
 }
-
-int schpf_coo_marginals(int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int kind,
-                        int ncells, int ngenes, double *row_sums, double *col_sums)
-{
-    return guarded([&] {
-        if (nnz < 0 || ncells < 0 || ngenes < 0) throw std::invalid_argument("negative size");
-        if (kind < SCHPF_VAL_I32 || kind > SCHPF_VAL_F64) throw std::invalid_argument("unknown value kind");
-        // per-thread partial sums over contiguous slabs, added up in thread order: exact for counts
-        // (integers far below 2^53) and run-to-run deterministic for anything else
-        const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(schpf::host_threads(), 16), nnz / 65536 + 1));
-        std::vector<std::vector<double>> pr((size_t)nth), pc((size_t)nth);
-        std::vector<int64_t> bad((size_t)nth, -1);
-        std::vector<std::thread> th;
-        for (int t = 0; t < nth; ++t)
-            th.emplace_back([&, t] {
-                pr[(size_t)t].assign((size_t)ncells, 0.0);
-                pc[(size_t)t].assign((size_t)ngenes, 0.0);
-                double *r = pr[(size_t)t].data(), *g = pc[(size_t)t].data();
-                const int64_t b = nnz * t / nth, e = nnz * (t + 1) / nth;
-                for (int64_t i = b; i < e; ++i) {
-                    if (row[i] < 0 || row[i] >= ncells || col[i] < 0 || col[i] >= ngenes) {
-                        if (bad[(size_t)t] < 0) bad[(size_t)t] = i;
-                        continue;
-                    }
-                    double d;
-                    switch (kind) {
-                    case SCHPF_VAL_I32: d = (double)((const int32_t *)val)[i]; break;
-                    case SCHPF_VAL_I64: d = (double)((const int64_t *)val)[i]; break;
-                    case SCHPF_VAL_F32: d = (double)((const float *)val)[i]; break;
-                    default: d = ((const double *)val)[i]; break;
-                    }
-                    r[row[i]] += d;
-                    g[col[i]] += d;
-                }
-            });
-        for (auto &x : th) x.join();
-        for (int t = 0; t < nth; ++t)
-            if (bad[(size_t)t] >= 0)
-                throw std::invalid_argument("COO index out of range at entry " + std::to_string(bad[(size_t)t]));
-        for (int i = 0; i < ncells; ++i) { double s = 0.0; for (int t = 0; t < nth; ++t) s += pr[(size_t)t][(size_t)i]; row_sums[i] = s; }
-        for (int i = 0; i < ngenes; ++i) { double s = 0.0; for (int t = 0; t < nth; ++t) s += pc[(size_t)t][(size_t)i]; col_sums[i] = s; }
-    });
-}
-
-int schpf_debug_plan_expand(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val,
-                            int n_major, int n_minor, int lpc, int chunk_len, int n_windows,
-                            int32_t *out_major, int32_t *out_minor, float *out_val, int32_t *out_natid,
-                            int32_t *out_wave, int32_t *out_cptr, int64_t stats[4])
-{
-    return guarded([&] {
-        schpf::SweepPlanHost P;
-        schpf::build_sweep_plan(nnz, major, minor, val, n_major, n_minor, lpc, chunk_len, n_windows, false, P);
-        std::vector<int32_t> wave_of_slice((size_t)P.n_slices, -1);
-        for (int64_t w = 0; w < P.n_waves; ++w)
-            if (P.wave_slice[(size_t)w] >= 0) {
-                if (wave_of_slice[(size_t)P.wave_slice[(size_t)w]] != -1)
-                    throw std::logic_error("slice scheduled twice");
-                wave_of_slice[(size_t)P.wave_slice[(size_t)w]] = (int32_t)w;
-            }
-        int64_t n = 0;
-        for (int64_t s = 0; s < P.n_slices; ++s) {
-            if (wave_of_slice[(size_t)s] < 0) throw std::logic_error("slice never scheduled");
-            const uint32_t *base = P.entries.data() + (size_t)P.slice_off[(size_t)s] * 4;
-            for (int step = 0; step < P.slice_steps[(size_t)s]; ++step)
-                for (int slot = 0; slot < P.cpw; ++slot)
-                    for (int u = 0; u < 2; ++u) {
-                        const uint32_t *e = base + ((size_t)step * P.cpw + slot) * 4 + (size_t)u * 2;
-                        float f;
-                        std::memcpy(&f, &e[1], 4);
-                        if (f == 0.0f) continue;
-                        if (n >= nnz) throw std::logic_error("plan stores more nonzeros than given");
-                        out_major[n] = P.chunk_major[(size_t)s * P.cpw + slot];
-                        out_minor[n] = (int32_t)e[0];
-                        out_val[n] = f;
-                        out_natid[n] = P.chunk_natid[(size_t)s * P.cpw + slot];
-                        out_wave[n] = wave_of_slice[(size_t)s];
-                        ++n;
-                    }
-        }
-        if (n != nnz) throw std::logic_error("plan lost nonzeros");
-        for (int m = 0; m <= n_major; ++m) out_cptr[m] = P.cptr[(size_t)m];
-        stats[0] = P.n_chunks; stats[1] = P.n_slices; stats[2] = P.n_waves;
-        stats[3] = (int64_t)P.entries.size() / 2;
-    });
-}
-
-
-int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val,
-                            int n_major, int n_minor, int lpc, int waves_per_block, int win_rows,
-                            int target_tasks, int ring, int slot_bytes, int32_t *out_major, int32_t *out_minor,
-                            float *out_val, int32_t *out_prow, int32_t *out_task, int32_t *out_pfirst,
-                            int32_t *out_pcount, int64_t stats[8])
-{
-    return guarded([&] {
-        const schpf::Tuning tn = schpf::tuning_from_env();   // per call: tests change the switches between calls
-        schpf::TilePlanHost P;
-        schpf::TileShape sh;
-        sh.lpc = lpc; sh.waves_per_block = waves_per_block; sh.win_rows = win_rows; sh.target_tasks = target_tasks;
-        sh.row_slots = tn.debug_row_slots;   // 160-byte table rows
-        sh.ring = ring < 0 ? -ring : ring; sh.sync_stage = sh.ring > 1 ? 1 : 0; sh.slot_bytes = slot_bytes;
-        // SCHPF_DEBUG_SINGLE=1: steps count nonzeros (plan.h; window schedule only)
-        sh.single = tn.debug_single && sh.ring <= 1;
-        sh.bank_order = tn.bank_order;
-        sh.taper = tn.taper.value_or(0) / 100.0;
-        sh.verbose = tn.verbose;
-        if (sh.taper > 0.0) sh.slots = 1;   // tapered ranges are for orientations with more tasks than workgroups (plan.h)
-        // SCHPF_DEBUG_BALANCE=1: balanced windows (plan.h) -- the plan is built on the blocks' virtual numbering of the
-        // minor rows and every entry is mapped back through minor_of
-        std::vector<int32_t> minor_of;
-        schpf::BalanceGeometry geo;
-        const bool balanced = tn.debug_balance && sh.ring <= 1;
-        if (balanced) {
-            schpf::BigVec<int32_t> vminor;
-            schpf::balance_windows_host(nnz, major, minor, n_major, n_minor, sh, vminor, minor_of, geo);
-            schpf::build_tile_plan(nnz, major, vminor.data(), val, n_major, geo.n_virtual, sh, false, P);
-        } else
-        schpf::build_tile_plan(nnz, major, minor, val, n_major, n_minor, sh, false, P);
-        const int W = P.n_windows, gpw = P.gpw, wpb = P.wpb, gpb = P.gpb;
-        // the LDS model of plan.cpp::bank_order: the lane groups of a pass read one row each per half step; rows of
-        // one class (16-byte position mod 16, / lpc) are served one after the other
-        const std::vector<int> pass_of = schpf::tile_pass_of(lpc, gpw);
-        const int n_classes = std::max(1, 16 / std::max(1, lpc));
-        int lpc_shift = 0;
-        while ((1 << lpc_shift) < lpc) ++lpc_shift;
-        int64_t lds_reads = 0, lds_extra = 0;
-        int64_t n = 0;
-        for (int64_t t = 0; t < P.n_tasks; ++t) {
-            const int b = P.task_block[(size_t)t];
-            for (int v = 0; v < wpb; ++v) {
-                int64_t off = P.task_wave_off[(size_t)t * wpb + v];
-                for (int w = P.task_w0[(size_t)t]; w < P.task_w1[(size_t)t]; ++w) {
-                    const int steps = P.steps[((size_t)b * wpb + v) * W + w];
-                    // the kernel's walk: `single` plans execute `steps` nonzeros (the slot halves 0 .. steps - 1)
-                    const int n_half = P.single ? steps : 2 * steps;
-                    for (int p = 0; 2 * p < n_half; ++p)
-                        for (int u = 0; u < 2 && 2 * p + u < n_half; ++u) {
-                          int in_class[4][16] = {};
-                          for (int grp = 0; grp < gpw; ++grp) {
-                                float f;
-                                uint32_t off16;
-                                if (P.packed) {
-                                    const uint32_t *e = P.entries.data() + ((size_t)off + (size_t)p * gpw + grp) * 2;
-                                    off16 = (e[0] >> (16 * u)) & 0xFFFFu;
-                                    f = (float)((e[1] >> (16 * u)) & 0xFFFFu);
-                                } else {
-                                    const uint32_t *e = P.entries.data() + ((size_t)off + (size_t)p * gpw + grp) * 4 + (size_t)u * 2;
-                                    off16 = e[0];
-                                    std::memcpy(&f, &e[1], 4);
-                                }
-                                int mn;   // the kernel's reconstruction (sweep_impl.h entry_minor)
-                                if (P.ring > 1) {
-                                    const int slot = (int)(off16 / (uint32_t)P.slot16);
-                                    const int r = (int)((off16 - (uint32_t)slot * P.slot16) / (uint32_t)P.row_slots);
-                                    const int ahead = (slot - w % P.ring + P.ring) % P.ring;
-                                    // readable in epoch w: sub-windows w .. w + look, inside the task
-                                    if (slot >= P.ring || ahead > P.look || w + ahead >= P.task_w1[(size_t)t])
-                                        throw std::logic_error("ring plan: an entry points outside the readable slots");
-                                    if (f == 0.0f && off16 != (uint32_t)(w % P.ring) * (uint32_t)P.slot16)
-                                        throw std::logic_error("ring plan: padding must point at the epoch's own slot");
-                                    mn = (w + ahead) * P.win_rows + r;
-                                } else {
-                                    mn = w * P.win_rows + (int)(off16 / (uint32_t)P.row_slots);
-                                }
-                                if (f == 0.0f) continue;
-                                in_class[pass_of[(size_t)grp]][((off16 & 15u) >> lpc_shift) & (unsigned)(n_classes - 1)]++;
-                                if (schpf::tile_off16(P, mn) != off16) throw std::logic_error("tile plan: bad LDS position");
-                                if (n >= nnz) throw std::logic_error("tile plan stores more nonzeros than given");
-                                const int g = v * gpw + grp;
-                                out_major[n] = P.block_rows[(size_t)b * gpb + g];
-                                out_minor[n] = balanced ? minor_of[(size_t)b * geo.n_virtual + (size_t)mn] : (int32_t)mn;
-                                out_val[n] = f;
-                                out_prow[n] = (int32_t)(t * gpb + g);
-                                out_task[n] = (int32_t)t;
-                                ++n;
-                          }
-                          for (int ps = 0; ps < 4; ++ps) {
-                              int worst = 0;
-                              for (int c = 0; c < 16; ++c) worst = std::max(worst, in_class[ps][c]);
-                              if (worst) { lds_reads++; lds_extra += worst - 1; }
-                          }
-                        }
-                    off += schpf::tile_stored_steps(P, steps) * gpw;
-                }
-            }
-        }
-        if (n != nnz) throw std::logic_error("tile plan lost nonzeros");
-        for (int m = 0; m < n_major; ++m) { out_pfirst[m] = P.pfirst[(size_t)m]; out_pcount[m] = P.pcount[(size_t)m]; }
-        stats[0] = P.n_tasks; stats[1] = P.n_blocks; stats[2] = P.n_windows; stats[3] = P.pstride;
-        stats[4] = (int64_t)P.entries.size() / (P.packed ? 1 : 2); stats[5] = P.windows_per_task;
-        stats[6] = lds_reads; stats[7] = lds_extra;
-    });
-}
-
 }  // extern "C"

@@ -1,0 +1,166 @@
+// What every translation unit behind the C ABI shares: the per-thread error string of schpf_last_error, the exception ->
+// status mapping of an entry point (guarded), and the RAII device buffer with its small copy helpers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/schpf_hip.h"
+#include "plan.h"
+
+namespace schpf {
+
+extern thread_local std::string g_err;   // one per thread for ALL entry points; defined in capi.hip (schpf_last_error)
+
+inline int fail(const char *fmt, ...)
+{
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return 1;
+}
+
+struct HipError : std::runtime_error {
+    hipError_t code;
+    HipError(const std::string &what, hipError_t code_ = hipErrorUnknown) : std::runtime_error(what), code(code_) {}
+};
+
+#define HIPCHK(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            char b_[512];                                                                    \
+            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
+                     __FILE__, __LINE__);                                                    \
+            throw schpf::HipError(b_, e_);                                                   \
+        }                                                                                    \
+    } while (0)
+
+template <typename F> int guarded(F &&f)
+{
+    // status SCHPF_ERR_NO_MEMORY: the device (hipErrorOutOfMemory) or the host (std::bad_alloc while building plans) ran
+    // out of memory -- the one failure a caller may answer with a smaller layout; everything else is 1
+    try {
+        f();
+        return 0;
+    } catch (const HipError &e) {
+        g_err = e.what();
+        if (e.code == hipErrorOutOfMemory) (void)hipGetLastError();
+        return e.code == hipErrorOutOfMemory ? SCHPF_ERR_NO_MEMORY : 1;
+    } catch (const DeviceNoMemory &e) {
+        g_err = e.what();
+        return SCHPF_ERR_NO_MEMORY;
+    } catch (const std::bad_alloc &) {
+        g_err = "out of host memory (std::bad_alloc)";
+        return SCHPF_ERR_NO_MEMORY;
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return 1;
+    } catch (...) {
+        g_err = "unknown error";
+        return 1;
+    }
+}
+
+inline bool bad_dtype(int dtype) { return dtype != SCHPF_F32 && dtype != SCHPF_F64; }
+
+// entry i of a caller's value array of kind SCHPF_VAL_*
+inline double read_count(const void *val, int kind, int64_t i)
+{
+    switch (kind) {
+    case SCHPF_VAL_I32: return (double)((const int32_t *)val)[i];
+    case SCHPF_VAL_I64: return (double)((const int64_t *)val)[i];
+    case SCHPF_VAL_F32: return (double)((const float *)val)[i];
+    default: return ((const double *)val)[i];
+    }
+}
+
+// RAII device buffer
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { adopt(o.p, o.bytes); o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    // takes ownership of a hipMalloc'ed pointer (plan_device.hip hands its results over as void *)
+    void adopt(void *p_, size_t bytes_)
+    {
+        release();
+        p = p_;
+        bytes = bytes_;
+    }
+    void alloc(size_t n, bool zero = false, hipStream_t st = nullptr)
+    {
+        release();
+        bytes = n ? n : 16;
+        HIPCHK(hipMalloc(&p, bytes));
+        if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, st));
+    }
+    template <typename U> U *as() const { return reinterpret_cast<U *>(p); }
+};
+
+template <typename U, typename A> void upload(DevBuf &b, const std::vector<U, A> &v, hipStream_t st)
+{
+    b.alloc(v.size() * sizeof(U));
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, st));
+}
+
+template <typename U> void h2d(DevBuf &b, const void *src, size_t count, hipStream_t st)
+{
+    b.alloc(count * sizeof(U));
+    if (count) HIPCHK(hipMemcpyAsync(b.p, src, count * sizeof(U), hipMemcpyHostToDevice, st));
+}
+inline void d2h(void *dst, const DevBuf &b, size_t bytes, hipStream_t st)
+{
+    if (bytes) HIPCHK(hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+}
+
+struct TempStream {
+    hipStream_t st = nullptr;
+    TempStream() { HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); }
+    ~TempStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+};
+
+// f(1, st) on a helper thread -- bound to `device`; st is a stream of its own, drained before the thread ends, where
+// the caller asks for one, else nullptr -- while f(0, mine) runs here.  Joins; the caller's own exception goes first,
+// else the helper's is rethrown
+template <typename F> void on_both_sides(int device, hipStream_t mine, bool own_stream, F &&f)
+{
+    std::exception_ptr err;
+    std::thread helper([&] {
+        try {
+            HIPCHK(hipSetDevice(device));
+            if (!own_stream) { f(1, (hipStream_t) nullptr); return; }
+            TempStream ts;
+            f(1, ts.st);
+            HIPCHK(hipStreamSynchronize(ts.st));
+        } catch (...) { err = std::current_exception(); }
+    });
+    try { f(0, mine); } catch (...) { helper.join(); throw; }
+    helper.join();
+    if (err) std::rethrow_exception(err);
+}
+
+}  // namespace schpf

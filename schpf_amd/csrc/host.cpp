@@ -1,0 +1,237 @@
+// Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
+// check the host builders with, and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
+#include <execinfo.h>
+#include <signal.h>
+#include <unistd.h>
+
+#include <cstring>
+#include <thread>
+
+#include "common.h"
+#include "policy.h"
+
+using namespace schpf;
+
+// SCHPF_BACKTRACE=1 (debugging aid, read when the library is loaded): a SIGSEGV / SIGBUS / SIGABRT prints the native call
+// stack (glibc backtrace: module + offset per frame, resolvable with addr2line against this .so) before the previous
+// handler -- Python's faulthandler under pytest -- runs.  The GPU boxes have no debugger.
+namespace {
+struct sigaction g_prev_segv, g_prev_bus, g_prev_abrt;
+void crash_trace(int sig, siginfo_t *info, void *uctx)
+{
+    void *frames[64];
+    const int n = backtrace(frames, 64);
+    const char msg[] = "[schpf_hip] fatal signal, native stack:\n";
+    (void)!write(2, msg, sizeof msg - 1);
+    backtrace_symbols_fd(frames, n, 2);
+    struct sigaction *prev = sig == SIGSEGV ? &g_prev_segv : sig == SIGBUS ? &g_prev_bus : &g_prev_abrt;
+    sigaction(sig, prev, nullptr);          // hand over: the previous handler (or the default action) sees the re-raised signal
+    raise(sig);
+    (void)info; (void)uctx;
+}
+struct CrashTraceInstaller {
+    CrashTraceInstaller()
+    {
+        const char *e = getenv("SCHPF_BACKTRACE");
+        if (!e || !*e || *e == '0') return;
+        void *frame[1];
+        (void)backtrace(frame, 1);   // the first call loads libgcc and allocates: here, not inside a signal handler
+        struct sigaction sa;
+        std::memset(&sa, 0, sizeof sa);
+        sa.sa_sigaction = crash_trace;
+        sa.sa_flags = SA_SIGINFO | SA_ONSTACK;
+        sigaction(SIGSEGV, &sa, &g_prev_segv);
+        sigaction(SIGBUS, &sa, &g_prev_bus);
+        sigaction(SIGABRT, &sa, &g_prev_abrt);
+    }
+} g_crash_trace_installer;
+}  // namespace
+
+extern "C" {
+
+int schpf_coo_marginals(int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int kind,
+                        int ncells, int ngenes, double *row_sums, double *col_sums)
+{
+    return guarded([&] {
+        if (nnz < 0 || ncells < 0 || ngenes < 0) throw std::invalid_argument("negative size");
+        if (kind < SCHPF_VAL_I32 || kind > SCHPF_VAL_F64) throw std::invalid_argument("unknown value kind");
+        // per-thread partial sums over contiguous slabs, added up in thread order: exact for counts
+        // (integers far below 2^53) and run-to-run deterministic for anything else
+        const int nth = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(schpf::host_threads(), 16), nnz / 65536 + 1));
+        std::vector<std::vector<double>> pr((size_t)nth), pc((size_t)nth);
+        std::vector<int64_t> bad((size_t)nth, -1);
+        std::vector<std::thread> th;
+        for (int t = 0; t < nth; ++t)
+            th.emplace_back([&, t] {
+                pr[(size_t)t].assign((size_t)ncells, 0.0);
+                pc[(size_t)t].assign((size_t)ngenes, 0.0);
+                double *r = pr[(size_t)t].data(), *g = pc[(size_t)t].data();
+                const int64_t b = nnz * t / nth, e = nnz * (t + 1) / nth;
+                for (int64_t i = b; i < e; ++i) {
+                    if (row[i] < 0 || row[i] >= ncells || col[i] < 0 || col[i] >= ngenes) {
+                        if (bad[(size_t)t] < 0) bad[(size_t)t] = i;
+                        continue;
+                    }
+                    const double d = read_count(val, kind, i);
+                    r[row[i]] += d;
+                    g[col[i]] += d;
+                }
+            });
+        for (auto &x : th) x.join();
+        for (int t = 0; t < nth; ++t)
+            if (bad[(size_t)t] >= 0)
+                throw std::invalid_argument("COO index out of range at entry " + std::to_string(bad[(size_t)t]));
+        for (int i = 0; i < ncells; ++i) { double s = 0.0; for (int t = 0; t < nth; ++t) s += pr[(size_t)t][(size_t)i]; row_sums[i] = s; }
+        for (int i = 0; i < ngenes; ++i) { double s = 0.0; for (int t = 0; t < nth; ++t) s += pc[(size_t)t][(size_t)i]; col_sums[i] = s; }
+    });
+}
+
+int schpf_debug_plan_expand(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val,
+                            int n_major, int n_minor, int lpc, int chunk_len, int n_windows,
+                            int32_t *out_major, int32_t *out_minor, float *out_val, int32_t *out_natid,
+                            int32_t *out_wave, int32_t *out_cptr, int64_t stats[4])
+{
+    return guarded([&] {
+        schpf::SweepPlanHost P;
+        schpf::build_sweep_plan(nnz, major, minor, val, n_major, n_minor, lpc, chunk_len, n_windows, false, P);
+        std::vector<int32_t> wave_of_slice((size_t)P.n_slices, -1);
+        for (int64_t w = 0; w < P.n_waves; ++w)
+            if (P.wave_slice[(size_t)w] >= 0) {
+                if (wave_of_slice[(size_t)P.wave_slice[(size_t)w]] != -1)
+                    throw std::logic_error("slice scheduled twice");
+                wave_of_slice[(size_t)P.wave_slice[(size_t)w]] = (int32_t)w;
+            }
+        int64_t n = 0;
+        for (int64_t s = 0; s < P.n_slices; ++s) {
+            if (wave_of_slice[(size_t)s] < 0) throw std::logic_error("slice never scheduled");
+            const uint32_t *base = P.entries.data() + (size_t)P.slice_off[(size_t)s] * 4;
+            for (int step = 0; step < P.slice_steps[(size_t)s]; ++step)
+                for (int slot = 0; slot < P.cpw; ++slot)
+                    for (int u = 0; u < 2; ++u) {
+                        const uint32_t *e = base + ((size_t)step * P.cpw + slot) * 4 + (size_t)u * 2;
+                        float f;
+                        std::memcpy(&f, &e[1], 4);
+                        if (f == 0.0f) continue;
+                        if (n >= nnz) throw std::logic_error("plan stores more nonzeros than given");
+                        out_major[n] = P.chunk_major[(size_t)s * P.cpw + slot];
+                        out_minor[n] = (int32_t)e[0];
+                        out_val[n] = f;
+                        out_natid[n] = P.chunk_natid[(size_t)s * P.cpw + slot];
+                        out_wave[n] = wave_of_slice[(size_t)s];
+                        ++n;
+                    }
+        }
+        if (n != nnz) throw std::logic_error("plan lost nonzeros");
+        for (int m = 0; m <= n_major; ++m) out_cptr[m] = P.cptr[(size_t)m];
+        stats[0] = P.n_chunks; stats[1] = P.n_slices; stats[2] = P.n_waves;
+        stats[3] = (int64_t)P.entries.size() / 2;
+    });
+}
+
+int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val,
+                            int n_major, int n_minor, int lpc, int waves_per_block, int win_rows,
+                            int target_tasks, int ring, int slot_bytes, int32_t *out_major, int32_t *out_minor,
+                            float *out_val, int32_t *out_prow, int32_t *out_task, int32_t *out_pfirst,
+                            int32_t *out_pcount, int64_t stats[8])
+{
+    return guarded([&] {
+        const schpf::Tuning tn = schpf::tuning_from_env();   // per call: tests change the switches between calls
+        schpf::TilePlanHost P;
+        schpf::TileShape sh;
+        sh.lpc = lpc; sh.waves_per_block = waves_per_block; sh.win_rows = win_rows; sh.target_tasks = target_tasks;
+        sh.row_slots = tn.debug_row_slots;   // 160-byte table rows
+        sh.ring = ring < 0 ? -ring : ring; sh.sync_stage = sh.ring > 1 ? 1 : 0; sh.slot_bytes = slot_bytes;
+        // SCHPF_DEBUG_SINGLE=1: steps count nonzeros (plan.h; window schedule only)
+        sh.single = tn.debug_single && sh.ring <= 1;
+        sh.bank_order = tn.bank_order;
+        sh.taper = tn.taper.value_or(0) / 100.0;
+        sh.verbose = tn.verbose;
+        if (sh.taper > 0.0) sh.slots = 1;   // tapered ranges are for orientations with more tasks than workgroups (plan.h)
+        // SCHPF_DEBUG_BALANCE=1: balanced windows (plan.h) -- the plan is built on the blocks' virtual numbering of the
+        // minor rows and every entry is mapped back through minor_of
+        std::vector<int32_t> minor_of;
+        schpf::BalanceGeometry geo;
+        const bool balanced = tn.debug_balance && sh.ring <= 1;
+        if (balanced) {
+            schpf::BigVec<int32_t> vminor;
+            schpf::balance_windows_host(nnz, major, minor, n_major, n_minor, sh, vminor, minor_of, geo);
+            schpf::build_tile_plan(nnz, major, vminor.data(), val, n_major, geo.n_virtual, sh, false, P);
+        } else
+        schpf::build_tile_plan(nnz, major, minor, val, n_major, n_minor, sh, false, P);
+        const int W = P.n_windows, gpw = P.gpw, wpb = P.wpb, gpb = P.gpb;
+        // the LDS model of plan.cpp::bank_order: the lane groups of a pass read one row each per half step; rows of
+        // one class (16-byte position mod 16, / lpc) are served one after the other
+        const std::vector<int> pass_of = schpf::tile_pass_of(lpc, gpw);
+        const int n_classes = std::max(1, 16 / std::max(1, lpc));
+        int lpc_shift = 0;
+        while ((1 << lpc_shift) < lpc) ++lpc_shift;
+        int64_t lds_reads = 0, lds_extra = 0;
+        int64_t n = 0;
+        for (int64_t t = 0; t < P.n_tasks; ++t) {
+            const int b = P.task_block[(size_t)t];
+            for (int v = 0; v < wpb; ++v) {
+                int64_t off = P.task_wave_off[(size_t)t * wpb + v];
+                for (int w = P.task_w0[(size_t)t]; w < P.task_w1[(size_t)t]; ++w) {
+                    const int steps = P.steps[((size_t)b * wpb + v) * W + w];
+                    // the kernel's walk: `single` plans execute `steps` nonzeros (the slot halves 0 .. steps - 1)
+                    const int n_half = P.single ? steps : 2 * steps;
+                    for (int p = 0; 2 * p < n_half; ++p)
+                        for (int u = 0; u < 2 && 2 * p + u < n_half; ++u) {
+                          int in_class[4][16] = {};
+                          for (int grp = 0; grp < gpw; ++grp) {
+                                float f;
+                                uint32_t off16;
+                                if (P.packed) {
+                                    const uint32_t *e = P.entries.data() + ((size_t)off + (size_t)p * gpw + grp) * 2;
+                                    off16 = (e[0] >> (16 * u)) & 0xFFFFu;
+                                    f = (float)((e[1] >> (16 * u)) & 0xFFFFu);
+                                } else {
+                                    const uint32_t *e = P.entries.data() + ((size_t)off + (size_t)p * gpw + grp) * 4 + (size_t)u * 2;
+                                    off16 = e[0];
+                                    std::memcpy(&f, &e[1], 4);
+                                }
+                                int mn;   // the kernel's reconstruction (sweep_impl.h entry_minor)
+                                if (P.ring > 1) {
+                                    const int slot = (int)(off16 / (uint32_t)P.slot16);
+                                    const int r = (int)((off16 - (uint32_t)slot * P.slot16) / (uint32_t)P.row_slots);
+                                    const int ahead = (slot - w % P.ring + P.ring) % P.ring;
+                                    // readable in epoch w: sub-windows w .. w + look, inside the task
+                                    if (slot >= P.ring || ahead > P.look || w + ahead >= P.task_w1[(size_t)t])
+                                        throw std::logic_error("ring plan: an entry points outside the readable slots");
+                                    if (f == 0.0f && off16 != (uint32_t)(w % P.ring) * (uint32_t)P.slot16)
+                                        throw std::logic_error("ring plan: padding must point at the epoch's own slot");
+                                    mn = (w + ahead) * P.win_rows + r;
+                                } else {
+                                    mn = w * P.win_rows + (int)(off16 / (uint32_t)P.row_slots);
+                                }
+                                if (f == 0.0f) continue;
+                                in_class[pass_of[(size_t)grp]][((off16 & 15u) >> lpc_shift) & (unsigned)(n_classes - 1)]++;
+                                if (schpf::tile_off16(P, mn) != off16) throw std::logic_error("tile plan: bad LDS position");
+                                if (n >= nnz) throw std::logic_error("tile plan stores more nonzeros than given");
+                                const int g = v * gpw + grp;
+                                out_major[n] = P.block_rows[(size_t)b * gpb + g];
+                                out_minor[n] = balanced ? minor_of[(size_t)b * geo.n_virtual + (size_t)mn] : (int32_t)mn;
+                                out_val[n] = f;
+                                out_prow[n] = (int32_t)(t * gpb + g);
+                                out_task[n] = (int32_t)t;
+                                ++n;
+                          }
+                          for (int ps = 0; ps < 4; ++ps) {
+                              int worst = 0;
+                              for (int c = 0; c < 16; ++c) worst = std::max(worst, in_class[ps][c]);
+                              if (worst) { lds_reads++; lds_extra += worst - 1; }
+                          }
+                        }
+                    off += schpf::tile_stored_steps(P, steps) * gpw;
+                }
+            }
+        }
+        if (n != nnz) throw std::logic_error("tile plan lost nonzeros");
+        for (int m = 0; m < n_major; ++m) { out_pfirst[m] = P.pfirst[(size_t)m]; out_pcount[m] = P.pcount[(size_t)m]; }
+        stats[0] = P.n_tasks; stats[1] = P.n_blocks; stats[2] = P.n_windows; stats[3] = P.pstride;
+        stats[4] = (int64_t)P.entries.size() / (P.packed ? 1 : 2); stats[5] = P.windows_per_task;
+        stats[6] = lds_reads; stats[7] = lds_extra;
+    });
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // Planning policy of an engine: which plan kind, row layout, workgroup shape, task ranges and loss-pass cut a matrix
 // gets, and every environment switch the planner and the launches consult.  Host-only decisions: the
-// engine (capi.hip) holds the device state and carries them out.
+// engine (capi.hip) holds the device state and carries them out.  A Problem is made per question: during an upload
+// from the engine and that upload's record (Engine::problem(UploadJob)), afterwards from the engine alone.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -45,8 +46,8 @@ struct Problem {
     bool expect_sharded = false;        // schpf_hint_sharded
     bool transient = false;             // schpf_hint_transient
     bool want_rows = false;             // schpf_keep_rows
-    bool planning_batch_rows = false;   // inside schpf_upload_rows
-    bool balance_now = false;           // balanced windows for this upload (balance_windows)
+    bool planning_batch_rows = false;   // this upload is schpf_upload_rows' (UploadJob::batch_rows); unset after it
+    bool balance_now = false;           // balanced windows for this upload (balance_windows); unset after it
 };
 
 struct Config { bool tile; int LPC, NV, KL, KP; };

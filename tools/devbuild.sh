@@ -10,13 +10,13 @@ mkdir -p $D
 for f in sweep_f64 sweep_f32; do
   /opt/rocm/bin/hipcc $FLAGS -DSCHPF_DEV_FAST $DEVFLAGS -c $f.hip -o $D/$f.o &
 done
-for f in kernels capi plan_device; do
-  if [ ! -f /tmp/schpf_dev_common/$f.o ] || [ $f.hip -nt /tmp/schpf_dev_common/$f.o ] || [ plan.h -nt /tmp/schpf_dev_common/$f.o ] || [ policy.h -nt /tmp/schpf_dev_common/$f.o ] || [ kernels.h -nt /tmp/schpf_dev_common/$f.o ]; then
+for f in kernels capi ops plan_device; do
+  if [ ! -f /tmp/schpf_dev_common/$f.o ] || [ $f.hip -nt /tmp/schpf_dev_common/$f.o ] || [ plan.h -nt /tmp/schpf_dev_common/$f.o ] || [ policy.h -nt /tmp/schpf_dev_common/$f.o ] || [ kernels.h -nt /tmp/schpf_dev_common/$f.o ] || [ common.h -nt /tmp/schpf_dev_common/$f.o ]; then
     mkdir -p /tmp/schpf_dev_common
     /opt/rocm/bin/hipcc $FLAGS -c $f.hip -o /tmp/schpf_dev_common/$f.o &
   fi
 done
-for f in plan policy; do
+for f in plan policy host; do
   if [ ! -f /tmp/schpf_dev_common/$f.o ] || [ $f.cpp -nt /tmp/schpf_dev_common/$f.o ] || [ plan.h -nt /tmp/schpf_dev_common/$f.o ] || [ policy.h -nt /tmp/schpf_dev_common/$f.o ]; then
     mkdir -p /tmp/schpf_dev_common
     /opt/rocm/bin/hipcc $FLAGS -x hip -c $f.cpp -o /tmp/schpf_dev_common/$f.o &
