@@ -180,6 +180,17 @@ int schpf_loss_terms(schpf_ctx *ctx, double *llh_sum, double *gammaln_sum, int64
  * A batch engine (schpf_upload_rows) fails, as schpf_loss_terms does.  Definition: DESIGN.md 11. */
 int schpf_elbo_terms(schpf_ctx *ctx, double ap, double cp, double terms[5]);
 
+#define SCHPF_BY_CELL 0
+#define SCHPF_BY_GENE 1
+/* Per major row m of the chosen axis, over the LOCAL stored entries (duplicates are separate observations, stored
+ * zeros count): llh_sum[m] = sum x log r - r, gammaln_sum[m] = sum lgamma(x+1), count[m] = stored entries.
+ * Mean negative llh of row m = -(llh_sum[m] - gammaln_sum[m]) / count[m].  Host arrays of ncells (local) / ngenes.
+ * Sweeps the plan whose major axis is `by`, reads the state only, no atomics: two calls on one state return the
+ * same bits.  Its scratch is allocated by the first call (SCHPF_ERR_NO_MEMORY if that fails) and released by the next
+ * upload.  A shard: concatenate the cells' arrays over the ranks, sum the genes'.  A batch engine
+ * (schpf_upload_rows) fails, as schpf_loss_terms does.  Definition: DESIGN.md 12. */
+int schpf_loss_rows(schpf_ctx *ctx, int by, double *llh_sum, double *gammaln_sum, int64_t *count);
+
 int schpf_synchronize(schpf_ctx *ctx);
 
 /* Cells sharded over the GPUs of a node, the collective inside the library (RCCL over xGMI, bound

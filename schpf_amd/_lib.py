@@ -15,6 +15,7 @@ XI, THETA, ETA, BETA = 0, 1, 2, 3
 VAL_I32, VAL_I64, VAL_F32, VAL_F64 = 0, 1, 2, 3
 STREAM_DEFAULT = 1   # SCHPF_STREAM_DEFAULT: the device's null stream
 FREEZE_GENES, SIMULTANEOUS, SHARDED, CELLS_FIRST, LOCAL_GENE, LOCAL_CELL = 1, 2, 4, 8, 16, 32
+BY_CELL, BY_GENE = 0, 1   # SCHPF_BY_CELL / SCHPF_BY_GENE: the axis of schpf_loss_rows
 
 _vp = ctypes.c_void_p
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -49,6 +50,7 @@ SIGNATURES = {
     "schpf_step_finish": [_vp, ctypes.c_uint],
     "schpf_loss_terms": [_vp, _dblp, _dblp, _i64p],
     "schpf_elbo_terms": [_vp, _dbl, _dbl, _dblp],
+    "schpf_loss_rows": [_vp, _int, _dblp, _dblp, _i64p],
     "schpf_synchronize": [_vp],
     "schpf_hint_sharded": [_vp, _int],
     "schpf_hint_transient": [_vp, _int],

@@ -112,6 +112,9 @@ def _parser():
     score.add_argument("-p", "--prefix", default="", help="Prefix for output files.")
     score.add_argument("-g", "--genefile", default=None,
                        help="Tab-delimited gene table without header (prep's genes.txt): also write ranked genes.")
+    score.add_argument("-i", "--input", default=None,
+                       help="The count matrix the model was fitted to (same formats as `train -i`): also write the mean "
+                            "negative log-likelihood of each cell and each gene (cell_loss.txt, gene_loss.txt).")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -260,6 +263,18 @@ def _score(args, outprefix):
         ranks = np.argsort(gene_score, axis=0)[::-1]
         ranked = np.stack([genes[ranks[:, k], name_col] for k in range(gene_score.shape[1])]).T
         np.savetxt(outprefix + "ranked_genes.txt", ranked, fmt="%s", delimiter="\t")
+    if args.input is not None:
+        from . import loss as ls
+        print("Loading data.....")
+        data = _load_matrix(args.input)
+        if tuple(data.shape) != (model.theta.dims[0], model.beta.dims[0]):
+            raise ValueError("{} is {} x {}, the model was fitted to {} cells x {} genes".format(
+                args.input, data.shape[0], data.shape[1], model.theta.dims[0], model.beta.dims[0]))
+        print("Saving per-cell and per-gene loss.....")
+        np.savetxt(outprefix + "cell_loss.txt", ls.cellmean_negative_pois_llh(data, theta=model.theta, beta=model.beta))
+        np.savetxt(outprefix + "gene_loss.txt", ls.genemean_negative_pois_llh(data, theta=model.theta, beta=model.beta))
+    else:
+        del args.input   # the arguments file of a run without the matrix stays what it was
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

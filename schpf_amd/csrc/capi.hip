@@ -1,5 +1,6 @@
 // C ABI of libschpf_hip.so (include/schpf_hip.h): context management, uploads, and the
 // ordering of kernel launches that makes one CAVI iteration (scHPF_.py:657-714).
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -157,6 +158,7 @@ struct schpf_ctx {
     virtual void exchange(void **p, int64_t *count) = 0;
     virtual void loss_terms(double *llh, double *gl, int64_t *nnz) = 0;
     virtual void elbo_terms(double ap, double cp, double terms[5]) = 0;
+    virtual void loss_rows(int by, double *llh, double *gl, int64_t *count) = 0;
     virtual void plan_info(int64_t info[16]) = 0;
     virtual void upload_info(int64_t info[4]) = 0;
     virtual void profile_clock(double *shader_mhz, int64_t *launches) = 0;
@@ -206,6 +208,12 @@ template <typename T> struct Engine final : schpf_ctx {
     int64_t n_rounded = 0, n_zero = 0;              // upload facts: values rounded to float32; stored zeros
     DevBuf zero_row, zero_col;                      // positions of explicitly stored zeros (loss only)
     DevBuf elbo_part, elbo_sums;                    // ELBO: Gamma-term block partials, their sums (elbo_terms)
+    // Per-row loss (loss_rows): scratch of its own, made at the first call, gone with the matrix.
+    DevBuf rows_rec;                                // the MODE_LLH_ROWS sweep's records, ROW_REC doubles per partial-row slot / chunk
+    DevBuf rows_out;                                // [n llh | n lgamma | n count (int64)] of the axis asked for
+    // the stored zeros sorted by an axis' rows (upload order within a row): a segment per row that has any
+    struct ZeroRows { DevBuf seg_major, seg_ptr, minor; int n_seg = 0; bool built = false; };
+    ZeroRows zero_rows[2];
     bool have_coo = false;
     int pending_init = 0;  // 0 none, 1 dense accumulators, 2 chunk partials
     int beta_parity = 0;               // swaps of the sum-of-beta buffers mod 2: which cached graph fits (schpf_ctx::graphs)
@@ -310,6 +318,8 @@ template <typename T> struct Engine final : schpf_ctx {
         dual_order.release(); dual_slots = 0;
         rows_ptr.release(); rows_col.release(); rows_val.release();
         zero_row.release(); zero_col.release();
+        rows_rec.release(); rows_out.release();
+        for (ZeroRows &z : zero_rows) z = ZeroRows();
         pending_init = 0;
         eager_since_upload = false;
     }
@@ -945,12 +955,12 @@ template <typename T> struct Engine final : schpf_ctx {
         }
     }
 
-    // The tables a sweep of side s reads: major = the side's own, minor = the other side's.  MODE_LLH reads the E
+    // The tables a sweep of side s reads: major = the side's own, minor = the other side's.  MODE_LLH and MODE_LLH_ROWS read the E
     // tables, every other mode the exp-shifted ones; the log tables are the same for all
     template <typename A> void table_args(A &a, int s, int mode)
     {
         const Side &mj = side[s], &mn = side[1 - s];
-        const bool llh = mode == schpf::MODE_LLH;
+        const bool llh = mode == schpf::MODE_LLH || mode == schpf::MODE_LLH_ROWS;
         a.tab_major = (llh ? mj.tab_e : mj.tab_exp).template as<T>();
         a.tab_minor = (llh ? mn.tab_e : mn.tab_exp).template as<T>();
         a.log_major = mj.tab_log.template as<T>();
@@ -1007,8 +1017,10 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         if (use_tile) {
             TileDev &td = side[s].tile;
-            const bool logs = mode == schpf::MODE_LLH || mode == schpf::MODE_ELBO;   // the ELBO pass is cut as the loss pass
-            const bool cut = logs && td.llh.n > 0;   // the loss pass's finer tasks (loss_tasks)
+            // the per-row pass keeps the iteration's own tasks: its records are addressed as their partial rows are
+            const bool rows = mode == schpf::MODE_LLH_ROWS;
+            const bool logs = mode == schpf::MODE_LLH || mode == schpf::MODE_ELBO || rows;   // the ELBO pass is cut as the loss pass
+            const bool cut = logs && !rows && td.llh.n > 0;   // the loss pass's finer tasks (loss_tasks)
             const TaskList &tl = cut ? td.llh : td.tasks;
             auto a = tile_args(s, mode, tl);
             a.seed = seed;
@@ -1021,11 +1033,13 @@ template <typename T> struct Engine final : schpf_ctx {
             // the loss pass keeps a 1 KiB logarithm table behind the window (sweep_impl.h LlhAccumulator)
             a.llh_tab_off = (int)((td.lds_bytes + 15) & ~(size_t)15);
             const size_t lds = logs ? (size_t)a.llh_tab_off + 1024 : td.lds_bytes;
-            if (mode == schpf::MODE_ELBO) a.clock_probe = nullptr;   // schpf_profile_clock: the sweeps and the loss pass
+            if (mode == schpf::MODE_ELBO || rows) a.clock_probe = nullptr;   // schpf_profile_clock: the sweeps and the loss pass
+            if (rows) a.wave_out = rows_rec.as<double>();
             HIPCHK(schpf::launch_tile_sweep<T>(a, NV, LPC, mode, td.packed ? 1 : 0, tl.n, td.threads, lds, stream));
         } else {
             PlanDev &pd = side[s].plan;
             auto a = sweep_args(s, mode);
+            if (mode == schpf::MODE_LLH_ROWS) a.wave_out = rows_rec.as<double>();
             if (mode == schpf::MODE_RANDOM)
                 HIPCHK(schpf::launch_random_phi<T>(a, NV, LPC, seed, s == 0 ? 1 : 0, pd.n_waves, stream));
             else
@@ -1293,6 +1307,76 @@ template <typename T> struct Engine final : schpf_ctx {
         terms[4] = h[(size_t)(W + K)];
     }
 
+    // The stored zeros grouped by the rows of axis s, once per upload: sorted by row, upload order kept within a row, so
+    // that one thread per row adds them in the same order on every call
+    void build_zero_rows(int s)
+    {
+        ZeroRows &z = zero_rows[s];
+        if (z.built) return;
+        std::vector<int32_t> idx[2] = {std::vector<int32_t>((size_t)n_zero), std::vector<int32_t>((size_t)n_zero)};
+        d2h(idx[0].data(), zero_row, (size_t)n_zero * 4, stream);
+        d2h(idx[1].data(), zero_col, (size_t)n_zero * 4, stream);
+        const std::vector<int32_t> &major = idx[s], &minor = idx[1 - s];
+        std::vector<int64_t> perm((size_t)n_zero);
+        for (int64_t i = 0; i < n_zero; ++i) perm[(size_t)i] = i;
+        std::stable_sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) { return major[(size_t)x] < major[(size_t)y]; });
+        std::vector<int32_t> seg_major, seg_ptr, mn((size_t)n_zero);
+        for (int64_t j = 0; j < n_zero; ++j) {
+            const int32_t m = major[(size_t)perm[(size_t)j]];
+            if (seg_major.empty() || seg_major.back() != m) { seg_major.push_back(m); seg_ptr.push_back((int32_t)j); }
+            mn[(size_t)j] = minor[(size_t)perm[(size_t)j]];
+        }
+        seg_ptr.push_back((int32_t)n_zero);
+        z.n_seg = (int)seg_major.size();
+        upload(z.seg_major, seg_major, stream); upload(z.seg_ptr, seg_ptr, stream); upload(z.minor, mn, stream);
+        HIPCHK(hipStreamSynchronize(stream));   // the host vectors die with this scope
+        z.built = true;
+    }
+
+    // Per major row of axis `by` (0: cells, 1: genes), over the stored entries: sum x log r - r, sum lgamma(x + 1) and the
+    // number of entries.  A MODE_LLH_ROWS sweep of THAT axis' plan over the iteration's own tasks (their
+    // partial-row addressing says where a row's records lie), a fixed-order sum per row, then the stored zeros.  Reads the
+    // state only, as elbo_terms does: scratch of its own, nothing cached but the sorted zero list.
+    void loss_rows(int by, double *llh, double *gl, int64_t *count) override
+    {
+        if (by != SCHPF_BY_CELL && by != SCHPF_BY_GENE) throw std::invalid_argument("by must be SCHPF_BY_CELL or SCHPF_BY_GENE");
+        need_coo();
+        need_loss_constants();
+        const int s = by;
+        const Side &sd = side[s];
+        const size_t n = (size_t)sd.n, n_max = (size_t)std::max(N, G);
+        int64_t n_rec[2];
+        for (int t = 0; t < 2; ++t) n_rec[t] = use_tile ? side[t].tile.host.n_partial_rows : side[t].plan.n_chunks;
+        const size_t rec_bytes = (size_t)std::max<int64_t>(std::max(n_rec[0], n_rec[1]), 1) * schpf::ROW_REC * sizeof(double);
+        if (rows_rec.bytes < rec_bytes) rows_rec.alloc(rec_bytes);
+        if (rows_out.bytes < n_max * 24) rows_out.alloc(n_max * 24);
+        if (n_zero > 0) build_zero_rows(s);
+        refresh_tables();
+        double *d_llh = rows_out.as<double>(), *d_gl = d_llh + n;
+        int64_t *d_cnt = reinterpret_cast<int64_t *>(d_gl + n);
+        ScopedTimer tm(prof, stream, 2);
+        run_sweep(s, schpf::MODE_LLH_ROWS);
+        if (use_tile) {
+            const TileDev &td = sd.tile;
+            HIPCHK(schpf::launch_row_records_reduce(rows_rec.as<double>(), td.pfirst.as<int>(), td.pcount.as<int>(),
+                                                    td.host.pstride, nullptr, sd.n, d_llh, d_gl, d_cnt, stream));
+        } else {
+            HIPCHK(schpf::launch_row_records_reduce(rows_rec.as<double>(), nullptr, nullptr, 0, sd.plan.cptr.as<int>(), sd.n,
+                                                    d_llh, d_gl, d_cnt, stream));
+        }
+        if (n_zero > 0) {
+            const ZeroRows &z = zero_rows[s];
+            HIPCHK(schpf::launch_zero_rate_rows<T>(z.seg_major.template as<int>(), z.seg_ptr.template as<int>(), z.n_seg,
+                                                   z.minor.template as<int>(),
+                                                   sd.tab_e.as<T>(), side[1 - s].tab_e.as<T>(), K, KP, d_llh, d_cnt, stream));
+        }
+        tm.stop();
+        HIPCHK(hipMemcpyAsync(llh, d_llh, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(gl, d_gl, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(count, d_cnt, n * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+
     // which tile plan the loss pass sweeps (policy.cpp loss_side)
     int loss_side() const
     {
@@ -1475,6 +1559,12 @@ int schpf_elbo_terms(schpf_ctx *ctx, double ap, double cp, double terms[5])
     if (!ctx) return fail("ctx is NULL");
     if (!terms) return fail("terms is NULL");
     CTX_CALL(ctx->elbo_terms(ap, cp, terms));
+}
+int schpf_loss_rows(schpf_ctx *ctx, int by, double *llh_sum, double *gammaln_sum, int64_t *count)
+{
+    if (!ctx) return fail("ctx is NULL");
+    if (!llh_sum || !gammaln_sum || !count) return fail("output pointer is NULL");
+    CTX_CALL(ctx->loss_rows(by, llh_sum, gammaln_sum, count));
 }
 int schpf_synchronize(schpf_ctx *ctx) { CTX_CALL(HIPCHK(hipStreamSynchronize(ctx->stream))); }
 

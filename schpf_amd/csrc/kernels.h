@@ -5,7 +5,10 @@
 
 namespace schpf {
 
-enum { MODE_PHI = 0, MODE_LLH = 1, MODE_RANDOM = 2, MODE_ELBO = 3 };
+enum { MODE_PHI = 0, MODE_LLH = 1, MODE_RANDOM = 2, MODE_ELBO = 3, MODE_LLH_ROWS = 4 };
+// MODE_LLH_ROWS leaves one record of ROW_REC doubles per lane group (tile sweep: per partial-row slot task * gpb + g;
+// gather sweep: per chunk) in wave_out: {sum x log r - r, sum lgamma(x + 1), entries with x > 0}
+enum { ROW_REC = 3 };
 enum { SRC_STRIDED = 3 };
 enum { SRC_NONE = 0, SRC_PARTIALS = 1, SRC_DENSE = 2 };
 
@@ -21,7 +24,7 @@ template <typename T> struct SweepArgs {
     const T *log_major;         // [n_major, KP] E[log x] (fallback only)
     const T *log_minor;         // [n_minor, KP]
     T *partials;                // [n_chunks, KP]
-    double *wave_out;           // [n_waves] (LLH, ELBO)
+    double *wave_out;           // [n_waves] (LLH, ELBO); [n_chunks * ROW_REC] (LLH_ROWS)
     int K;
 };
 
@@ -40,7 +43,7 @@ template <typename T> struct TileArgs {
     const T *tab_minor;            // [n_minor, KP]  (staged window by window)
     const T *log_major, *log_minor;
     T *partials;                   // [n_tasks * gpb, KP]
-    double *wave_out;              // [n_tasks * wpb] (LLH, ELBO)
+    double *wave_out;              // [n_tasks * wpb] (LLH, ELBO); [n_tasks * gpb * ROW_REC] (LLH_ROWS)
     int K, n_minor, n_windows, win_rows, wpb;
     // balanced windows (plan.h): block b stages window w from the table rows minor_of[b * n_virtual + w * win_rows + j]
     // (-1: none); n_minor is then n_virtual.  nullptr: windows are index ranges of the table
@@ -151,6 +154,18 @@ hipError_t launch_gammaln_sum(const float *x, int64_t n, double *block_out, int 
 template <typename T>
 hipError_t launch_zero_rate_sum(const int *row, const int *col, int64_t n, const T *et, const T *eb, int K, int KP,
                                 double *out, hipStream_t st);
+// Per-row loss.  The records a MODE_LLH_ROWS sweep left, summed per major row in fixed order -- addressed as
+// the update kernel addresses a row's partial rows: pfirst != nullptr: records pfirst[row] + j * pstride, j < pcount[row]
+// (tile plan); else records cptr[row] .. cptr[row + 1] (gather plan) -- into llh[n], gl[n], cnt[n]
+hipError_t launch_row_records_reduce(const double *rec, const int *pfirst, const int *pcount, int64_t pstride,
+                                     const int *cptr, int n, double *llh, double *gl, int64_t *cnt, hipStream_t st);
+// ... and the explicitly stored zeros, which the sweeps take for padding: one thread per major row that has any
+// (seg_major[s]; its zeros are minor[seg_ptr[s] .. seg_ptr[s + 1]), an order fixed when the list was sorted):
+// llh[row] -= sum r, cnt[row] += their number
+template <typename T>
+hipError_t launch_zero_rate_rows(const int *seg_major, const int *seg_ptr, int n_seg, const int *minor,
+                                 const T *e_major, const T *e_minor, int K, int KP, double *llh, int64_t *cnt,
+                                 hipStream_t st);
 template <typename T>
 hipError_t launch_segment_sum(const double *xphi, const int *order, const int64_t *mptr, int n, int K, T *out,
                               hipStream_t st);

@@ -310,6 +310,50 @@ __global__ __launch_bounds__(256) void zero_rate_sum_kernel(const int *__restric
     if (threadIdx.x == 0) out[0] = red[0];
 }
 
+// Per-row loss: one thread per major row sums the row's MODE_LLH_ROWS records, field by field, in the
+// order the update kernel sums the row's partial rows (sum_strided) -- no atomics, the same bits on every call.
+__global__ __launch_bounds__(256) void row_records_reduce_kernel(const double *__restrict__ rec,
+                                                                 const int *__restrict__ pfirst,
+                                                                 const int *__restrict__ pcount, int64_t pstride,
+                                                                 const int *__restrict__ cptr, int n,
+                                                                 double *__restrict__ llh, double *__restrict__ gl,
+                                                                 int64_t *__restrict__ cnt)
+{
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const double *p;
+    int m;
+    size_t stride;
+    if (pfirst) { p = rec + (size_t)pfirst[row] * ROW_REC; m = pcount[row]; stride = (size_t)pstride * ROW_REC; }
+    else { p = rec + (size_t)cptr[row] * ROW_REC; m = cptr[row + 1] - cptr[row]; stride = ROW_REC; }
+    llh[row] = sum_strided(p, m, stride);
+    gl[row] = sum_strided(p + 1, m, stride);
+    cnt[row] = (int64_t)sum_strided(p + 2, m, stride);   // whole numbers below 2^31: exact
+}
+// The stored zeros of one major row, in the order of the sorted list: each adds -r to the row's llh sum and 1 to its
+// count (x log r - r - lgamma(x + 1) = -r at x = 0, hpf_numba.py:43-50).  r as zero_rate_sum_kernel computes it.
+template <typename T>
+__global__ __launch_bounds__(256) void zero_rate_rows_kernel(const int *__restrict__ seg_major,
+                                                             const int *__restrict__ seg_ptr, int n_seg,
+                                                             const int *__restrict__ minor, const T *__restrict__ e_major,
+                                                             const T *__restrict__ e_minor, int K, int KP,
+                                                             double *__restrict__ llh, int64_t *__restrict__ cnt)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_seg) return;
+    const int row = seg_major[s];
+    const T *t = e_major + (size_t)row * KP;
+    double sum = 0.0;
+    for (int i = seg_ptr[s]; i < seg_ptr[s + 1]; ++i) {
+        const T *b = e_minor + (size_t)minor[i] * KP;
+        T r = T(0);
+        for (int k = 0; k < K; ++k) r += t[k] * b[k];
+        sum += (double)r;
+    }
+    llh[row] -= sum;
+    cnt[row] += seg_ptr[s + 1] - seg_ptr[s];
+}
+
 // ------------------------------------------------------ t = 0 random responsibilities
 // scHPF_.py:652-655: X*phi with phi ~ Dirichlet(1_K), drawn by the caller (NumPy global
 // RNG, for seed parity) and uploaded as (nnz, K) float64 in the caller's COO order.
@@ -659,6 +703,25 @@ hipError_t launch_zero_rate_sum(const int *row, const int *col, int64_t n, const
     hipLaunchKernelGGL((zero_rate_sum_kernel<T>), dim3(1), dim3(256), 0, st, row, col, n, et, eb, K, KP, out);
     return hipGetLastError();
 }
+hipError_t launch_row_records_reduce(const double *rec, const int *pfirst, const int *pcount, int64_t pstride,
+                                     const int *cptr, int n, double *llh, double *gl, int64_t *cnt, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    if (!pfirst && !cptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(row_records_reduce_kernel, dim3(blocks_for(n)), dim3(256), 0, st, rec, pfirst, pcount, pstride,
+                       cptr, n, llh, gl, cnt);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_zero_rate_rows(const int *seg_major, const int *seg_ptr, int n_seg, const int *minor,
+                                 const T *e_major, const T *e_minor, int K, int KP, double *llh, int64_t *cnt,
+                                 hipStream_t st)
+{
+    if (n_seg <= 0) return hipSuccess;
+    hipLaunchKernelGGL((zero_rate_rows_kernel<T>), dim3(blocks_for(n_seg)), dim3(256), 0, st, seg_major, seg_ptr,
+                       n_seg, minor, e_major, e_minor, K, KP, llh, cnt);
+    return hipGetLastError();
+}
 template <typename T>
 hipError_t launch_segment_sum(const double *xphi, const int *order, const int64_t *mptr, int n, int K, T *out,
                               hipStream_t st)
@@ -763,6 +826,8 @@ hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStre
                                                   T *, hipStream_t);                                           \
     template hipError_t launch_zero_rate_sum<T>(const int *, const int *, int64_t, const T *, const T *, int,  \
                                                 int, double *, hipStream_t);                                  \
+    template hipError_t launch_zero_rate_rows<T>(const int *, const int *, int, const int *, const T *,        \
+                                                 const T *, int, int, double *, int64_t *, hipStream_t);       \
     template hipError_t launch_segment_sum<T>(const double *, const int *, const int64_t *, int, int, T *,     \
                                               hipStream_t);                                                    \
     template hipError_t launch_elog<T>(const T *, const T *, int64_t, T *, hipStream_t);                       \

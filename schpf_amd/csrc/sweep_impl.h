@@ -435,6 +435,8 @@ __device__ __noinline__ double slow_task_elbo(const void *__restrict__ entries, 
 //            (hpf_numba.py:43-50 minus the constant gammaln term); one double per wave.
 // MODE_ELBO: sum over the chunk of x*log(s), s the normaliser of MODE_PHI (exp-shifted tables): the data term of
 //            the ELBO less its shifts m_i + m_g; one double per wave.  Underflowed s: slow_chunk_elbo.
+// MODE_LLH_ROWS: MODE_LLH kept per chunk instead of per wave, with sum lgamma(x + 1) and the number of entries beside it
+//            (DESIGN.md 12): one record of ROW_REC doubles per chunk, at the chunk's partial-row index.
 template <typename T, int NV, int LPC, int MODE>
 __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
 {
@@ -459,6 +461,8 @@ __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
     for (int k = 0; k < KL; ++k) { tm[k] = T(0); acc[k] = T(0); }
     if (live) load_lane<T, NV, LPC>(a.tab_major + (size_t)major * KP, sub, tm);
     double llh = 0.0;
+    double row_gl = 0.0;   // MODE_LLH_ROWS
+    int row_cnt = 0;
     bool any_bad = false;
 
     const uint4 *__restrict__ ep = a.entries + a.slice_off[slice] + slot;
@@ -486,6 +490,17 @@ __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
         } else if (MODE == MODE_LLH) {
             if (x0 > T(0)) llh += (double)x0 * log((double)s0) - (double)s0;
             if (x1 > T(0)) llh += (double)x1 * log((double)s1) - (double)s1;
+        } else if constexpr (MODE == MODE_LLH_ROWS) {   // every lane of the group knows s: lane 0 keeps the chunk's sums
+            if (sub == 0 && x0 > T(0)) {
+                llh += (double)x0 * log((double)s0) - (double)s0;
+                row_gl += lgamma((double)x0 + 1.0);
+                ++row_cnt;
+            }
+            if (sub == 0 && x1 > T(0)) {
+                llh += (double)x1 * log((double)s1) - (double)s1;
+                row_gl += lgamma((double)x1 + 1.0);
+                ++row_cnt;
+            }
         } else {   // MODE_ELBO: an underflowed s is left to the cold path (slow_chunk_elbo)
             const bool ok0 = s0 >= tiny, ok1 = s1 >= tiny;
             any_bad |= (x0 > T(0) && !ok0) || (x1 > T(0) && !ok1);
@@ -494,6 +509,13 @@ __global__ __launch_bounds__(256) void sweep_kernel(SweepArgs<T> a)
         }
     }
 
+    if constexpr (MODE == MODE_LLH_ROWS) {   // every chunk belongs to exactly one live group (as its partial row does)
+        if (live && sub == 0) {
+            double *rec = a.wave_out + (size_t)a.chunk_natid[(size_t)slice * CPW + slot] * ROW_REC;
+            rec[0] = llh; rec[1] = row_gl; rec[2] = (double)row_cnt;
+        }
+        return;
+    }
     if (MODE == MODE_LLH || MODE == MODE_ELBO) {
         if constexpr (MODE == MODE_ELBO) {
             if (__builtin_expect(any_bad && live, 0))   // group-uniform; rare
@@ -706,8 +728,12 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
     for (int k = 0; k < KL; ++k) { tm[k] = T(0); acc[k] = T(0); }
     if (MODE != MODE_RANDOM && live) load_lane<T, NV, LPC>(a.tab_major + (size_t)major * KP, sub, tm);
     double llh = 0.0;
-    constexpr bool LOGS = MODE == MODE_LLH || MODE == MODE_ELBO;
-    LlhAccumulator lacc;   // MODE_LLH, MODE_ELBO
+    constexpr bool LOGS = MODE == MODE_LLH || MODE == MODE_ELBO || MODE == MODE_LLH_ROWS;
+    LlhAccumulator lacc;   // MODE_LLH, MODE_ELBO, MODE_LLH_ROWS
+    // MODE_LLH_ROWS: sum lgamma(x + 1) and the number of entries, beside lacc and in the lanes that feed
+    // it.  Touched under `if constexpr` only, for the reason given below for MODE_ELBO
+    double row_gl = 0.0;
+    int row_cnt = 0;
     // ... and its logarithm table, behind the window in LDS (a.llh_tab_off; the window loop's first barrier publishes it)
     const double2 *llh_tab = reinterpret_cast<const double2 *>(lds_raw + (LOGS ? a.llh_tab_off : 0));
     if (LOGS) LlhAccumulator::fill_table(reinterpret_cast<double2 *>(lds_raw + a.llh_tab_off), (int)threadIdx.x);
@@ -902,6 +928,20 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
                         load_lane<T, NV, LPC>(lds_row<T>(lds_raw, n0), sub, bA);
                         load_lane<T, NV, LPC>(lds_row<T>(lds_raw, n1), sub, bB);
                     }
+                    if constexpr (MODE == MODE_LLH_ROWS) {   // as MODE_LLH below, plus the row's lgamma sum and count
+                        if (LPC == 1) {
+                            if (x0 > T(0)) { lacc.add((double)x0, (double)s0, llh_tab); row_gl += lgamma((double)x0 + 1.0); ++row_cnt; }
+                            if (x1 > T(0)) { lacc.add((double)x1, (double)s1, llh_tab); row_gl += lgamma((double)x1 + 1.0); ++row_cnt; }
+                        } else {
+                            const T sm = (sub & 1) ? s1 : s0;
+                            const T xm = (sub & 1) ? x1 : x0;
+                            if (sub < 2 && xm > T(0)) {
+                                lacc.add((double)xm, (double)sm, llh_tab);
+                                row_gl += lgamma((double)xm + 1.0);
+                                ++row_cnt;
+                            }
+                        }
+                    }
                     if (MODE == MODE_LLH) {
                         if (LPC == 1) {
                             if (x0 > T(0)) lacc.add((double)x0, (double)s0, llh_tab);
@@ -989,7 +1029,10 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
                         const bool ok = s >= Vec16<T>::tiny();
                         any_bad |= x > T(0) && !ok;
                         if ((LPC == 1 || sub == 0) && x > T(0) && ok) lacc.add_log((double)x, (double)s, llh_tab);
-                    } else if ((LPC == 1 || sub == 0) && x > T(0)) lacc.add((double)x, (double)s, llh_tab);
+                    } else if ((LPC == 1 || sub == 0) && x > T(0)) {
+                        lacc.add((double)x, (double)s, llh_tab);
+                        if constexpr (MODE == MODE_LLH_ROWS) { row_gl += lgamma((double)x + 1.0); ++row_cnt; }
+                    }
                 }
             };
             auto roll_step = [&](auto I_) {
@@ -1086,7 +1129,10 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
                                 if ((LPC == 1 || sub == 0) && x > T(0) && ok) lacc.add_log((double)x, (double)s, llh_tab);
                             } else {
                                 // lane 0 of the group keeps the group's share
-                                if ((LPC == 1 || sub == 0) && x > T(0)) lacc.add((double)x, (double)s, llh_tab);
+                                if ((LPC == 1 || sub == 0) && x > T(0)) {
+                                    lacc.add((double)x, (double)s, llh_tab);
+                                    if constexpr (MODE == MODE_LLH_ROWS) { row_gl += lgamma((double)x + 1.0); ++row_cnt; }
+                                }
                             }
                         }
                     }
@@ -1108,6 +1154,19 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
         llh += lacc.total();   // zero where nothing was added
         // which lanes hold a share: all (LPC 1), lanes 0-1 of a group (paired steps), lane 0 (else)
         if (LPC > 1 && !(PAIR ? sub < 2 : sub == 0)) llh = 0.0;
+        if constexpr (MODE == MODE_LLH_ROWS) {
+            // the group's lanes that hold a share are the ones named above (row_gl and row_cnt are zero in the others, as
+            // llh is): summed over the group, not the wave, in the fixed order of the DPP exchange.  One record per
+            // partial-row slot of the task; dead groups' sums are zero (padding only), so every record is defined
+            llh = group_sum<double, LPC>(llh);
+            row_gl = group_sum<double, LPC>(row_gl);
+            const double cnt = group_sum<double, LPC>((double)row_cnt);
+            if (sub == 0) {
+                double *rec = a.wave_out + ((size_t)task * gpb + g) * ROW_REC;
+                rec[0] = live ? llh : 0.0; rec[1] = live ? row_gl : 0.0; rec[2] = live ? cnt : 0.0;
+            }
+            return;
+        }
         if constexpr (MODE == MODE_ELBO) {
             if (__builtin_expect(any_bad && live, 0)) {   // group-uniform; rare: see slow_task_elbo
                 const double r = slow_task_elbo<T, NV, LPC, PACK>(
@@ -1264,6 +1323,9 @@ static hipError_t launch_tile_b(const TileArgs<T> &a_in, int mode, int64_t n_tas
             if (e == hipSuccess)
                 e = hipFuncSetAttribute((const void *)tile_sweep_kernel<T, NV, LPC, MODE_ELBO, MAXT, PACK, BAL>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute((const void *)tile_sweep_kernel<T, NV, LPC, MODE_LLH_ROWS, MAXT, PACK, BAL>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
             if (e != hipSuccess) { raised = 0; return e; }
         }
     }
@@ -1273,6 +1335,8 @@ static hipError_t launch_tile_b(const TileArgs<T> &a_in, int mode, int64_t n_tas
         hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_LLH, MAXT, PACK, BAL>), grid, block, lds_bytes, st, a);
     else if (mode == MODE_ELBO)
         hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_ELBO, MAXT, PACK, BAL>), grid, block, lds_bytes, st, a);
+    else if (mode == MODE_LLH_ROWS)
+        hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_LLH_ROWS, MAXT, PACK, BAL>), grid, block, lds_bytes, st, a);
     else   // one-off: the 1024-thread bound serves every workgroup size (one instantiation instead of two)
         hipLaunchKernelGGL((tile_sweep_kernel<T, NV, LPC, MODE_RANDOM, 1024, PACK>), grid, block, 0, st, a);
     return hipGetLastError();
@@ -1339,6 +1403,8 @@ static hipError_t launch_sweep_t(const SweepArgs<T> &a, int mode, int64_t n_wave
         hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_PHI>), grid, block, 0, st, a);
     else if (mode == MODE_LLH)
         hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_LLH>), grid, block, 0, st, a);
+    else if (mode == MODE_LLH_ROWS)
+        hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_LLH_ROWS>), grid, block, 0, st, a);
     else
         hipLaunchKernelGGL((sweep_kernel<T, NV, LPC, MODE_ELBO>), grid, block, 0, st, a);
     return hipGetLastError();
@@ -1354,7 +1420,7 @@ static hipError_t launch_random_t(const SweepArgs<T> &a, uint64_t seed, int majo
 }
 
 // Only the (vectors per lane, lanes per row) pairs that capi.hip choose_config can pick are instantiated
-// (kernels.h tile_combo_ok / gather_combo_ok list them): every pair costs 16 tile kernels or 3 gather
+// (kernels.h tile_combo_ok / gather_combo_ok list them): every pair costs 32 tile kernels or 5 gather
 // kernels per dtype, and the full 9 x 5 grid made a 21 MB library.
 #define SCHPF_COMBO(nv_, lpc_, CALLEXPR)                                      \
     if (nv == nv_ && lpc == lpc_) { constexpr int NV = nv_; constexpr int LPC = lpc_; return CALLEXPR; }

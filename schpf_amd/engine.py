@@ -27,6 +27,15 @@ def mean_negative(llh, gl, nnz):
     return -(llh - gl) / nnz if nnz else float("nan")
 
 
+def rowmean_negative(llh, gl, count):
+    """-(llh - gl) / count per row, float64; NaN where a row has no stored entry (the reference's mean over an empty
+    row is 0/0 = NaN too), without a warning."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return -(np.asarray(llh, np.float64) - np.asarray(gl, np.float64)) / np.asarray(count, np.float64)
+
+
+_AXES = {"cell": _lib.BY_CELL, "gene": _lib.BY_GENE}
+
 ELBO_TERMS = ("data", "logfac", "rate", "cell", "gene")
 
 
@@ -260,6 +269,27 @@ class DeviceCAVI(object):
     def mean_negative_pois_llh(self):
         llh, gl, nnz = self.loss_terms()
         return mean_negative(llh, gl, nnz)
+
+    def loss_rows(self, by="cell"):
+        """Per cell (by="cell") or per gene (by="gene"), over the local stored entries of that row -- duplicates are
+        separate observations, stored zeros count --: (sum x log r - r, sum lgamma(x+1), number of entries), float64,
+        float64 and int64 arrays of ncells / ngenes.  One sweep of the plan of that axis on the device (DESIGN.md 12);
+        the state is only read, and two calls on one state return the same bits."""
+        if by not in _AXES:
+            raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
+        n = self.ncells if by == "cell" else self.ngenes
+        llh, gl, cnt = np.empty(n, np.float64), np.empty(n, np.float64), np.empty(n, np.int64)
+        _lib.check(self._lib.schpf_loss_rows(self._h, _AXES[by], llh.ctypes.data_as(_lib._dblp),
+                                             gl.ctypes.data_as(_lib._dblp), cnt.ctypes.data_as(_lib._i64p)))
+        return llh, gl, cnt
+
+    def cellmean_negative_pois_llh(self):
+        """Mean negative Poisson log-likelihood of each cell's stored entries (NaN for a cell without any)."""
+        return rowmean_negative(*self.loss_rows("cell"))
+
+    def genemean_negative_pois_llh(self):
+        """Mean negative Poisson log-likelihood of each gene's stored entries (NaN for a gene without any)."""
+        return rowmean_negative(*self.loss_rows("gene"))
 
     def elbo_terms(self, ap, cp):
         """The evidence lower bound of the current state over the local cells, by term:

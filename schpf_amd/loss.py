@@ -13,7 +13,7 @@ import numpy as np
 from .hpf_hip import compute_pois_llh
 
 __all__ = ["loss_function_for_data", "projection_loss_function", "pois_llh_pointwise",
-           "mean_negative_pois_llh", "elbo"]
+           "mean_negative_pois_llh", "elbo", "cellmean_negative_pois_llh", "genemean_negative_pois_llh"]
 
 
 def loss_function_for_data(loss_function, X):
@@ -118,3 +118,30 @@ def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=N
             eng.set_gamma(name, g.vi_shape, g.vi_rate)
         out = eng.elbo_terms(ap, cp)
     return out if terms else out["elbo"]
+
+
+def _rowmean_on_device(X, theta, beta, by, device):
+    """X uploaded once, theta / beta set, the per-row loss of axis `by` evaluated on the device."""
+    from .engine import DeviceCAVI   # late import, as in projection_loss_function
+    import os
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    if not hasattr(X, "row"):
+        X = X.tocoo()
+    with DeviceCAVI(X.shape[0], X.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
+        eng.upload(X)
+        eng.set_gamma("theta", theta.vi_shape, theta.vi_rate)
+        eng.set_gamma("beta", beta.vi_shape, beta.vi_rate)
+        return eng.cellmean_negative_pois_llh() if by == "cell" else eng.genemean_negative_pois_llh()
+
+
+def cellmean_negative_pois_llh(X, *, theta, beta, device=None, **kwargs):
+    """Mean negative Poisson log-likelihood of the stored entries of each cell of X (NaN for a cell without any),
+    float64 [ncells], evaluated on the GPU.  `device`: HIP device ordinal, default $SCHPF_DEVICE or 0."""
+    return _rowmean_on_device(X, theta, beta, "cell", device)
+
+
+def genemean_negative_pois_llh(X, *, theta, beta, device=None, **kwargs):
+    """Mean negative Poisson log-likelihood of the stored entries of each gene of X (NaN for a gene without any),
+    float64 [ngenes], evaluated on the GPU.  `device`: HIP device ordinal, default $SCHPF_DEVICE or 0."""
+    return _rowmean_on_device(X, theta, beta, "gene", device)

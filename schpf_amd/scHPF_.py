@@ -272,7 +272,9 @@ class scHPF(BaseEstimator):
         return ls.pois_llh_pointwise(X=X, theta=theta, beta=beta)
 
     def cellmean_negative_pois_llh(self, X, theta=None, beta=None):
-        """Mean negative llh of the nonzeros of each cell (scHPF_.py:395-411)."""
+        """Mean negative llh of the nonzeros of each cell (scHPF_.py:395-411).  This is the reference's host route
+        (pointwise values back, row means on the CPU); schpf_amd.loss.cellmean_negative_pois_llh and
+        DeviceCAVI.cellmean_negative_pois_llh evaluate the same on the device."""
         theta = self.theta if theta is None else theta
         assert theta.vi_shape.shape[0] == X.shape[0]
         beta = self.beta if beta is None else beta
@@ -283,6 +285,14 @@ class scHPF(BaseEstimator):
         averages = sums / counts
         assert averages.shape[0] == theta.vi_shape.shape[0]
         return averages
+
+    def genemean_negative_pois_llh(self, X, theta=None, beta=None, device=None):
+        """Mean negative llh of the stored entries of each gene (NaN for a gene without any), evaluated on the GPU
+        (schpf_amd.loss.genemean_negative_pois_llh; an addition to the reference's surface)."""
+        theta = self.theta if theta is None else theta
+        assert theta.vi_shape.shape[0] == X.shape[0]
+        beta = self.beta if beta is None else beta
+        return ls.genemean_negative_pois_llh(X, theta=theta, beta=beta, device=device)
 
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""

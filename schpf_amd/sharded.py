@@ -22,7 +22,7 @@ import inspect
 
 import numpy as np
 
-from .engine import elbo_dict, mean_negative
+from .engine import elbo_dict, mean_negative, rowmean_negative
 
 __all__ = ["row_partition", "take_rows", "ShardedCAVI", "exchange_tensor_of", "ThreadedShards", "NativeShard"]
 
@@ -288,6 +288,26 @@ class ThreadedShards(object):
 
     def elbo(self, ap, cp):
         return self.elbo_terms(ap, cp)["elbo"]
+
+    def loss_rows(self, by="cell"):
+        """DeviceCAVI.loss_rows of the whole matrix: by cell, the shards' arrays concatenated (the row partition is in
+        the original cell order); by gene, the three arrays summed over the shards on the host, shard 0 first."""
+        if by not in ("cell", "gene"):
+            raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
+        parts = self._each(lambda r: self.engines[r].loss_rows(by))
+        if by == "cell":
+            return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+        out = [np.array(a, copy=True) for a in parts[0]]
+        for p in parts[1:]:
+            for acc, a in zip(out, p):
+                acc += a
+        return tuple(out)
+
+    def cellmean_negative_pois_llh(self):
+        return rowmean_negative(*self.loss_rows("cell"))
+
+    def genemean_negative_pois_llh(self):
+        return rowmean_negative(*self.loss_rows("gene"))
 
     def close(self):
         engines, self.engines = getattr(self, "engines", []), []
