@@ -11,7 +11,7 @@
  *
  * Conventions
  *   - plain C types only; all array arguments of the stateless functions and of
- *     set/get_state are HOST pointers to C-contiguous row-major buffers owned by the
+ *     set/get_state are HOST pointers (the *_device entry points take device pointers and say so) to C-contiguous row-major buffers owned by the
  *     caller for the duration of the call (nothing is retained);
  *   - `dtype` selects the model precision T: SCHPF_F32 or SCHPF_F64 (the reference's
  *     scHPF(dtype=...) / hpf_numba.py:30,80);  indices are int32 (SciPy COO default);
@@ -133,6 +133,33 @@ int schpf_destroy(schpf_ctx *ctx);
 int schpf_upload_coo(schpf_ctx *ctx, int64_t nnz, const int32_t *row, const int32_t *col,
                      const void *val, int val_kind);
 
+/* The same matrix when it is in GPU memory already, as a COO or as a CSR (a torch sparse tensor, the output of a
+ * GPU-side filtering step): nothing of O(nnz) crosses PCIe.  Everything schpf_upload_coo does with host
+ * threads -- validation, conversion to float32 / int32, the stored-zero list, the order of the entries, the samples of
+ * the task-range model -- runs as device passes, and the engine then holds what schpf_upload_coo would hold after the
+ * same entries in the same order: the same plans and upload_info, every later result bit for bit.  Under
+ * SCHPF_PLAN=gather / SCHPF_DEVICE_PLAN=0 the converted triples are staged to the host builders (the cross-check).
+ *   row/col/val (indptr/indices/val): DEVICE pointers on the context's device, complete before the call, not
+ *   modified, not retained; on return the engine has finished reading them.  Indices are int32 or int64 (idx_kind;
+ *   a CSR's indptr[ncells + 1] has a kind of its own), values of any SCHPF_VAL_* kind; int32 / float32 arrays are
+ *   read in place.
+ * Errors carry schpf_upload_coo's messages, "COO index out of range at entry N" (negative, >= ncells / ngenes, or an
+ * int64 beyond int32) and "X.data must be finite and >= 0; offending entry N", with THIS path's rule for N: the smallest
+ * offending entry of the whole matrix, an index error before a value error (the host path reports per slab of its
+ * threads).  A CSR is refused unless indptr[0] == 0, indptr is non-decreasing and indptr[ncells] == nnz.
+ * nnz >= 2^31 and NULL pointers with nnz > 0 are refused.  A failed upload leaves the engine without a matrix. */
+#define SCHPF_IDX_I32 0
+#define SCHPF_IDX_I64 1
+int schpf_upload_coo_device(schpf_ctx *ctx, int64_t nnz, const void *row, const void *col, int idx_kind,
+                            const void *val, int val_kind);
+int schpf_upload_csr_device(schpf_ctx *ctx, int64_t nnz, const void *indptr, int indptr_kind,
+                            const void *indices, int idx_kind, const void *val, int val_kind);
+
+/* Row sums (per local cell) and column sums (per gene) of the matrix the engine holds, as the doubles it already
+ * keeps for the ELBO shift terms: sums of the stored float32 values in plan order, exact for counts.  Host arrays of
+ * ncells / ngenes (either may be NULL).  Fails on a batch engine (schpf_upload_rows). */
+int schpf_marginals(schpf_ctx *ctx, double *row_sums, double *col_sums);
+
 /* a, c (shape priors of theta, beta) and bp, dp (rate hyper-priors; scHPF_.py:847-879).
  * ap/cp only enter through the constant xi/eta shapes (scHPF_.py:616-618), which the
  * caller sets with schpf_set_state. */
@@ -141,6 +168,10 @@ int schpf_set_hypers(schpf_ctx *ctx, double a, double c, double bp, double dp);
 /* vi_shape / vi_rate of one HPF_Gamma (scHPF_.py:27-81); (n,) for xi/eta, (n, K) else. */
 int schpf_set_state(schpf_ctx *ctx, int which, const void *shape, const void *rate);
 int schpf_get_state(schpf_ctx *ctx, int which, void *shape, void *rate);
+/* The same with DEVICE pointers of the engine's dtype on the context's device (copies on the context's stream; both
+ * calls synchronise it before returning, so the caller may release or read its arrays at once). */
+int schpf_set_state_device(schpf_ctx *ctx, int which, const void *shape, const void *rate);
+int schpf_get_state_device(schpf_ctx *ctx, int which, void *shape, void *rate);
 
 /* t == 0 of a fit with reinit=True (scHPF_.py:652-655): X*phi with phi ~ Dirichlet(1_K).
  * _host: the caller drew it (NumPy, seed-compatible with the reference) and passes

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SCHPF_LIB_PATH") or os.path.join(_HERE, "libschpf_hip
 F32, F64 = 0, 1
 XI, THETA, ETA, BETA = 0, 1, 2, 3
 VAL_I32, VAL_I64, VAL_F32, VAL_F64 = 0, 1, 2, 3
+IDX_I32, IDX_I64 = 0, 1   # SCHPF_IDX_*: the index types of the device uploads
 STREAM_DEFAULT = 1   # SCHPF_STREAM_DEFAULT: the device's null stream
 FREEZE_GENES, SIMULTANEOUS, SHARDED, CELLS_FIRST, LOCAL_GENE, LOCAL_CELL = 1, 2, 4, 8, 16, 32
 BY_CELL, BY_GENE = 0, 1   # SCHPF_BY_CELL / SCHPF_BY_GENE: the axis of schpf_loss_rows
@@ -38,6 +39,11 @@ SIGNATURES = {
     "schpf_create": [ctypes.POINTER(_vp), _int, _vp, _int, _int, _int, _int],
     "schpf_destroy": [_vp],
     "schpf_upload_coo": [_vp, _i64, _vp, _vp, _vp, _int],
+    "schpf_upload_coo_device": [_vp, _i64, _vp, _vp, _int, _vp, _int],
+    "schpf_upload_csr_device": [_vp, _i64, _vp, _int, _vp, _int, _vp, _int],
+    "schpf_marginals": [_vp, _dblp, _dblp],
+    "schpf_set_state_device": [_vp, _int, _vp, _vp],
+    "schpf_get_state_device": [_vp, _int, _vp, _vp],
     "schpf_set_hypers": [_vp, _dbl, _dbl, _dbl, _dbl],
     "schpf_set_state": [_vp, _int, _vp, _vp],
     "schpf_get_state": [_vp, _int, _vp, _vp],

@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "policy.h"
 #include "rccl.h"
+#include "upload_device.h"
 
 using namespace schpf;
 
@@ -121,8 +122,13 @@ struct schpf_ctx {
     bool own_stream = false;
     virtual ~schpf_ctx() { comm_destroy(); }
     virtual void upload_coo(int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int kind) = 0;
-    virtual void set_state(int which, const void *shape, const void *rate) = 0;
-    virtual void get_state(int which, void *shape, void *rate) = 0;
+    // an upload from device memory: a COO (indptr_kind < 0, rows = the row index per entry) or a CSR (rows = indptr)
+    virtual void upload_device(int64_t nnz, const void *rows, int indptr_kind, const void *col, int idx_kind,
+                               const void *val, int val_kind) = 0;
+    virtual void marginals(double *row_sums, double *col_sums) = 0;
+    // device: shape / rate are device pointers (a copy on the stream) instead of host pointers
+    virtual void set_state(int which, const void *shape, const void *rate, bool device = false) = 0;
+    virtual void get_state(int which, void *shape, void *rate, bool device = false) = 0;
     virtual void init_phi_host(const double *xphi) = 0;
     virtual void init_phi_device(uint64_t seed) = 0;
     virtual void step_local(unsigned flags) = 0;
@@ -530,11 +536,11 @@ template <typename T> struct Engine final : schpf_ctx {
     // engine's constants only, so the per-upload fields are simply unset
     schpf::Problem problem() const { return problem(UploadJob{nnz}); }
 
-    // The shapes of both tile plans, once per upload, for whichever builder runs.  row / col: the COO on the host for
-    // the task-range model to sample; nullptr: no ranges (batch rows)
-    void plan_shapes(UploadJob &job, const int32_t *row, const int32_t *col) const
+    // The shapes of both tile plans, once per upload, for whichever builder runs.  sample: the histograms of the COO's
+    // sampled indices for the task-range model, from wherever the COO lies (policy.h); empty: no ranges (batch rows)
+    void plan_shapes(UploadJob &job, const schpf::SampleHistograms &sample) const
     {
-        if (!row || !schpf::choose_ranges(problem(job), tuning, row, col, job.ranges, job.half)) {
+        if (!sample || !schpf::choose_ranges(problem(job), tuning, sample, job.ranges, job.half)) {
             job.ranges[0] = job.ranges[1] = 0;
             job.half[0] = job.half[1] = -1;
         }
@@ -547,10 +553,10 @@ template <typename T> struct Engine final : schpf_ctx {
 
     // Both tile plans built by device passes over a COO that is in HBM (plan_device.hip): same plans, bit for bit, as
     // tiles_from_host_coo(); SCHPF_DEVICE_PLAN=0 selects the host builder for schpf_upload_coo.
-    void tiles_from_device_coo(const UploadJob &job, const DevBuf &d_row, const DevBuf &d_col, const DevBuf &d_val)
+    void tiles_from_device_coo(const UploadJob &job, const int32_t *d_row, const int32_t *d_col, const float *d_val)
     {
         // per side: its index array is the major one, the other side's the minor one
-        const int32_t *const d_idx[2] = {d_row.as<int32_t>(), d_col.as<int32_t>()};
+        const int32_t *const d_idx[2] = {d_row, d_col};
         const int64_t nz = job.nnz;
         auto build_side = [&](int si, hipStream_t st) {
             TileDev &td = side[si].tile;
@@ -593,7 +599,7 @@ template <typename T> struct Engine final : schpf_ctx {
                     fprintf(stderr, "[schpf_hip]   balanced windows, side %d: %d sections of %d windows, %.3f s\n", si,
                             geo.n_sections, geo.D, now_s() - tb);
             }
-            schpf::build_tile_plan_device((void *)st, nz, d_major, d_minor, d_val.as<float>(),
+            schpf::build_tile_plan_device((void *)st, nz, d_major, d_minor, d_val,
                                           presorted, job.packed_ok, n_major, n_minor_plan,
                                           sh, td.host, &e, &eb, &s, &o);
             td.entries.adopt(e, eb);
@@ -767,8 +773,8 @@ template <typename T> struct Engine final : schpf_ctx {
                                          src->rows_val.as<float>(), d_dp.as<int64_t>(), d_row.as<int>(), d_col.as<int>(),
                                          d_val.as<float>(), stream));
         use_tile = true;
-        plan_shapes(job, nullptr, nullptr);
-        tiles_from_device_coo(job, d_row, d_col, d_val);
+        plan_shapes(job, nullptr);
+        tiles_from_device_coo(job, d_row.as<int32_t>(), d_col.as<int32_t>(), d_val.as<float>());
         holds_matrix(side[0].tile.n_wave_out, false);
     }
 
@@ -836,40 +842,71 @@ template <typename T> struct Engine final : schpf_ctx {
         use_tile = want_tile;
         int64_t n_out;
         DevBuf d_val;   // the values on the device: beside the indices for the device builder, afterwards for the others
-        if (use_tile) {
-            plan_shapes(job, row, col);
-            if (device_plans) {
-                schpf::coo_order_flags(nnz, row, col, job.sorted[0], job.sorted[1]);
-                d_val.alloc((size_t)nnz * 4);
-                if (nnz > 0) HIPCHK(hipMemcpyAsync(d_val.p, v.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, stream));
-                early.join();                                  // the indices went up beside the validation pass
-                if (!early.error.empty()) throw HipError(early.error);
-                const double t1 = now_s();
-                tiles_from_device_coo(job, early.d_row, early.d_col, d_val);
-                if (tuning.verbose)
-                    fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
-                            "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
-                            t1 - t_valid, early.seconds, now_s() - t1, (side[0].tile.entries.bytes + side[1].tile.entries.bytes) * 1e-9);
-            } else tiles_from_host_coo(job, row, col, v.data());
+        if (device_plans) {
+            plan_shapes(job, host_samples(job, row, col));
+            schpf::coo_order_flags(nnz, row, col, job.sorted[0], job.sorted[1]);
+            d_val.alloc((size_t)nnz * 4);
+            if (nnz > 0) HIPCHK(hipMemcpyAsync(d_val.p, v.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, stream));
+            early.join();                                  // the indices went up beside the validation pass
+            if (!early.error.empty()) throw HipError(early.error);
+            const double t1 = now_s();
+            tiles_from_device_coo(job, static_cast<const int32_t *>(early.d_row.p), static_cast<const int32_t *>(early.d_col.p), d_val.as<float>());
+            if (tuning.verbose)
+                fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
+                        "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
+                        t1 - t_valid, early.seconds, now_s() - t1, (side[0].tile.entries.bytes + side[1].tile.entries.bytes) * 1e-9);
             n_out = std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);   // the loss pass sweeps either plan (loss_side)
-        } else {
-            const int32_t *const idx[2] = {row, col};
-            const int chunk = schpf::gather_chunk_len(problem(job));
-            for (int s = 0; s < 2; ++s)   // windows: by the size of the minor side's table
-                build_plan(side[s].plan, nnz, idx[s], idx[1 - s], v.data(), side[s].n, side[1 - s].n,
-                           schpf::pick_windows((size_t)side[1 - s].n * KP * sizeof(T)), chunk);
-            n_out = side[0].plan.n_waves;   // the gather loss pass always sweeps the cell plan (loss_side)
-        }
+        } else n_out = plans_from_host_coo(job, row, col, v.data());
         const double t_plans = now_s();
         // the device builder's values are still resident: no second trip over PCIe.  Host-built plans: they go up now
         if (!device_plans) upload(d_val, v, stream);
-        const double count_seconds = loss_constants(d_val.as<float>());
-        if (device_plans && want_rows) {   // the (row, col)-sorted copy minibatches gather their rows from
+        const double count_seconds = finish_upload(job, device_plans ? static_cast<const int32_t *>(early.d_col.p) : nullptr, d_val.as<float>(), n_out);
+        d_val.release();
+        if (tuning.verbose)
+            fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads); "
+                    "ELBO count sums %.4f s of it\n",
+                    (long long)nnz, t_valid - t_start, t_plans - t_valid, now_s() - t_plans, schpf::host_threads(),
+                    count_seconds);
+    }
+
+    // the task-range model's samples from a COO on the host
+    schpf::SampleHistograms host_samples(const UploadJob &job, const int32_t *row, const int32_t *col) const
+    {
+        return [this, &job, row, col](int64_t stride, std::vector<int32_t> hist[2]) {
+            hist[0] = schpf::sample_histogram(job.nnz, row, N, stride);
+            hist[1] = schpf::sample_histogram(job.nnz, col, G, stride);
+        };
+    }
+
+    // Both plans from the host builders over a COO on the host: tile plans (SCHPF_DEVICE_PLAN=0) or gather plans.
+    // Returns the doubles a loss pass leaves in wave_out
+    int64_t plans_from_host_coo(UploadJob &job, const int32_t *row, const int32_t *col, const float *val)
+    {
+        if (use_tile) {
+            plan_shapes(job, host_samples(job, row, col));
+            tiles_from_host_coo(job, row, col, val);
+            return std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);   // the loss pass sweeps either plan (loss_side)
+        }
+        const int32_t *const idx[2] = {row, col};
+        const int chunk = schpf::gather_chunk_len(problem(job));
+        for (int s = 0; s < 2; ++s)   // windows: by the size of the minor side's table
+            build_plan(side[s].plan, job.nnz, idx[s], idx[1 - s], val, side[s].n, side[1 - s].n,
+                       schpf::pick_windows((size_t)side[1 - s].n * KP * sizeof(T)), chunk);
+        return side[0].plan.n_waves;   // the gather loss pass always sweeps the cell plan (loss_side)
+    }
+
+    // What every whole-matrix upload does once its plans stand: the loss constants from the values on the device, the
+    // (row, col)-sorted copy minibatches gather their rows from (d_col: the column indices on the device in the
+    // caller's order, or nullptr where the plans were built on the host), and the engine holds the matrix.  Returns
+    // the wall time of the count sums
+    double finish_upload(const UploadJob &job, const int32_t *d_col, const float *d_val, int64_t n_out)
+    {
+        const double count_seconds = loss_constants(d_val);
+        if (d_col && want_rows) {
             rows_col.alloc((size_t)nnz * 4); rows_val.alloc((size_t)nnz * 4);
             const TileDev &tc = side[0].tile;   // the cell plan's order; rows_ptr's host copy stays tc.host.mptr
-            HIPCHK(schpf::launch_gather_by_order(tc.order_identity ? nullptr : tc.order_dev.as<int>(),
-                                                 static_cast<const int *>(early.d_col.p), d_val.as<float>(), nnz, rows_col.as<int>(),
-                                                 rows_val.as<float>(), stream));
+            HIPCHK(schpf::launch_gather_by_order(tc.order_identity ? nullptr : tc.order_dev.as<int>(), d_col, d_val, nnz,
+                                                 rows_col.as<int>(), rows_val.as<float>(), stream));
             upload(rows_ptr, tc.host.mptr, stream);
             rows_packed_ok = job.packed_ok;
             HIPCHK(hipStreamSynchronize(stream));
@@ -877,13 +914,100 @@ template <typename T> struct Engine final : schpf_ctx {
         HIPCHK(hipMemcpyAsync(&gammaln_sum, scalars.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost,
                               stream));
         HIPCHK(hipStreamSynchronize(stream));
-        d_val.release();
         holds_matrix(n_out, true);
+        return count_seconds;
+    }
+
+    // The matrix is in HBM already (schpf_upload_coo_device / schpf_upload_csr_device): the stages
+    // upload_coo runs on host threads -- validate + convert, the stored-zero list, the order flags, the task-range
+    // samples -- as device passes (upload_device.h), arriving at tiles_from_device_coo with the job a host upload of the
+    // same entries in the same order makes.  Nothing of O(nnz) crosses PCIe.  Host-built plans (SCHPF_PLAN=gather,
+    // SCHPF_DEVICE_PLAN=0) are the cross-check: the converted triples are staged to the host for those builders.
+    // Errors: the smallest offending entry; an index error goes before a value error.
+    void upload_device(int64_t nnz_, const void *rows, int indptr_kind, const void *col, int idx_kind, const void *val,
+                       int val_kind) override
+    {
+        const double t_start = now_s();
+        const bool csr = indptr_kind >= 0;
+        if (nnz_ < 0 || nnz_ >= (int64_t)1 << 31) throw std::invalid_argument("nnz must be < 2^31");
+        if (val_kind < SCHPF_VAL_I32 || val_kind > SCHPF_VAL_F64) throw std::invalid_argument("unknown value kind");
+        for (int k : {idx_kind, csr ? indptr_kind : idx_kind})
+            if (k != SCHPF_IDX_I32 && k != SCHPF_IDX_I64) throw std::invalid_argument("unknown index kind");
+        forget_matrix();
+        UploadJob job;
+        job.nnz = nnz_;
+        job.balance = want_tile && schpf::balance_windows(problem(job), tuning);
+        n_rounded = 0; n_zero = 0;
+        // engine-owned int32 / float32 copies, only of what the caller did not hand over in that type already (an empty
+        // matrix may come with NULL pointers: the builders then get the engine's own empty buffers)
+        DevBuf own_row, own_col, own_val;
+        if (csr) {
+            if (!schpf::csr_indptr_valid(stream, rows, indptr_kind, N, nnz_))
+                throw std::invalid_argument("CSR indptr must be non-decreasing from 0 to nnz");
+            own_row.alloc((size_t)nnz_ * 4);
+            schpf::csr_expand_rows(stream, rows, indptr_kind, N, nnz_, own_row.as<int32_t>());
+        } else if (idx_kind != SCHPF_IDX_I32 || nnz_ == 0) own_row.alloc((size_t)nnz_ * 4);
+        if (idx_kind != SCHPF_IDX_I32 || nnz_ == 0) own_col.alloc((size_t)nnz_ * 4);
+        if (val_kind != SCHPF_VAL_F32 || nnz_ == 0) own_val.alloc((size_t)nnz_ * 4);
+        const schpf::ConvertStats cs =
+            schpf::convert_coo_device(stream, nnz_, csr ? own_row.p : rows, csr ? SCHPF_IDX_I32 : idx_kind, col, idx_kind, val,
+                                      val_kind, N, G, csr ? nullptr : own_row.as<int32_t>(), own_col.as<int32_t>(),
+                                      own_val.as<float>());
+        if (cs.first_bad_index >= 0)
+            throw std::invalid_argument("COO index out of range at entry " + std::to_string(cs.first_bad_index));
+        if (cs.first_bad_value >= 0)
+            throw std::invalid_argument("X.data must be finite and >= 0; offending entry " + std::to_string(cs.first_bad_value));
+        const int32_t *d_row = own_row.p ? own_row.as<int32_t>() : static_cast<const int32_t *>(rows);
+        const int32_t *d_col = own_col.p ? own_col.as<int32_t>() : static_cast<const int32_t *>(col);
+        const float *d_val = own_val.p ? own_val.as<float>() : static_cast<const float *>(val);
+        job.packed_ok = cs.packed_ok;
+        job.sorted[0] = cs.sorted[0]; job.sorted[1] = cs.sorted[1];
+        n_rounded = cs.rounded; n_zero = cs.zeros;
+        zero_row.alloc((size_t)n_zero * 4); zero_col.alloc((size_t)n_zero * 4);
+        schpf::compact_zeros_device(stream, nnz_, d_row, d_col, val, val_kind, n_zero, zero_row.as<int32_t>(), zero_col.as<int32_t>());
+        const double t_valid = now_s();
+        nnz = nnz_;
+        use_tile = want_tile;
+        const bool device_plans = want_tile && tuning.device_plan;
+        int64_t n_out;
+        double t_shapes = t_valid;
+        if (device_plans) {
+            plan_shapes(job, [&](int64_t stride, std::vector<int32_t> hist[2]) {
+                hist[0].resize((size_t)N); hist[1].resize((size_t)G);
+                schpf::sample_histograms_device(stream, nnz, d_row, d_col, N, G, stride, hist[0].data(), hist[1].data());
+            });
+            t_shapes = now_s();
+            tiles_from_device_coo(job, d_row, d_col, d_val);
+            n_out = std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);
+        } else {
+            schpf::BigVec<int32_t> h_row((size_t)nnz), h_col((size_t)nnz);
+            schpf::BigVec<float> h_val((size_t)nnz);
+            if (nnz > 0) {
+                HIPCHK(hipMemcpyAsync(h_row.data(), d_row, (size_t)nnz * 4, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(h_col.data(), d_col, (size_t)nnz * 4, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipMemcpyAsync(h_val.data(), d_val, (size_t)nnz * 4, hipMemcpyDeviceToHost, stream));
+            }
+            HIPCHK(hipStreamSynchronize(stream));
+            n_out = plans_from_host_coo(job, h_row.data(), h_col.data(), h_val.data());
+        }
+        const double t_plans = now_s();
+        const double count_seconds = finish_upload(job, device_plans ? d_col : nullptr, d_val, n_out);
         if (tuning.verbose)
-            fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads); "
-                    "ELBO count sums %.4f s of it\n",
-                    (long long)nnz, t_valid - t_start, t_plans - t_valid, now_s() - t_plans, schpf::host_threads(),
-                    count_seconds);
+            fprintf(stderr, "[schpf_hip] upload_%s_device nnz=%lld: %svalidate + convert + zeros %.3f s, order flags in it, task-range "
+                    "samples %.3f s, plans %.3f s%s, gammaln %.3f s; ELBO count sums %.4f s of it\n",
+                    csr ? "csr" : "coo", (long long)nnz, csr ? "row expansion + " : "", t_valid - t_start, t_shapes - t_valid,
+                    t_plans - t_shapes, device_plans ? "" : " (staged to the host builders)", now_s() - t_plans, count_seconds);
+    }
+
+    // Row and column sums of the matrix the engine holds: the ELBO's count sums (loss_constants), N + G doubles
+    void marginals(double *row_sums, double *col_sums) override
+    {
+        need_coo();
+        need_loss_constants();
+        double *const out[2] = {row_sums, col_sums};
+        for (int s = 0; s < 2; ++s)
+            if (out[s]) HIPCHK(hipMemcpyAsync(out[s], side[s].count.p, (size_t)side[s].n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
     }
 
     // SCHPF_XI / THETA / ETA / BETA -> the side's capacity (xi, eta) or loading (theta, beta) buffer
@@ -900,20 +1024,22 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         return (size_t)side[axis_of(which)].n * (is_loading(which) ? (size_t)K : 1) * sizeof(T);
     }
-    void set_state(int which, const void *shape, const void *rate) override
+    void set_state(int which, const void *shape, const void *rate, bool dev) override
     {
         const size_t b = state_bytes(which);
-        if (shape) HIPCHK(hipMemcpyAsync(state_buf(which, false).p, shape, b, hipMemcpyHostToDevice, stream));
-        if (rate) HIPCHK(hipMemcpyAsync(state_buf(which, true).p, rate, b, hipMemcpyHostToDevice, stream));
+        const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        if (shape) HIPCHK(hipMemcpyAsync(state_buf(which, false).p, shape, b, kind, stream));
+        if (rate) HIPCHK(hipMemcpyAsync(state_buf(which, true).p, rate, b, kind, stream));
         HIPCHK(hipStreamSynchronize(stream));
         if (is_loading(which)) side[axis_of(which)].dirty = true;
         // the graph reads the parameters through fixed pointers: still valid; only xi/eta shapes are constants
     }
-    void get_state(int which, void *shape, void *rate) override
+    void get_state(int which, void *shape, void *rate, bool dev) override
     {
         const size_t b = state_bytes(which);
-        if (shape) HIPCHK(hipMemcpyAsync(shape, state_buf(which, false).p, b, hipMemcpyDeviceToHost, stream));
-        if (rate) HIPCHK(hipMemcpyAsync(rate, state_buf(which, true).p, b, hipMemcpyDeviceToHost, stream));
+        const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (shape) HIPCHK(hipMemcpyAsync(shape, state_buf(which, false).p, b, kind, stream));
+        if (rate) HIPCHK(hipMemcpyAsync(rate, state_buf(which, true).p, b, kind, stream));
         HIPCHK(hipStreamSynchronize(stream));
     }
 
@@ -1531,6 +1657,31 @@ int schpf_set_state(schpf_ctx *ctx, int which, const void *shape, const void *ra
 int schpf_get_state(schpf_ctx *ctx, int which, void *shape, void *rate)
 {
     CTX_CALL(ctx->get_state(which, shape, rate));
+}
+int schpf_set_state_device(schpf_ctx *ctx, int which, const void *shape, const void *rate)
+{
+    CTX_CALL(ctx->set_state(which, shape, rate, true));
+}
+int schpf_get_state_device(schpf_ctx *ctx, int which, void *shape, void *rate)
+{
+    CTX_CALL(ctx->get_state(which, shape, rate, true));
+}
+int schpf_upload_coo_device(schpf_ctx *ctx, int64_t nnz, const void *row, const void *col, int idx_kind, const void *val,
+                            int val_kind)
+{
+    if (nnz > 0 && (!row || !col || !val)) return fail("row, col and val must be device pointers, not NULL");
+    CTX_CALL(ctx->upload_device(nnz, row, -1, col, idx_kind, val, val_kind));
+}
+int schpf_upload_csr_device(schpf_ctx *ctx, int64_t nnz, const void *indptr, int indptr_kind, const void *indices,
+                            int idx_kind, const void *val, int val_kind)
+{
+    if (!indptr || (nnz > 0 && (!indices || !val))) return fail("indptr, indices and val must be device pointers, not NULL");
+    if (indptr_kind != SCHPF_IDX_I32 && indptr_kind != SCHPF_IDX_I64) return fail("unknown index kind");
+    CTX_CALL(ctx->upload_device(nnz, indptr, indptr_kind, indices, idx_kind, val, val_kind));
+}
+int schpf_marginals(schpf_ctx *ctx, double *row_sums, double *col_sums)
+{
+    CTX_CALL(ctx->marginals(row_sums, col_sums));
 }
 int schpf_init_phi_host(schpf_ctx *ctx, const double *xphi) { CTX_CALL(ctx->init_phi_host(xphi)); }
 int schpf_init_phi_device(schpf_ctx *ctx, uint64_t seed) { CTX_CALL(ctx->init_phi_device(seed)); }

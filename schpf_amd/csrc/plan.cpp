@@ -525,7 +525,7 @@ void tile_plan_begin(TilePlanHost &P, int64_t nnz, int n_major, int n_minor, con
     P.steps.assign((size_t)P.n_blocks * P.wpb * W, 0);
 }
 
-std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major, int rows_per_block, int64_t stride)
+std::vector<int32_t> sample_histogram(int64_t nnz, const int32_t *major, int n_major, int64_t stride)
 {
     stride = std::max<int64_t>(1, stride);
     const int64_t n_samples = (nnz + stride - 1) / stride;
@@ -539,13 +539,19 @@ std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major,
         }
     });
     std::vector<int32_t> &count = local[0];
-    int32_t longest = 0;
     for (int m = 0; m < n_major; ++m) {
         int32_t c = 0;
         for (int t = 0; t < nth; ++t) c += local[(size_t)t][(size_t)m];
         count[(size_t)m] = c;
-        longest = std::max(longest, c);
     }
+    return std::move(count);
+}
+
+std::vector<double> block_shares(const std::vector<int32_t> &count, int rows_per_block)
+{
+    const int n_major = (int)count.size();
+    int32_t longest = 0;
+    for (int32_t c : count) longest = std::max(longest, c);
     // rows by decreasing length = a histogram of lengths walked from the top
     std::vector<int64_t> rows_of_length((size_t)longest + 1, 0);
     for (int m = 0; m < n_major; ++m) ++rows_of_length[(size_t)count[(size_t)m]];
@@ -567,6 +573,11 @@ std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major,
     if (total > 0.0)
         for (double &v : share) v /= total;
     return share;
+}
+
+std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major, int rows_per_block, int64_t stride)
+{
+    return block_shares(sample_histogram(nnz, major, n_major, stride), rows_per_block);
 }
 
 RangeChoice choose_task_ranges(const int64_t blocks[2], const int64_t half_windows[2], const bool half_ok[2],

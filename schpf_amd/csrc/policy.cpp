@@ -132,6 +132,14 @@ void pick_workgroup(const Problem &p, const Tuning &tn, int n_major, int n_minor
 bool choose_ranges(const Problem &p, const Tuning &tn, const int32_t *row, const int32_t *col, int ranges[2],
                    int half[2])
 {
+    return choose_ranges(p, tn, [&](int64_t stride, std::vector<int32_t> hist[2]) {
+        hist[0] = sample_histogram(p.nnz, row, p.N, stride);
+        hist[1] = sample_histogram(p.nnz, col, p.G, stride);
+    }, ranges, half);
+}
+
+bool choose_ranges(const Problem &p, const Tuning &tn, const SampleHistograms &sample, int ranges[2], int half[2])
+{
     if (!p.expect_sharded && !tn.dual) return false;
     if (tn.tasks || tn.half >= 2) return false;
     const size_t row_bytes = (size_t)p.KP * p.elem;
@@ -160,8 +168,10 @@ bool choose_ranges(const Problem &p, const Tuning &tn, const int32_t *row, const
     // cell block -- the uniform model's choice -- doubles the iteration, its heaviest block runs last)
     // the blocks the plans will cut: rows per block follow the workgroup (a forced SCHPF_WPB=12 has 12 waves)
     const int64_t stride = std::max<int64_t>(1, p.nnz / 4000000);   // ~4 M samples per orientation: a few ms
-    const std::vector<double> share[2] = {block_shares(p.nnz, row, p.N, (64 / p.LPC) * wpb[0], stride),
-                                          block_shares(p.nnz, col, p.G, (64 / p.LPC) * wpb[1], stride)};
+    std::vector<int32_t> hist[2];
+    sample(stride, hist);
+    const std::vector<double> share[2] = {block_shares(hist[0], (64 / p.LPC) * wpb[0]),
+                                          block_shares(hist[1], (64 / p.LPC) * wpb[1])};
     const RangeChoice c = choose_task_ranges(blocks, half_windows, half_ok, share, (double)p.nnz, resident,
                                              1.7e11 / ((double)p.K * p.elem), 1e-6 * 3, partial_seconds,
                                              p.expect_sharded ? 4 : 6, p.balance_now ? 1.0 : 1.12, 32, p.expect_sharded,

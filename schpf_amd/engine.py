@@ -75,6 +75,7 @@ class DeviceCAVI(object):
         else:
             raise TypeError("dtype must be float64 or float32")
         self.ncells, self.ngenes, self.nfactors = int(ncells), int(ngenes), int(nfactors)
+        self.device = int(device)
         self.nnz = 0
         handle = ctypes.c_void_p()
         if stream is None:
@@ -106,21 +107,47 @@ class DeviceCAVI(object):
 
     # -------------------------------------------------------------------- inputs
     def upload(self, X, warn=True):
-        """X: scipy coo_matrix-like with .row, .col, .data (ncells x ngenes).  warn=False: the caller
-        issues rounding_warning() itself (a helper thread must not touch the warnings machinery)."""
-        if tuple(X.shape) != (self.ncells, self.ngenes):
-            raise ValueError("X has shape %s, engine was created for %s"
-                             % (tuple(X.shape), (self.ncells, self.ngenes)))
-        data = np.ascontiguousarray(X.data)
-        if data.dtype not in _VAL_KINDS:
-            data = data.astype(np.float64)
-        row = np.ascontiguousarray(X.row, dtype=np.int32)
-        col = np.ascontiguousarray(X.col, dtype=np.int32)
-        _lib.check(self._lib.schpf_upload_coo(self._h, data.shape[0], _p(row), _p(col), _p(data),
-                                              _VAL_KINDS[data.dtype]))
-        self.nnz = int(data.shape[0])
+        """X (ncells x ngenes): a SciPy sparse matrix (coo_matrix-like with .row, .col, .data, or anything with
+        .tocoo()), or a torch sparse COO / CSR tensor.  A tensor in GPU memory -- it must be on this engine's device --
+        is handed to the library by pointer and validated, converted and planned there: nothing of it
+        crosses PCIe, and the engine ends up as after an upload of the same entries from the host.  A CPU tensor takes
+        the host path.  warn=False: the caller issues rounding_warning() itself (a helper thread must not touch the
+        warnings machinery)."""
+        from .device_input import classify
+        inp = classify(X, (self.ncells, self.ngenes))
+        if inp.kind == "host":
+            X = inp.matrix
+            data = np.ascontiguousarray(X.data)
+            if data.dtype not in _VAL_KINDS:
+                data = data.astype(np.float64)
+            row = np.ascontiguousarray(X.row, dtype=np.int32)
+            col = np.ascontiguousarray(X.col, dtype=np.int32)
+            _lib.check(self._lib.schpf_upload_coo(self._h, data.shape[0], _p(row), _p(col), _p(data),
+                                                  _VAL_KINDS[data.dtype]))
+        else:
+            import torch
+            if inp.device != self.device:
+                raise ValueError("X is on GPU %d, the engine on GPU %d" % (inp.device, self.device))
+            torch.cuda.current_stream(inp.device).synchronize()     # whatever produced X has finished
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+            if inp.kind == "coo":
+                status = self._lib.schpf_upload_coo_device(self._h, inp.nnz, ptr(inp.major), ptr(inp.minor),
+                                                           inp.minor_kind, ptr(inp.values), inp.value_kind)
+            else:
+                status = self._lib.schpf_upload_csr_device(self._h, inp.nnz, ptr(inp.major), inp.major_kind,
+                                                           ptr(inp.minor), inp.minor_kind, ptr(inp.values),
+                                                           inp.value_kind)
+            _lib.check(status)
+        self.nnz = inp.nnz
         if warn:
             self.rounding_warning(stacklevel=3)
+
+    def marginals(self):
+        """(row_sums, col_sums) of the matrix the engine holds, float64 [ncells] / [ngenes]: what X.sum(1) / X.sum(0)
+        give, from the sums the engine keeps anyway (exact for counts).  A batch engine (upload_rows) raises."""
+        rows, cols = np.empty(self.ncells, np.float64), np.empty(self.ngenes, np.float64)
+        _lib.check(self._lib.schpf_marginals(self._h, rows.ctypes.data_as(_lib._dblp), cols.ctypes.data_as(_lib._dblp)))
+        return rows, cols
 
     def rounding_warning(self, stacklevel=2):
         """Warn (on the calling thread) if the last upload rounded values of X.data to float32."""
@@ -159,16 +186,46 @@ class DeviceCAVI(object):
         n = self.ncells if name in ("xi", "theta") else self.ngenes
         return (n, self.nfactors) if name in ("theta", "beta") else (n,)
 
+    def _torch_dtype(self):
+        import torch
+        return torch.float64 if self.dtype == np.float64 else torch.float32
+
     def set_gamma(self, name, vi_shape, vi_rate):
+        """vi_shape / vi_rate: array-likes (converted to the engine's dtype), or two torch tensors on the engine's GPU of
+        the engine's dtype, which are copied device to device."""
+        from .device_input import on_gpu
         dims = self._dims(name)
+        if on_gpu(vi_shape) or on_gpu(vi_rate):
+            s, r = vi_shape, vi_rate
+            for t in (s, r):
+                if not on_gpu(t) or t.device.index != self.device or t.dtype != self._torch_dtype():
+                    raise ValueError("%s must be two %s tensors on GPU %d" % (name, self._torch_dtype(), self.device))
+                if tuple(t.shape) != dims:
+                    raise ValueError("%s must have shape %s, got %s" % (name, dims, tuple(t.shape)))
+            import torch
+            s, r = s.contiguous(), r.contiguous()
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(self._lib.schpf_set_state_device(self._h, _NAMES[name], ctypes.c_void_p(s.data_ptr()),
+                                                        ctypes.c_void_p(r.data_ptr())))
+            return
         s = np.ascontiguousarray(vi_shape, dtype=self.dtype)
         r = np.ascontiguousarray(vi_rate, dtype=self.dtype)
         if s.shape != dims or r.shape != dims:
             raise ValueError("%s must have shape %s, got %s / %s" % (name, dims, s.shape, r.shape))
         _lib.check(self._lib.schpf_set_state(self._h, _NAMES[name], _p(s), _p(r)))
 
-    def get_gamma(self, name):
+    def get_gamma(self, name, device=False):
+        """(vi_shape, vi_rate) as NumPy arrays; device=True: as torch tensors on the engine's GPU (a device-to-device
+        copy, nothing crosses PCIe)."""
         dims = self._dims(name)
+        if device:
+            import torch
+            s = torch.empty(dims, dtype=self._torch_dtype(), device="cuda:%d" % self.device)
+            r = torch.empty_like(s)
+            torch.cuda.current_stream(self.device).synchronize()
+            _lib.check(self._lib.schpf_get_state_device(self._h, _NAMES[name], ctypes.c_void_p(s.data_ptr()),
+                                                        ctypes.c_void_p(r.data_ptr())))
+            return s, r
         s = np.empty(dims, dtype=self.dtype)
         r = np.empty(dims, dtype=self.dtype)
         _lib.check(self._lib.schpf_get_state(self._h, _NAMES[name], _p(s), _p(r)))

@@ -37,8 +37,8 @@ def projection_loss_function(loss_function, X, nfactors, model_kwargs={}, proj_k
     from .engine import DeviceCAVI
 
     pmodel = scHPF(nfactors=nfactors, **model_kwargs)
-    if not hasattr(X, "row"):
-        X = X.tocoo()
+    from .device_input import as_matrix
+    X = as_matrix(X)
     import os
     if device is None:
         device = int(os.environ.get("SCHPF_DEVICE", "0"))
@@ -100,7 +100,8 @@ def mean_negative_pois_llh(X, *, theta, beta, single_process=False, **kwargs):
 
 def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=None, **kwargs):
     """The evidence lower bound of the variational state (xi, eta, theta, beta) on X, with the responsibilities at
-    their optimum, evaluated on the GPU: X is uploaded, the state set and the ELBO computed.
+    their optimum, evaluated on the GPU: X is uploaded, the state set and the ELBO computed.  X: a SciPy
+    sparse matrix or a torch sparse COO / CSR tensor (DeviceCAVI.upload), as for the per-row means below.
 
     terms=True returns the dict {'data', 'logfac', 'rate', 'cell', 'gene', 'elbo'}, else the total.  `device`: HIP
     device ordinal, default $SCHPF_DEVICE or 0.
@@ -109,8 +110,8 @@ def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=N
     import os
     if device is None:
         device = int(os.environ.get("SCHPF_DEVICE", "0"))
-    if not hasattr(X, "row"):
-        X = X.tocoo()
+    from .device_input import as_matrix
+    X = as_matrix(X)          # a SciPy matrix or a torch sparse tensor (in GPU memory: uploaded from there)
     with DeviceCAVI(X.shape[0], X.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
         eng.upload(X)
         eng.set_hypers(a, c, bp, dp)
@@ -126,8 +127,8 @@ def _rowmean_on_device(X, theta, beta, by, device):
     import os
     if device is None:
         device = int(os.environ.get("SCHPF_DEVICE", "0"))
-    if not hasattr(X, "row"):
-        X = X.tocoo()
+    from .device_input import as_matrix
+    X = as_matrix(X)          # a SciPy matrix or a torch sparse tensor (in GPU memory: uploaded from there)
     with DeviceCAVI(X.shape[0], X.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
         eng.upload(X)
         eng.set_gamma("theta", theta.vi_shape, theta.vi_rate)

@@ -364,12 +364,29 @@ class scHPF(BaseEstimator):
         device too: the matrix goes up once and each batch's rows are gathered in HBM
         (_fit_minibatch); only when the whole matrix does not fit beside its plans are the
         batch's rows sliced on the host and uploaded per iteration, like the reference re-slices.
+        X may also be a torch sparse COO / CSR tensor.  In GPU memory it is uploaded from there (DeviceCAVI.upload,
+        DESIGN.md 13): the engine is made first, bp / dp come from its marginals(), the draws follow in the usual
+        order -- equal seeds give the model of a fit of the same matrix from SciPy with init='device', bit for bit;
+        init='auto' means 'device'; init='numpy', batchsize and several devices raise ValueError.
         `elbo_out`, a list: the ELBO at every loss check is appended to it (fit / project record_elbo).
         Returns (bp, dp, xi, eta, theta, beta, loss) like the reference.
         """
         assert loss_smoothing > 0
-        if not hasattr(X, "row"):
-            X = X.tocoo()
+        from .device_input import classify, is_torch_tensor, on_gpu
+        on_device = on_gpu(X)      # a torch sparse tensor in GPU memory: uploaded from there (DESIGN.md 13)
+        if on_device:
+            nnz = classify(X).nnz
+            if init == "numpy":
+                raise ValueError("init='numpy' draws the t=0 responsibilities from X.data on the host; a matrix in GPU "
+                                 "memory is fitted with init='device' (or 'auto')")
+            if batchsize is not None:
+                raise ValueError("minibatch fits (batchsize=...) slice X on the host: pass a SciPy matrix")
+            if devices is not None and len(devices) > 1:
+                raise ValueError("a matrix in GPU memory is fitted on the GPU that holds it: give one device, or pass a "
+                                 "SciPy matrix to shard it")
+        else:
+            X = classify(X).matrix if is_torch_tensor(X) else (X if hasattr(X, "row") else X.tocoo())
+            nnz = X.data.shape[0]
         batched = batchsize is not None and 1 < batchsize <= X.shape[0]
         if elbo_out is not None and batchsize is not None:
             raise ValueError("record_elbo needs full-data iterations: a minibatch iteration (batchsize) is not "
@@ -388,14 +405,37 @@ class scHPF(BaseEstimator):
         # uniform draws for the four Gammas: ~0.06 s) does not depend on the device: run them side by
         # side.  The library calls release the GIL; NumPy's RNG is only touched on this thread.
         early = None
-        if engine is None and not batched and not (devices is not None and len(devices) > 1):
-            early = _EarlyUpload(X, nfactors, model_dtype, device)
-        try:
-            bp, dp, xi, eta, theta, beta = self._setup(X, freeze_genes, reinit)
-        except BaseException:
-            if early is not None:
-                early.abandon()
-            raise
+        marginals = None
+        if on_device:
+            # the other way round: the empirical bp / dp come from the engine that holds the matrix (its count sums),
+            # so the engine is made and X uploaded first, on this thread; then _setup draws, in the same order
+            if engine is None:
+                engine = DeviceCAVI(ncells, ngenes, nfactors, dtype=model_dtype, device=device)
+                try:
+                    engine.upload(X)
+                except BaseException:
+                    engine.close()
+                    raise
+                own_upload = True
+            else:
+                own_upload = False
+            try:
+                if self.bp is None or (self.dp is None and not freeze_genes):
+                    marginals = engine.marginals()
+                bp, dp, xi, eta, theta, beta = self._setup(X, freeze_genes, reinit, marginals=marginals)
+            except BaseException:
+                if own_upload:
+                    engine.close()
+                raise
+        else:
+            if engine is None and not batched and not (devices is not None and len(devices) > 1):
+                early = _EarlyUpload(X, nfactors, model_dtype, device)
+            try:
+                bp, dp, xi, eta, theta, beta = self._setup(X, freeze_genes, reinit)
+            except BaseException:
+                if early is not None:
+                    early.abandon()
+                raise
         # the hierarchical shapes are constants of the model (scHPF_.py:616-618)
         xi.vi_shape[:] = ap + nfactors * a
         if not freeze_genes:
@@ -416,8 +456,8 @@ class scHPF(BaseEstimator):
             return self._fit_minibatch(X, bp, dp, xi, eta, theta, beta, monitor, freeze_genes, reinit,
                                        loss_function, max_iter, check_freq, checkstep_function, verbose,
                                        batchsize, beta_theta_simultaneous, device)
-        own_engine = engine is None
-        sharded = own_engine and devices is not None and len(devices) > 1
+        own_engine = engine is None or (on_device and own_upload)
+        sharded = not on_device and own_engine and devices is not None and len(devices) > 1
         if sharded:
             from .sharded import ThreadedShards
             import os
@@ -426,12 +466,12 @@ class scHPF(BaseEstimator):
         elif early is not None:
             eng = early.result()                     # the engine with X uploaded (raises what the upload raised)
         else:
-            eng = DeviceCAVI(ncells, ngenes, nfactors, dtype=model_dtype, device=device) if own_engine else engine
+            eng = DeviceCAVI(ncells, ngenes, nfactors, dtype=model_dtype, device=device) if engine is None else engine
         if not own_engine and ((eng.ncells, eng.ngenes, eng.nfactors) != (ncells, ngenes, nfactors)
-                               or eng.dtype != model_dtype or eng.nnz != X.data.shape[0]):
+                               or eng.dtype != model_dtype or eng.nnz != nnz):
             raise ValueError("engine was built for a different matrix, nfactors or dtype")
         try:
-            if own_engine and not sharded and early is None:
+            if own_engine and not sharded and early is None and not on_device:
                 eng.upload(X)
             eng.set_hypers(a, c, bp, dp)
             for name, g in (("xi", xi), ("theta", theta), ("eta", eta), ("beta", beta)):
@@ -446,8 +486,8 @@ class scHPF(BaseEstimator):
             t = 0
             while t < max_iter:
                 if t == 0 and reinit:   # random responsibilities, scHPF_.py:652-655
-                    use_host = init == "numpy" or (init == "auto"
-                                                   and X.data.shape[0] * nfactors <= _HOST_PHI_LIMIT)
+                    use_host = not on_device and (init == "numpy" or (init == "auto"
+                                                                      and nnz * nfactors <= _HOST_PHI_LIMIT))
                     if use_host:
                         random_phi = np.random.dirichlet(np.ones(nfactors), X.data.shape[0])
                         eng.init_phi_host(X.data[:, None] * random_phi)
@@ -618,13 +658,13 @@ class scHPF(BaseEstimator):
             eta, beta = gene_side()
         return (bp, dp, xi, eta, theta, beta, monitor.loss)
 
-    def _setup(self, X, freeze_genes=False, reinit=True, clip=True):
+    def _setup(self, X, freeze_genes=False, reinit=True, clip=True, marginals=None):
         """Empirical bp/dp and (re)initialised Gammas, draw order xi, theta, eta, beta
-        (scHPF_.py:783-844)."""
+        (scHPF_.py:783-844).  marginals: (row sums, column sums) of X where the caller has them already."""
         nfactors, (ncells, ngenes) = self.nfactors, X.shape
         a, ap, c, cp = self.a, self.ap, self.c, self.cp
         xi, eta, theta, beta = self.xi, self.eta, self.theta, self.beta
-        bp, dp = self._get_empirical_hypers(X, freeze_genes, clip)
+        bp, dp = self._get_empirical_hypers(X, freeze_genes, clip, marginals=marginals)
 
         make = HPF_Gamma.random_gamma_factory
         if reinit or xi is None:
@@ -643,12 +683,12 @@ class scHPF(BaseEstimator):
                 beta = make((ngenes, nfactors), c, dp, dtype=self.dtype)
         return (bp, dp, xi, eta, theta, beta)
 
-    def _get_empirical_hypers(self, X, freeze_genes=False, clip=True):
+    def _get_empirical_hypers(self, X, freeze_genes=False, clip=True, marginals=None):
         """bp = ap * mean/var of the cell sums, dp = cp * mean/var of the gene sums, only where
         unset; dp is clipped to bp/1000 (scHPF_.py:847-879)."""
         bp, dp = self.bp, self.dp
 
-        marginals = []
+        marginals = list(marginals) if marginals is not None else []
 
         def mean_over_var(axis):
             # X.sum(axis) of the reference, both axes in one threaded pass of the library
