@@ -300,6 +300,33 @@ int schpf_upload_info(schpf_ctx *ctx, int64_t info[4]);
 int schpf_coo_marginals(int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int val_kind,
                         int ncells, int ngenes, double *row_sums, double *col_sums);
 
+/* Count thinning (count splitting): every stored count x is split into x_test ~ Binomial(x, frac) and
+ * x_train = x - x_test, so that a model fitted to the train matrix can be scored on the test matrix (for x ~ Poisson(l)
+ * the parts are independent Poisson((1 - frac) l) and Poisson(frac l)).  The draw of an entry depends on (seed, frac, row,
+ * col, x) alone -- philox.h: Philox4x32-10 keyed by the seed, counter (row, col, block, 0), trial t goes to the test
+ * matrix iff word t % 4 of block t / 4 is < floor(frac * 2^32) -- not on the entry's position, the index or value type,
+ * or where the matrix lives.  Entries that share a coordinate share a stream: sum duplicates first.
+ *   train / test: int32[nnz], the parts in the order of the entries.  stats = {train nonzeros, test nonzeros, sum of
+ *   train, sum of test}.  0 < frac < 1 and frac >= 2^-32; every value a non-negative integer <= 2^24 (float values must
+ *   be integral), every index in [0, 2^31).  An invalid entry is never drawn: the call fails with "COO index out of range
+ *   at entry N" or "thinning needs integer counts in [0, 2^24]; offending entry N", N the smallest offending entry of
+ *   the whole matrix, an index error before a value error, and the outputs are then unspecified.  nnz = 0 succeeds with
+ *   zero statistics; nnz >= 2^31 and NULL pointers with nnz > 0 are refused.
+ * _device: row / col (of idx_kind) / val (of val_kind) and train / test are DEVICE pointers on `device`, read and written
+ *   in place -- nothing of O(nnz) crosses PCIe; stream as in schpf_create (NULL = a stream of the call's own), on which the
+ *   inputs must be complete or ordered; synchronised before the call returns.
+ * schpf_thin_counts: host pointers; the entries are staged through the device in slabs; the same result. */
+int schpf_thin_counts_device(int device, void *stream, int64_t nnz, const void *row, const void *col, int idx_kind,
+                             const void *val, int val_kind, double frac, uint64_t seed, int32_t *train, int32_t *test,
+                             int64_t stats[4]);
+int schpf_thin_counts(int device, int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int val_kind,
+                      double frac, uint64_t seed, int32_t *train, int32_t *test, int64_t stats[4]);
+/* Test hooks (host only, no GPU needed): the serial restatement of the thinning kernels on the same header, which they
+ * must match bit for bit, and one block of the generator. */
+int schpf_debug_thin_counts(int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int val_kind,
+                            double frac, uint64_t seed, int32_t *train, int32_t *test, int64_t stats[4]);
+int schpf_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
+
 /* Test hook (host only, no GPU needed): build one sweep plan from (major, minor, val) and expand
  * it back into per-nonzero records in storage order -- the major/minor/val it will be processed
  * with, the partials row (natural chunk id) it accumulates into and the wavefront that streams

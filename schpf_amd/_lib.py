@@ -75,6 +75,10 @@ SIGNATURES = {
     "schpf_plan_info": [_vp, _i64p],
     "schpf_upload_info": [_vp, _i64p],
     "schpf_coo_marginals": [_i64, _vp, _vp, _vp, _int, _int, _int, _vp, _vp],
+    "schpf_thin_counts_device": [_int, _vp, _i64, _vp, _vp, _int, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
+    "schpf_thin_counts": [_int, _i64, _vp, _vp, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
+    "schpf_debug_thin_counts": [_i64, _vp, _vp, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
+    "schpf_debug_philox": [_vp, _vp, _vp],
     "schpf_debug_plan_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _i64p],
     "schpf_debug_tile_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int,
@@ -208,7 +212,8 @@ def ipc_hint():
 def check(status):
     if status != 0:
         msg = load().schpf_last_error().decode("utf-8", "replace")
-        if status != ERR_NO_MEMORY and ("must be" in msg or "out of range" in msg or "unknown" in msg):
+        if status != ERR_NO_MEMORY and ("must be" in msg or "out of range" in msg or "unknown" in msg
+                                        or "thinning needs" in msg):
             raise ValueError(msg)
         raise SchpfHipError(msg, status)
 

@@ -51,6 +51,11 @@ def _add_train_options(train, nargs_k=None):
                        help="Reproject the data onto the fixed gene parameters before model selection.")
     train.add_argument("--quiet", dest="verbose", action="store_false", default=True,
                        help="Do not print intermediate losses.")
+    train.add_argument("--thin", type=float, default=None, metavar="FRAC",
+                       help="Split every count into train and test counts (test ~ Binomial(count, FRAC)), fit on the "
+                            "train counts, check convergence and choose the model by the held-out loss on the test "
+                            "counts; writes thin_train.mtx and thin_test.mtx beside the model (this build's addition).")
+    train.add_argument("--thin-seed", type=int, default=0, metavar="N", help="Seed of the --thin split. [0]")
     train.add_argument("--devices", type=int, nargs="+", default=None,
                        help="HIP device ordinals to spread the restarts over (this build's addition).")
 
@@ -195,6 +200,17 @@ def _train(args, outprefix):
         vcells = _load_matrix(args.validation_cells)
         print(".....found {} validation cells and {} genes in {}".format(vcells.shape[0], vcells.shape[1],
                                                                           args.validation_cells))
+    thin_kwargs = {}
+    if args.thin is not None:       # the split run_trials makes from the same (frac, seed), written out for reuse
+        if vcells is not None:
+            raise ValueError("--thin cannot be combined with --validation-cells")
+        from .thinning import thin_counts
+        print("Thinning counts (test fraction {}, seed {}).....".format(args.thin, args.thin_seed))
+        thin_train, thin_test = thin_counts(train, args.thin, seed=args.thin_seed,
+                                            device=args.devices[0] if args.devices else None)
+        _write_matrix("{}thin_train.mtx".format(outprefix), thin_train)
+        _write_matrix("{}thin_test.mtx".format(outprefix), thin_test)
+        thin_kwargs = dict(thin=args.thin, thin_seed=args.thin_seed)
     print("Running trials.....")
     dtype = np.float32 if args.float32 else np.float64
     pooled = args.cmd != "train"
@@ -213,7 +229,7 @@ def _train(args, outprefix):
                  better_than_n_ago=args.better_than_n_ago, dtype=dtype, verbose=args.verbose,
                  model_kwargs=dict(a=args.a, c=args.c), return_all=args.save_all, reproject=args.reproject,
                  batchsize=args.batchsize, beta_theta_simultaneous=args.beta_theta_simultaneous,
-                 loss_smoothing=args.smooth_loss)
+                 loss_smoothing=args.smooth_loss, **thin_kwargs)
     model, reject = result if args.save_all else (result, None)
     klist = [args.nfactors] if isinstance(args.nfactors, int) else args.nfactors
     if not pooled:                                      # run_trials: one model (and one list of rejects)
@@ -234,6 +250,8 @@ def _train(args, outprefix):
         if args.save_all:
             for j, r in enumerate(reject[i]):
                 joblib.dump(r, stem + "_reject{}.joblib".format(j + 1))
+    if args.thin is None:
+        del args.thin, args.thin_seed   # the arguments file of a run without thinning stays what it was
     cmdfile = "{}train_commandline_args.json".format(outprefix)
     if os.path.exists(cmdfile):
         cmdfile = "{}train_commandline_args.{}.json".format(outprefix, time.strftime("%Y%m%d-%H%M%S"))

@@ -1,5 +1,6 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
-// check the host builders with, and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
+// check the host builders with, the serial restatement of count thinning (thin.hip) and the SCHPF_BACKTRACE crash
+// handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -8,6 +9,7 @@
 #include <thread>
 
 #include "common.h"
+#include "philox.h"
 #include "policy.h"
 
 using namespace schpf;
@@ -231,6 +233,54 @@ int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *mi
         stats[0] = P.n_tasks; stats[1] = P.n_blocks; stats[2] = P.n_windows; stats[3] = P.pstride;
         stats[4] = (int64_t)P.entries.size() / (P.packed ? 1 : 2); stats[5] = P.windows_per_task;
         stats[6] = lds_reads; stats[7] = lds_extra;
+    });
+}
+
+int schpf_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4])
+{
+    if (!counter || !key || !out) return fail("counter, key and out must not be NULL");
+    const schpf::Philox4 b = schpf::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1]);
+    for (int w = 0; w < 4; ++w) out[w] = b.w[w];
+    return 0;
+}
+
+// the kernels of thin.hip restated as one serial loop over the entries: the same predicates, the same draw (philox.h)
+int schpf_debug_thin_counts(int64_t nnz, const int32_t *row, const int32_t *col, const void *val, int val_kind,
+                            double frac, uint64_t seed, int32_t *train, int32_t *test, int64_t stats[4])
+{
+    if (!stats) return fail("stats is NULL");
+    if (nnz < 0 || nnz >= (1ll << 31)) return fail("nnz must be in [0, 2^31)");
+    if (nnz > 0 && (!row || !col || !val || !train || !test)) return fail("row, col, val, train and test must not be NULL");
+    return guarded([&] {
+        if (val_kind < SCHPF_VAL_I32 || val_kind > SCHPF_VAL_F64) throw std::invalid_argument("unknown value kind");
+        uint32_t T = 0;
+        if (!schpf::thin_threshold(frac, &T)) throw std::invalid_argument("frac must be in (0, 1) and at least 2^-32");
+        for (int k = 0; k < 4; ++k) stats[k] = 0;
+        int64_t first_bad_index = -1, first_bad_value = -1;
+        for (int64_t e = 0; e < nnz; ++e) {
+            if (schpf::thin_index_bad(row[e]) || schpf::thin_index_bad(col[e])) {
+                if (first_bad_index < 0) first_bad_index = e;
+            } else if (schpf::thin_value_bad(read_count(val, val_kind, e))) {
+                if (first_bad_value < 0) first_bad_value = e;
+            }
+        }
+        // an index error before a value error, the rule of schpf_upload_coo_device; an invalid matrix is not drawn
+        if (first_bad_index >= 0)
+            throw std::invalid_argument("COO index out of range at entry " + std::to_string(first_bad_index));
+        if (first_bad_value >= 0)
+            throw std::invalid_argument("thinning needs integer counts in [0, 2^24]; offending entry " +
+                                        std::to_string(first_bad_value));
+        const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+        for (int64_t e = 0; e < nnz; ++e) {
+            const uint32_t x = (uint32_t)read_count(val, val_kind, e);
+            const uint32_t hits = schpf::thin_draw((uint32_t)row[e], (uint32_t)col[e], x, k0, k1, T);
+            train[e] = (int32_t)(x - hits);
+            test[e] = (int32_t)hits;
+            stats[0] += x > hits;
+            stats[1] += hits > 0;
+            stats[2] += x - hits;
+            stats[3] += hits;
+        }
     });
 }
 

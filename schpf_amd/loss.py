@@ -13,7 +13,8 @@ import numpy as np
 from .hpf_hip import compute_pois_llh
 
 __all__ = ["loss_function_for_data", "projection_loss_function", "pois_llh_pointwise",
-           "mean_negative_pois_llh", "elbo", "cellmean_negative_pois_llh", "genemean_negative_pois_llh"]
+           "mean_negative_pois_llh", "elbo", "cellmean_negative_pois_llh", "genemean_negative_pois_llh",
+           "thinned_mean_negative_pois_llh"]
 
 
 def loss_function_for_data(loss_function, X):
@@ -96,6 +97,32 @@ def pois_llh_pointwise(X, *, theta, beta, single_process=False, **kwargs):
 def mean_negative_pois_llh(X, *, theta, beta, single_process=False, **kwargs):
     """Mean over the stored nonzeros of X of the negative Poisson log-likelihood."""
     return np.mean(-pois_llh_pointwise(X=X, theta=theta, beta=beta))
+
+
+def thinned_mean_negative_pois_llh(X_test, *, theta, beta, frac, device=None, **kwargs):
+    """Held-out loss of a model fitted to the train part of a thinned matrix (thinning.thin_counts): the
+    mean over the stored entries of X_test of -log Poisson(x_test | s E[theta_i] E[beta_g]), s = frac / (1 - frac) -- the
+    test counts have frac / (1 - frac) times the rate of the train counts.  No kernel of its own: the usual device loss
+    on a theta whose rate is divided by s.  X_test: a SciPy matrix, or a torch sparse tensor (one in GPU memory is
+    uploaded from there; `device` as for the per-row means)."""
+    from .scHPF_ import HPF_Gamma   # late import: scHPF_ imports this module
+    from .device_input import as_matrix, is_torch_tensor
+    if not 0.0 < frac < 1.0:
+        raise ValueError("frac must be in (0, 1), got %r" % (frac,))
+    s = theta.vi_rate.dtype.type(frac / (1.0 - frac))
+    scaled = HPF_Gamma(theta.vi_shape, theta.vi_rate / s)
+    X_test = as_matrix(X_test)
+    if not is_torch_tensor(X_test):
+        return mean_negative_pois_llh(X_test, theta=scaled, beta=beta)
+    from .engine import DeviceCAVI
+    import os
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    with DeviceCAVI(X_test.shape[0], X_test.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
+        eng.upload(X_test)
+        eng.set_gamma("theta", scaled.vi_shape, scaled.vi_rate)
+        eng.set_gamma("beta", beta.vi_shape, beta.vi_rate)
+        return eng.mean_negative_pois_llh()
 
 
 def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=None, **kwargs):

@@ -8,6 +8,10 @@ the device instead of through a host callback.  `run_trials_pool` keeps its sign
 `max_threads` are accepted) but there is no process pool: restarts run back to back on the GPU,
 which is where the time goes; give `devices=[0, 1, ...]` to spread restarts over several GPUs
 (one host thread and one engine per device).
+
+An addition to the reference's arguments: `thin=frac` (with `thin_seed`) splits X once into train and test counts
+(thinning.thin_counts), fits every restart on the train counts and checks convergence and selects by the
+held-out loss on the test counts.
 """
 from functools import partial
 from concurrent.futures import ThreadPoolExecutor
@@ -49,20 +53,37 @@ def _loss_plumbing(X, nfactors, check_freq, vcells, vX, loss_function, single_pr
     return loss_function, ls.loss_function_for_data(loss_function, X if vX is None else vX)
 
 
+def _thin(X, thin, thin_seed, vcells, vX, device):
+    """thin=frac: (X_train, the held-out loss bound to X_test); thin=None: (X, None)."""
+    if thin is None:
+        return X, None
+    if vcells is not None or vX is not None:
+        raise ValueError("thin cannot be combined with vcells / vX: the test counts are the validation data")
+    from .thinning import thin_counts
+    X_train, X_test = thin_counts(X, thin, seed=thin_seed, device=device)
+    return X_train, partial(partial(ls.thinned_mean_negative_pois_llh, frac=thin), X_test)
+
+
 def run_trials(X, nfactors, ntrials=5, min_iter=30, max_iter=1000, check_freq=10, epsilon=0.001,
                better_than_n_ago=5, dtype=np.float64, verbose=True, vcells=None, vX=None,
                loss_function=None, model_kwargs={}, return_all=False, reproject=False,
                reproject_kwargs={}, batchsize=0, beta_theta_simultaneous=False, loss_smoothing=1,
-               device=None):
+               device=None, thin=None, thin_seed=0):
     """Train `ntrials` randomly initialised models, return the one with the lowest final loss
-    (and, with return_all, the others ordered by increasing loss)."""
+    (and, with return_all, the others ordered by increasing loss).  thin=frac: fit on the train counts of a thinned X,
+    the loss is the held-out loss on its test counts."""
     if not hasattr(X, "row"):
         X = X.tocoo()
     ncells, ngenes = X.shape
     if ngenes >= 20000:
         print(_GENE_WARNING.format(ngenes))
     device = _default_device() if device is None else device
-    raw_loss, data_loss_function = _loss_plumbing(X, nfactors, check_freq, vcells, vX, loss_function, False, device)
+    X, thin_loss = _thin(X, thin, thin_seed, vcells, vX, device)
+    if thin_loss is None:
+        raw_loss, data_loss_function = _loss_plumbing(X, nfactors, check_freq, vcells, vX, loss_function, False, device)
+    else:
+        raw_loss, data_loss_function = None, thin_loss
+        reproject_kwargs = dict(reproject_kwargs, loss_function=thin_loss)
     batched = batchsize is not None and 1 < batchsize <= ncells
 
     engine = None
@@ -120,10 +141,10 @@ def run_trials_pool(X, nfactors, ntrials=5, njobs=0, max_threads=None, min_iter=
                     check_freq=10, epsilon=0.001, better_than_n_ago=5, dtype=np.float64, verbose=True,
                     vcells=None, vX=None, loss_function=None, model_kwargs={}, return_all=False,
                     reproject=False, reproject_kwargs={}, batchsize=0, beta_theta_simultaneous=False,
-                    loss_smoothing=1, devices=None):
+                    loss_smoothing=1, devices=None, thin=None, thin_seed=0):
     """`ntrials` restarts for every K in `nfactors` (int or list); per K the model with the lowest
     final loss.  Returns a list of best models (and, with return_all, a list of lists of the
-    rejected ones ordered by increasing loss), like the reference."""
+    rejected ones ordered by increasing loss), like the reference.  thin=frac: as in run_trials, one split for all K."""
     if not hasattr(X, "row"):
         X = X.tocoo()
     if X.shape[1] >= 20000:
@@ -131,10 +152,14 @@ def run_trials_pool(X, nfactors, ntrials=5, njobs=0, max_threads=None, min_iter=
     if isinstance(nfactors, (int, np.integer)):
         nfactors = [int(nfactors)]
     devices = [_default_device()] if not devices else list(devices)
+    X, thin_loss = _thin(X, thin, thin_seed, vcells, vX, devices[0])
     batched = batchsize is not None and 1 < batchsize <= X.shape[0]
 
     def fit_all(K, device, count):
-        _, dlf = _loss_plumbing(X, K, check_freq, vcells, vX, loss_function, True, device)
+        if thin_loss is None:
+            _, dlf = _loss_plumbing(X, K, check_freq, vcells, vX, loss_function, True, device)
+        else:
+            dlf = thin_loss
         engine = None
         if not batched:
             engine = DeviceCAVI(X.shape[0], X.shape[1], K, dtype=dtype, device=device)
