@@ -20,10 +20,29 @@ thread_local std::string schpf::g_err;
 
 namespace {
 
-struct PlanDev {
-    schpf::SweepPlanHost host;  // entries cleared after upload; order/mptr/cptr kept
-    DevBuf entries, slice_off, slice_steps, chunk_major, chunk_natid, wave_slice, cptr, partials;
-    int64_t n_waves = 0, n_chunks = 0, entry_slots = 0;
+// A major row's partial rows -- the K-vectors a sweep accumulates for it, and the records of a MODE_LLH_ROWS pass, which
+// are addressed alike -- are first[row] + j * stride, j < count[row].  Tile plans: one per (row, task) (plan.h pfirst /
+// pcount / pstride); gather plans: the row's consecutive chunks, stride 1
+struct PartialRows { DevBuf rows, first, count; int64_t stride = 1, n = 0; };   // rows: [n, KP] of T
+
+// What the engine asks of a side's plan whatever its kind (Side::active); the builders fill it
+struct PlanFacts {
+    PartialRows part;
+    std::vector<int64_t> mptr;      // run pointers of the (major, minor)-sorted order, on the host (moved out of `host`)
+    // (major, minor)-sorted position -> caller's COO position: on the device (device-built plans), the identity (the
+    // input was already in that order), or on the host (host-built plans; moved out of `host`)
+    DevBuf order_dev; bool order_identity = false; schpf::BigVec<int32_t> order;
+    int64_t launch = 0;             // size of an iteration's sweep launch: tasks (tile) / wavefronts (gather)
+    // doubles a loss / ELBO pass over this plan leaves in wave_out.  Not symmetric: gather plans only ever sweep the cell
+    // side for it (loss_side), so a gather plan of the gene side leaves this 0
+    int64_t n_wave_out = 0, entry_slots = 0;
+    int windows = 0;
+    bool packed = false;            // 8-byte entries (tile plans whose counts all fit 16 bits)
+};
+
+struct PlanDev : PlanFacts {
+    schpf::SweepPlanHost host;  // entries and the per-slice arrays cleared after upload; order / mptr moved to the facts
+    DevBuf entries, slice_off, slice_steps, chunk_major, chunk_natid, wave_slice;
 };
 
 // The tasks a tile sweep launches, one entry per task.  stage_end: only sub-range tasks have one (kernels.h task_stage_end)
@@ -33,9 +52,9 @@ struct TaskList {
     int64_t n = 0;
 };
 
-struct TileDev {
-    schpf::TilePlanHost host;   // entries/steps cleared after upload; order/mptr kept
-    DevBuf entries, steps, block_rows, pfirst, pcount, partials;
+struct TileDev : PlanFacts {
+    schpf::TilePlanHost host;   // entries/steps cleared after upload; order / mptr moved to the facts
+    DevBuf entries, steps, block_rows;
     TaskList tasks;             // the iteration's
     // The loss pass (MODE_LLH) writes no partial rows, so its tasks may be cut finer than the iteration's: sub-ranges of
     // the tasks' window ranges, enough of them for a few rounds of the device (Engine::loss_tasks); n = 0: not cut
@@ -43,12 +62,8 @@ struct TileDev {
     double llh_model = 0.0;     // modelled length of the loss pass on this plan, in step units (0: unknown)
     DevBuf minor_of;            // balanced windows (plan.h): [n_blocks * n_virtual] table row staged at a window position, or empty
     int n_virtual = 0;
-    DevBuf order_dev;           // device-built plans: (major, minor)-sorted position -> caller's COO position
-    bool order_identity = false; //                    ... or the input was already in that order
-    int64_t entry_slots = 0, n_wave_out = 0;
     int threads = 512;
     size_t lds_bytes = 0;
-    bool packed = false;
 };
 
 // Everything the engine holds once per matrix axis.  Engine::side[0] is the cell axis (major = cell: xi, theta), side[1]
@@ -63,6 +78,7 @@ struct Side {
     DevBuf count;                      // ELBO: sum of the stored counts of each row of this axis, double[n]
     PlanDev plan;                      // gather plan with this axis as major
     TileDev tile;                      // tile plan (LDS-staged sweep) with this axis as major
+    PlanFacts *active = &plan;         // whichever of the two the last upload built (Engine::choose_plan)
     bool dirty = true;                 // the tables and column sums are older than the parameters
     Side() = default;
     Side(const Side &) = delete; Side &operator=(const Side &) = delete;
@@ -313,6 +329,11 @@ template <typename T> struct Engine final : schpf_ctx {
     {
         return !prof.on && stream != nullptr && pending_init == 0 && eager_since_upload && !side[0].dirty && !side[1].dirty;
     }
+    void choose_plan(bool tile)   // which kind of plan this upload builds, for both sides
+    {
+        use_tile = tile;
+        for (Side &sd : side) sd.active = tile ? static_cast<PlanFacts *>(&sd.tile) : &sd.plan;
+    }
     // the engine holds no count matrix any more: plans, row copy and captured graphs released; step / loss calls
     // raise until the next successful upload
     void forget_matrix()
@@ -439,18 +460,24 @@ template <typename T> struct Engine final : schpf_ctx {
         schpf::build_sweep_plan(nnz_, major, minor, val, n_major, n_minor, LPC, chunk_len, windows, true,
                                 pd.host);
         auto &h = pd.host;
-        pd.n_waves = h.n_waves;
-        pd.n_chunks = h.n_chunks;
+        pd.launch = h.n_waves;
         pd.entry_slots = (int64_t)h.entries.size() / 2;
+        pd.windows = h.n_windows;
+        // a row's partial rows are its chunks cptr[row] .. cptr[row + 1]
+        std::vector<int32_t> first(h.cptr.begin(), h.cptr.end() - 1), count((size_t)n_major);
+        for (int m = 0; m < n_major; ++m) count[(size_t)m] = h.cptr[(size_t)m + 1] - h.cptr[(size_t)m];
+        pd.part.n = h.n_chunks;   // stride 1
         upload(pd.entries, h.entries, stream);
         upload(pd.slice_off, h.slice_off, stream);
         upload(pd.slice_steps, h.slice_steps, stream);
         upload(pd.chunk_major, h.chunk_major, stream);
         upload(pd.chunk_natid, h.chunk_natid, stream);
         upload(pd.wave_slice, h.wave_slice, stream);
-        upload(pd.cptr, h.cptr, stream);
-        pd.partials.alloc((size_t)std::max<int64_t>(h.n_chunks, 1) * KP * sizeof(T), true, stream);
+        upload(pd.part.first, first, stream);
+        upload(pd.part.count, count, stream);
+        pd.part.rows.alloc((size_t)std::max<int64_t>(h.n_chunks, 1) * KP * sizeof(T), true, stream);
         HIPCHK(hipStreamSynchronize(stream));
+        pd.mptr = std::move(h.mptr); pd.order = std::move(h.order);
         schpf::BigVec<uint32_t>().swap(h.entries);
         std::vector<int32_t>().swap(h.chunk_major);
         std::vector<int32_t>().swap(h.chunk_natid);
@@ -510,18 +537,21 @@ template <typename T> struct Engine final : schpf_ctx {
         td.packed = h.packed;
         loss_tasks(td, job);
         TaskList &tl = td.tasks;
-        tl.n = h.n_tasks;
+        td.launch = tl.n = h.n_tasks;
         td.n_wave_out = std::max<int64_t>(tl.n, td.llh.n) * wpb;
+        td.windows = h.n_windows;
+        td.part.stride = h.pstride; td.part.n = h.n_partial_rows;
         upload(td.block_rows, h.block_rows, stream);
         upload(tl.block, h.task_block, stream);
         upload(tl.w0, h.task_w0, stream);
         upload(tl.w1, h.task_w1, stream);
         upload(tl.wave_off, h.task_wave_off, stream);
         upload(tl.order, h.task_order, stream);
-        upload(td.pfirst, h.pfirst, stream);
-        upload(td.pcount, h.pcount, stream);
-        td.partials.alloc((size_t)std::max<int64_t>(h.n_partial_rows, 1) * KP * sizeof(T), true, stream);
+        upload(td.part.first, h.pfirst, stream);
+        upload(td.part.count, h.pcount, stream);
+        td.part.rows.alloc((size_t)std::max<int64_t>(h.n_partial_rows, 1) * KP * sizeof(T), true, stream);
         HIPCHK(hipStreamSynchronize(stream));
+        td.mptr = std::move(h.mptr); td.order = std::move(h.order);
         std::vector<uint16_t>().swap(h.steps);
         std::vector<int64_t>().swap(h.task_wave_off);
     }
@@ -706,7 +736,7 @@ template <typename T> struct Engine final : schpf_ctx {
             Side &sd = side[s];
             DevBuf scratch, mp;
             const int *ord = nullptr;
-            if (!use_tile || !sd.tile.order_identity) ord = order_of(s, scratch);
+            if (!sd.active->order_identity) ord = order_of(s, scratch);
             upload(mp, major_ptr(s), stream);
             sd.count.alloc((size_t)sd.n * sizeof(double));
             HIPCHK(schpf::launch_count_sums(d_values, ord, mp.as<int64_t>(), sd.n, sd.count.as<double>(), stream));
@@ -749,7 +779,7 @@ template <typename T> struct Engine final : schpf_ctx {
         if (src->G != G || src->K != K) throw std::invalid_argument("source and batch engine differ in genes or factors");
         if (n_rows != N) throw std::invalid_argument("n_rows must be the number of cells the batch engine was created with");
         if (!want_tile) throw std::invalid_argument("upload_rows needs the tile plan");
-        const std::vector<int64_t> &sp = src->side[0].tile.host.mptr;   // host copy of src->rows_ptr
+        const std::vector<int64_t> &sp = src->side[0].tile.mptr;   // host copy of src->rows_ptr
         std::vector<int64_t> dp((size_t)n_rows + 1, 0);
         for (int i = 0; i < n_rows; ++i) {
             if (rows[i] < 0 || rows[i] >= src->N) throw std::invalid_argument("batch row out of range");
@@ -772,7 +802,7 @@ template <typename T> struct Engine final : schpf_ctx {
         HIPCHK(schpf::launch_gather_rows(d_rows.as<int>(), n_rows, src->rows_ptr.as<int64_t>(), src->rows_col.as<int>(),
                                          src->rows_val.as<float>(), d_dp.as<int64_t>(), d_row.as<int>(), d_col.as<int>(),
                                          d_val.as<float>(), stream));
-        use_tile = true;
+        choose_plan(true);
         plan_shapes(job, nullptr);
         tiles_from_device_coo(job, d_row.as<int32_t>(), d_col.as<int32_t>(), d_val.as<float>());
         holds_matrix(side[0].tile.n_wave_out, false);
@@ -839,8 +869,7 @@ template <typename T> struct Engine final : schpf_ctx {
         upload(zero_col, zcol, stream);
         const double t_valid = now_s();
         nnz = nnz_;
-        use_tile = want_tile;
-        int64_t n_out;
+        choose_plan(want_tile);
         DevBuf d_val;   // the values on the device: beside the indices for the device builder, afterwards for the others
         if (device_plans) {
             plan_shapes(job, host_samples(job, row, col));
@@ -855,12 +884,11 @@ template <typename T> struct Engine final : schpf_ctx {
                 fprintf(stderr, "[schpf_hip]   tile plans on the device: ranges + H2D of the values %.3f s (indices: %.3f s on the "
                         "helper thread, from the start of the upload), both plans %.3f s (%.2f GB entries)\n",
                         t1 - t_valid, early.seconds, now_s() - t1, (side[0].tile.entries.bytes + side[1].tile.entries.bytes) * 1e-9);
-            n_out = std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);   // the loss pass sweeps either plan (loss_side)
-        } else n_out = plans_from_host_coo(job, row, col, v.data());
+        } else plans_from_host_coo(job, row, col, v.data());
         const double t_plans = now_s();
         // the device builder's values are still resident: no second trip over PCIe.  Host-built plans: they go up now
         if (!device_plans) upload(d_val, v, stream);
-        const double count_seconds = finish_upload(job, device_plans ? static_cast<const int32_t *>(early.d_col.p) : nullptr, d_val.as<float>(), n_out);
+        const double count_seconds = finish_upload(job, device_plans ? static_cast<const int32_t *>(early.d_col.p) : nullptr, d_val.as<float>());
         d_val.release();
         if (tuning.verbose)
             fprintf(stderr, "[schpf_hip] upload_coo nnz=%lld: validate %.3f s, plans+H2D %.3f s, gammaln %.3f s (%d host threads); "
@@ -878,43 +906,42 @@ template <typename T> struct Engine final : schpf_ctx {
         };
     }
 
-    // Both plans from the host builders over a COO on the host: tile plans (SCHPF_DEVICE_PLAN=0) or gather plans.
-    // Returns the doubles a loss pass leaves in wave_out
-    int64_t plans_from_host_coo(UploadJob &job, const int32_t *row, const int32_t *col, const float *val)
+    // Both plans from the host builders over a COO on the host: tile plans (SCHPF_DEVICE_PLAN=0) or gather plans
+    void plans_from_host_coo(UploadJob &job, const int32_t *row, const int32_t *col, const float *val)
     {
         if (use_tile) {
             plan_shapes(job, host_samples(job, row, col));
             tiles_from_host_coo(job, row, col, val);
-            return std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);   // the loss pass sweeps either plan (loss_side)
+            return;
         }
         const int32_t *const idx[2] = {row, col};
         const int chunk = schpf::gather_chunk_len(problem(job));
         for (int s = 0; s < 2; ++s)   // windows: by the size of the minor side's table
             build_plan(side[s].plan, job.nnz, idx[s], idx[1 - s], val, side[s].n, side[1 - s].n,
                        schpf::pick_windows((size_t)side[1 - s].n * KP * sizeof(T)), chunk);
-        return side[0].plan.n_waves;   // the gather loss pass always sweeps the cell plan (loss_side)
+        side[0].plan.n_wave_out = side[0].plan.launch;   // one double per wavefront; the cell plan only (PlanFacts)
     }
 
     // What every whole-matrix upload does once its plans stand: the loss constants from the values on the device, the
     // (row, col)-sorted copy minibatches gather their rows from (d_col: the column indices on the device in the
     // caller's order, or nullptr where the plans were built on the host), and the engine holds the matrix.  Returns
     // the wall time of the count sums
-    double finish_upload(const UploadJob &job, const int32_t *d_col, const float *d_val, int64_t n_out)
+    double finish_upload(const UploadJob &job, const int32_t *d_col, const float *d_val)
     {
         const double count_seconds = loss_constants(d_val);
         if (d_col && want_rows) {
             rows_col.alloc((size_t)nnz * 4); rows_val.alloc((size_t)nnz * 4);
-            const TileDev &tc = side[0].tile;   // the cell plan's order; rows_ptr's host copy stays tc.host.mptr
+            const TileDev &tc = side[0].tile;   // the cell plan's order; rows_ptr's host copy stays tc.mptr
             HIPCHK(schpf::launch_gather_by_order(tc.order_identity ? nullptr : tc.order_dev.as<int>(), d_col, d_val, nnz,
                                                  rows_col.as<int>(), rows_val.as<float>(), stream));
-            upload(rows_ptr, tc.host.mptr, stream);
+            upload(rows_ptr, tc.mptr, stream);
             rows_packed_ok = job.packed_ok;
             HIPCHK(hipStreamSynchronize(stream));
         }
         HIPCHK(hipMemcpyAsync(&gammaln_sum, scalars.as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost,
                               stream));
         HIPCHK(hipStreamSynchronize(stream));
-        holds_matrix(n_out, true);
+        holds_matrix(std::max(side[0].active->n_wave_out, side[1].active->n_wave_out), true);   // the loss pass sweeps either plan
         return count_seconds;
     }
 
@@ -967,9 +994,8 @@ template <typename T> struct Engine final : schpf_ctx {
         schpf::compact_zeros_device(stream, nnz_, d_row, d_col, val, val_kind, n_zero, zero_row.as<int32_t>(), zero_col.as<int32_t>());
         const double t_valid = now_s();
         nnz = nnz_;
-        use_tile = want_tile;
+        choose_plan(want_tile);
         const bool device_plans = want_tile && tuning.device_plan;
-        int64_t n_out;
         double t_shapes = t_valid;
         if (device_plans) {
             plan_shapes(job, [&](int64_t stride, std::vector<int32_t> hist[2]) {
@@ -978,7 +1004,6 @@ template <typename T> struct Engine final : schpf_ctx {
             });
             t_shapes = now_s();
             tiles_from_device_coo(job, d_row, d_col, d_val);
-            n_out = std::max(side[0].tile.n_wave_out, side[1].tile.n_wave_out);
         } else {
             schpf::BigVec<int32_t> h_row((size_t)nnz), h_col((size_t)nnz);
             schpf::BigVec<float> h_val((size_t)nnz);
@@ -988,10 +1013,10 @@ template <typename T> struct Engine final : schpf_ctx {
                 HIPCHK(hipMemcpyAsync(h_val.data(), d_val, (size_t)nnz * 4, hipMemcpyDeviceToHost, stream));
             }
             HIPCHK(hipStreamSynchronize(stream));
-            n_out = plans_from_host_coo(job, h_row.data(), h_col.data(), h_val.data());
+            plans_from_host_coo(job, h_row.data(), h_col.data(), h_val.data());
         }
         const double t_plans = now_s();
-        const double count_seconds = finish_upload(job, device_plans ? d_col : nullptr, d_val, n_out);
+        const double count_seconds = finish_upload(job, device_plans ? d_col : nullptr, d_val);
         if (tuning.verbose)
             fprintf(stderr, "[schpf_hip] upload_%s_device nnz=%lld: %svalidate + convert + zeros %.3f s, order flags in it, task-range "
                     "samples %.3f s, plans %.3f s%s, gammaln %.3f s; ELBO count sums %.4f s of it\n",
@@ -1104,7 +1129,7 @@ template <typename T> struct Engine final : schpf_ctx {
         a.chunk_natid = pd.chunk_natid.as<int>();
         a.wave_slice = pd.wave_slice.as<int>();
         table_args(a, s, mode);
-        a.partials = pd.partials.as<T>();
+        a.partials = pd.part.rows.as<T>();
         a.wave_out = wave_out.as<double>();
         a.K = K;
         return a;
@@ -1125,7 +1150,7 @@ template <typename T> struct Engine final : schpf_ctx {
         a.task_wave_off = tl.wave_off.as<int64_t>();
         a.task_order = nullptr;   // natural order (plan.cpp)
         table_args(a, s, mode);
-        a.partials = td.partials.as<T>();
+        a.partials = td.part.rows.as<T>();
         a.wave_out = wave_out.as<double>();
         a.K = K; a.n_minor = td.n_virtual ? td.n_virtual : side[1 - s].n; a.n_windows = td.host.n_windows; a.win_rows = td.host.win_rows;
         a.minor_of = td.n_virtual ? td.minor_of.as<int>() : nullptr;
@@ -1167,25 +1192,17 @@ template <typename T> struct Engine final : schpf_ctx {
             auto a = sweep_args(s, mode);
             if (mode == schpf::MODE_LLH_ROWS) a.wave_out = rows_rec.as<double>();
             if (mode == schpf::MODE_RANDOM)
-                HIPCHK(schpf::launch_random_phi<T>(a, NV, LPC, seed, s == 0 ? 1 : 0, pd.n_waves, stream));
+                HIPCHK(schpf::launch_random_phi<T>(a, NV, LPC, seed, s == 0 ? 1 : 0, pd.launch, stream));
             else
-                HIPCHK(schpf::launch_sweep<T>(a, NV, LPC, mode, pd.n_waves, stream));
+                HIPCHK(schpf::launch_sweep<T>(a, NV, LPC, mode, pd.launch, stream));
         }
     }
 
-    // where the update kernel finds a side's accumulated chunk/task partials
-    void partial_source(int s, schpf::UpdateArgs<T> &u, int &src)
+    // where the update kernel finds a side's accumulated partial rows (SRC_STRIDED)
+    void partial_source(int s, schpf::UpdateArgs<T> &u)
     {
-        if (use_tile) {
-            TileDev &td = side[s].tile;
-            src = schpf::SRC_STRIDED;
-            u.partials = td.partials.as<T>(); u.pfirst = td.pfirst.as<int>(); u.pcount = td.pcount.as<int>();
-            u.pstride = td.host.pstride;
-        } else {
-            PlanDev &pd = side[s].plan;
-            src = schpf::SRC_PARTIALS;
-            u.partials = pd.partials.as<T>(); u.cptr = pd.cptr.as<int>();
-        }
+        const PartialRows &pr = side[s].active->part;
+        u.partials = pr.rows.as<T>(); u.pfirst = pr.first.as<int>(); u.pcount = pr.count.as<int>(); u.pstride = pr.stride;
     }
 
     void need_coo() const
@@ -1198,25 +1215,23 @@ template <typename T> struct Engine final : schpf_ctx {
             throw std::logic_error("this engine holds gathered batch rows (schpf_upload_rows): evaluate the loss on the source");
     }
     // run pointers of a side's (major, minor)-sorted order, on the host
-    const std::vector<int64_t> &major_ptr(int s) const { return use_tile ? side[s].tile.host.mptr : side[s].plan.host.mptr; }
-    // doubles a loss / ELBO pass over side s leaves in wave_out.  Not symmetric: gather plans only ever sweep the cell
-    // side for it (loss_side), so theirs is the cell plan's n_waves
-    int64_t n_wave_out(int s) const { return use_tile ? side[s].tile.n_wave_out : side[0].plan.n_waves; }
+    const std::vector<int64_t> &major_ptr(int s) const { return side[s].active->mptr; }
+    // doubles a loss / ELBO pass over side s (= loss_side()) leaves in wave_out
+    int64_t n_wave_out(int s) const { return side[s].active->n_wave_out; }
 
     // (major, minor)-sorted position -> position in the caller's COO, on the device
     const int *order_of(int s, DevBuf &scratch)
     {
-        if (!use_tile) { upload(scratch, side[s].plan.host.order, stream); return scratch.as<int>(); }
-        TileDev &td = side[s].tile;
-        if (td.order_dev.p) return td.order_dev.as<int>();
-        if (td.order_identity) {
+        const PlanFacts &pl = *side[s].active;
+        if (pl.order_dev.p) return pl.order_dev.as<int>();
+        if (pl.order_identity) {
             std::vector<int32_t> iota((size_t)nnz);
             for (int64_t j = 0; j < nnz; ++j) iota[(size_t)j] = (int32_t)j;
             upload(scratch, iota, stream);
             HIPCHK(hipStreamSynchronize(stream));   // iota dies with this scope
             return scratch.as<int>();
         }
-        upload(scratch, td.host.order, stream);
+        upload(scratch, pl.order, stream);
         return scratch.as<int>();
     }
 
@@ -1258,7 +1273,7 @@ template <typename T> struct Engine final : schpf_ctx {
         const bool sharded = flags_ & SCHPF_SHARDED;
         const bool only_gene = flags_ & SCHPF_LOCAL_GENE, only_cell = flags_ & SCHPF_LOCAL_CELL;
         const bool do_cell = !only_gene || only_cell, do_gene = !only_cell || only_gene;
-        if (pending_init == 0 && use_tile && dual_slots > 0 && do_gene && do_cell && !freeze) {
+        if (pending_init == 0 && dual_slots > 0 && do_gene && do_cell && !freeze) {   // dual_slots: tile plans only
             // both sweeps read the same old tables: one launch (timed as kind 0, see schpf_profile_read)
             ScopedTimer tm(prof, stream, 0);
             // Not symmetric: the kernel takes (cell args, gene args) in that order; dual_order names gene tasks as ~task
@@ -1292,14 +1307,9 @@ template <typename T> struct Engine final : schpf_ctx {
         }
         if (sharded && !freeze && pending_init != 1 && do_gene) {
             // fixed-order reduction of this rank's gene-side partials into the exchange buffer (the cells stay on their rank)
-            const TileDev &tg = side[1].tile;
-            const PlanDev &pg = side[1].plan;
-            if (use_tile)
-                HIPCHK(schpf::launch_combine_strided<T>(tg.partials.as<T>(), tg.pfirst.as<int>(), tg.pcount.as<int>(),
-                                                        tg.host.pstride, G, K, KP, exchange_buf.as<T>(), stream));
-            else
-                HIPCHK(schpf::launch_combine_partials<T>(pg.partials.as<T>(), pg.cptr.as<int>(), G, K, KP,
-                                                         exchange_buf.as<T>(), stream));
+            const PartialRows &pr = side[1].active->part;
+            HIPCHK(schpf::launch_combine_strided<T>(pr.rows.as<T>(), pr.first.as<int>(), pr.count.as<int>(), pr.stride, G, K,
+                                                    KP, exchange_buf.as<T>(), stream));
         }
     }
 
@@ -1332,13 +1342,13 @@ template <typename T> struct Engine final : schpf_ctx {
             if (gene && freeze) return;   // SCHPF_FREEZE_GENES: eta / beta stay as they are
             Side &sd = side[s], &other = side[1 - s];
             schpf::UpdateArgs<T> u = update_args(s);
-            int src;
+            int src = schpf::SRC_STRIDED;
             // dense sums instead of plan partials: right after init_phi_host (the cells' in dense_cell, the genes' in the
             // exchange buffer) and, gene side only, in every sharded iteration (the all-reduced exchange buffer)
             if (pending_init == 1 || (gene && sharded)) {
                 src = schpf::SRC_DENSE;
                 u.dense = gene ? exchange_buf.as<T>() : dense_cell.as<T>();
-            } else partial_source(s, u, src);
+            } else partial_source(s, u);
             u.prior_shape = prior_shape(s);
             u.cap_shape = sd.cap_shape.as<T>(); u.cap_rate = sd.cap_rate.as<T>();
             if (gene) {
@@ -1471,9 +1481,8 @@ template <typename T> struct Engine final : schpf_ctx {
         const int s = by;
         const Side &sd = side[s];
         const size_t n = (size_t)sd.n, n_max = (size_t)std::max(N, G);
-        int64_t n_rec[2];
-        for (int t = 0; t < 2; ++t) n_rec[t] = use_tile ? side[t].tile.host.n_partial_rows : side[t].plan.n_chunks;
-        const size_t rec_bytes = (size_t)std::max<int64_t>(std::max(n_rec[0], n_rec[1]), 1) * schpf::ROW_REC * sizeof(double);
+        const int64_t n_rec = std::max(side[0].active->part.n, side[1].active->part.n);   // one scratch for either axis
+        const size_t rec_bytes = (size_t)std::max<int64_t>(n_rec, 1) * schpf::ROW_REC * sizeof(double);
         if (rows_rec.bytes < rec_bytes) rows_rec.alloc(rec_bytes);
         if (rows_out.bytes < n_max * 24) rows_out.alloc(n_max * 24);
         if (n_zero > 0) build_zero_rows(s);
@@ -1482,14 +1491,9 @@ template <typename T> struct Engine final : schpf_ctx {
         int64_t *d_cnt = reinterpret_cast<int64_t *>(d_gl + n);
         ScopedTimer tm(prof, stream, 2);
         run_sweep(s, schpf::MODE_LLH_ROWS);
-        if (use_tile) {
-            const TileDev &td = sd.tile;
-            HIPCHK(schpf::launch_row_records_reduce(rows_rec.as<double>(), td.pfirst.as<int>(), td.pcount.as<int>(),
-                                                    td.host.pstride, nullptr, sd.n, d_llh, d_gl, d_cnt, stream));
-        } else {
-            HIPCHK(schpf::launch_row_records_reduce(rows_rec.as<double>(), nullptr, nullptr, 0, sd.plan.cptr.as<int>(), sd.n,
-                                                    d_llh, d_gl, d_cnt, stream));
-        }
+        const PartialRows &pr = sd.active->part;
+        HIPCHK(schpf::launch_row_records_reduce(rows_rec.as<double>(), pr.first.as<int>(), pr.count.as<int>(),
+                                                pr.stride, sd.n, d_llh, d_gl, d_cnt, stream));
         if (n_zero > 0) {
             const ZeroRows &z = zero_rows[s];
             HIPCHK(schpf::launch_zero_rate_rows<T>(z.seg_major.template as<int>(), z.seg_ptr.template as<int>(), z.n_seg,
@@ -1518,7 +1522,7 @@ template <typename T> struct Engine final : schpf_ctx {
     void upload_info(int64_t info[4]) override
     {
         info[0] = nnz; info[1] = n_rounded; info[2] = n_zero;
-        info[3] = (use_tile ? (side[0].tile.packed ? 1 : 0) : 0) | (rows_ptr.p ? 2 : 0);   // bit 1: a row-sorted copy is kept
+        info[3] = (side[0].active->packed ? 1 : 0) | (rows_ptr.p ? 2 : 0);   // bit 0: packed entries; bit 1: a row-sorted copy
     }
 
     // Shader clock the chip sustained under the sweep launches since the last read (tile plans; 0 launches: unknown).
@@ -1566,7 +1570,7 @@ template <typename T> struct Engine final : schpf_ctx {
         info[2] = staged_bytes(0);
         info[3] = staged_bytes(1);
         info[4] = (tc.entry_slots + tg.entry_slots) * (tc.packed ? 4 : 8);
-        info[5] = (tc.host.n_partial_rows + tg.host.n_partial_rows) * row;
+        info[5] = (tc.part.n + tg.part.n) * row;
         // what the loss pass will sweep (loss_side, loss_tasks): so that a report can say which plan and cut the model chose
         const int ls = loss_side();
         const TileDev &tl = side[ls].tile;
@@ -1578,17 +1582,16 @@ template <typename T> struct Engine final : schpf_ctx {
     void plan_info(int64_t info[16]) override
     {
         info[0] = KP; info[1] = KL; info[2] = LPC;
-        const TileDev &tc = side[0].tile;
-        info[3] = use_tile ? -tc.host.win_rows : side[0].plan.host.chunk_len;   // negative: tile plan, rows per LDS window
-        info[14] = use_tile ? tc.host.slot16 * 16 : 0; info[15] = use_tile ? tc.host.wpb : 0;
         for (int s = 0; s < 2; ++s) {
-            const TileDev &td = side[s].tile;
-            const PlanDev &pd = side[s].plan;
-            info[4 + s] = use_tile ? td.host.n_windows : pd.host.n_windows;
-            info[6 + s] = use_tile ? td.host.n_partial_rows : pd.n_chunks;
-            info[8 + s] = use_tile ? td.tasks.n : pd.n_waves;
-            info[10 + s] = use_tile ? td.entry_slots : pd.entry_slots;
-            info[12 + s] = use_tile ? td.host.ring : 0;
+            const PlanFacts &pl = *side[s].active;
+            info[4 + s] = pl.windows; info[6 + s] = pl.part.n; info[8 + s] = pl.launch; info[10 + s] = pl.entry_slots;
+        }
+        info[3] = side[0].plan.host.chunk_len;
+        info[12] = info[13] = info[14] = info[15] = 0;
+        if (use_tile) {   // tile-only: [3] negative, rows per LDS window; ring slots per side; slot bytes; waves per block
+            const schpf::TilePlanHost &hc = side[0].tile.host;
+            info[3] = -hc.win_rows; info[12] = hc.ring; info[13] = side[1].tile.host.ring;
+            info[14] = hc.slot16 * 16; info[15] = hc.wpb;
         }
     }
 };

@@ -9,8 +9,9 @@ enum { MODE_PHI = 0, MODE_LLH = 1, MODE_RANDOM = 2, MODE_ELBO = 3, MODE_LLH_ROWS
 // MODE_LLH_ROWS leaves one record of ROW_REC doubles per lane group (tile sweep: per partial-row slot task * gpb + g;
 // gather sweep: per chunk) in wave_out: {sum x log r - r, sum lgamma(x + 1), entries with x > 0}
 enum { ROW_REC = 3 };
-enum { SRC_STRIDED = 3 };
-enum { SRC_NONE = 0, SRC_PARTIALS = 1, SRC_DENSE = 2 };
+// where gamma_update_kernel takes a row's accumulated sums from: nowhere (tables from the stored parameters), a dense
+// [n, K] matrix, or the row's partial rows
+enum { SRC_NONE = 0, SRC_DENSE = 1, SRC_STRIDED = 2 };
 
 template <typename T> struct SweepArgs {
     const uint4 *entries;       // sliced-ELL nonzeros {minor0, val0, minor1, val1}
@@ -82,11 +83,10 @@ template <typename T> __device__ __forceinline__ double sum_strided(const T *__r
 
 template <typename T> struct UpdateArgs {
     int n, K, KP, rows_per_block;
-    const T *partials;          // SRC_PARTIALS: [n_chunks, KP]
-    const int *cptr;            //               [n + 1]
+    const T *partials;          // SRC_STRIDED:  [partial rows, KP]
     const T *dense;             // SRC_DENSE:    [n, K]
-    const int *pfirst, *pcount; // SRC_STRIDED:  partial rows pfirst[row] + j * pstride, j < pcount[row]
-    int64_t pstride;
+    const int *pfirst, *pcount; // SRC_STRIDED:  a row's partial rows are pfirst[row] + j * pstride, j < pcount[row]
+    int64_t pstride;            //               (a gather plan's: its consecutive chunks, pstride = 1)
     double prior_shape;         // a or c
     const T *cap_shape;         // xi / eta shape [n]
     const T *cap_rate;          // xi / eta rate BEFORE this update [n]
@@ -135,9 +135,6 @@ int update_rows_per_block(int K);
 hipError_t launch_colsum_reduce(const double *part, int nblocks, int K, double *out, void *mirror,
                                 int mirror_is_f32, hipStream_t st);
 template <typename T>
-hipError_t launch_combine_partials(const T *partials, const int *cptr, int n, int K, int KP, T *out,
-                                   hipStream_t st);
-template <typename T>
 hipError_t launch_combine_strided(const T *partials, const int *pfirst, const int *pcount, int64_t pstride, int n,
                                   int K, int KP, T *out, hipStream_t st);
 hipError_t launch_sum_doubles(const double *v, int64_t n, double *out, hipStream_t st);
@@ -155,10 +152,10 @@ template <typename T>
 hipError_t launch_zero_rate_sum(const int *row, const int *col, int64_t n, const T *et, const T *eb, int K, int KP,
                                 double *out, hipStream_t st);
 // Per-row loss.  The records a MODE_LLH_ROWS sweep left, summed per major row in fixed order -- addressed as
-// the update kernel addresses a row's partial rows: pfirst != nullptr: records pfirst[row] + j * pstride, j < pcount[row]
-// (tile plan); else records cptr[row] .. cptr[row + 1] (gather plan) -- into llh[n], gl[n], cnt[n]
-hipError_t launch_row_records_reduce(const double *rec, const int *pfirst, const int *pcount, int64_t pstride,
-                                     const int *cptr, int n, double *llh, double *gl, int64_t *cnt, hipStream_t st);
+// the update kernel addresses a row's partial rows: records pfirst[row] + j * pstride, j < pcount[row] -- into llh[n],
+// gl[n], cnt[n]
+hipError_t launch_row_records_reduce(const double *rec, const int *pfirst, const int *pcount, int64_t pstride, int n,
+                                     double *llh, double *gl, int64_t *cnt, hipStream_t st);
 // ... and the explicitly stored zeros, which the sweeps take for padding: one thread per major row that has any
 // (seg_major[s]; its zeros are minor[seg_ptr[s] .. seg_ptr[s + 1]), an order fixed when the list was sorted):
 // llh[row] -= sum r, cnt[row] += their number

@@ -125,10 +125,7 @@ __global__ __launch_bounds__(256, MINW) void gamma_update_kernel(UpdateArgs<T> a
                 rate = (double)a.rate[(size_t)row * K + k];
             } else {
                 double acc = 0.0;
-                if (SRC == SRC_PARTIALS) {
-                    acc = sum_strided(a.partials + (size_t)a.cptr[row] * KP + k, a.cptr[row + 1] - a.cptr[row],
-                                      (size_t)KP);
-                } else if (SRC == SRC_STRIDED) {
+                if (SRC == SRC_STRIDED) {
                     acc = sum_strided(a.partials + (size_t)a.pfirst[row] * KP + k, a.pcount[row],
                                       (size_t)a.pstride * KP);
                 } else {
@@ -220,19 +217,8 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const double *__rest
     }
 }
 
-// Reduce the chunk partials of every row in fixed order into a dense [n, K] matrix
+// Reduce the partial rows of every row in fixed order into a dense [n, K] matrix
 // (the gene-side accumulator that is all-reduced across GPUs when cells are sharded).
-template <typename T>
-__global__ __launch_bounds__(256) void combine_partials_kernel(const T *__restrict__ partials,
-                                                               const int *__restrict__ cptr, int n, int K,
-                                                               int KP, T *__restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * K) return;
-    const int row = (int)(i / K), k = (int)(i - (size_t)row * K);
-    out[i] = (T)sum_strided(partials + (size_t)cptr[row] * KP + k, cptr[row + 1] - cptr[row], (size_t)KP);
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void combine_strided_kernel(const T *__restrict__ partials,
                                                               const int *__restrict__ pfirst,
@@ -315,17 +301,14 @@ __global__ __launch_bounds__(256) void zero_rate_sum_kernel(const int *__restric
 __global__ __launch_bounds__(256) void row_records_reduce_kernel(const double *__restrict__ rec,
                                                                  const int *__restrict__ pfirst,
                                                                  const int *__restrict__ pcount, int64_t pstride,
-                                                                 const int *__restrict__ cptr, int n,
-                                                                 double *__restrict__ llh, double *__restrict__ gl,
-                                                                 int64_t *__restrict__ cnt)
+                                                                 int n, double *__restrict__ llh,
+                                                                 double *__restrict__ gl, int64_t *__restrict__ cnt)
 {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= n) return;
-    const double *p;
-    int m;
-    size_t stride;
-    if (pfirst) { p = rec + (size_t)pfirst[row] * ROW_REC; m = pcount[row]; stride = (size_t)pstride * ROW_REC; }
-    else { p = rec + (size_t)cptr[row] * ROW_REC; m = cptr[row + 1] - cptr[row]; stride = ROW_REC; }
+    const double *p = rec + (size_t)pfirst[row] * ROW_REC;
+    const int m = pcount[row];
+    const size_t stride = (size_t)pstride * ROW_REC;
     llh[row] = sum_strided(p, m, stride);
     gl[row] = sum_strided(p + 1, m, stride);
     cnt[row] = (int64_t)sum_strided(p + 2, m, stride);   // whole numbers below 2^31: exact
@@ -595,7 +578,6 @@ template <typename T, bool WR, int MINW> static void launch_update_w(const Updat
 {
     dim3 block(256);
     if (src == SRC_NONE) hipLaunchKernelGGL((gamma_update_kernel<T, SRC_NONE, WR, MINW>), grid, block, lds, st, a);
-    else if (src == SRC_PARTIALS) hipLaunchKernelGGL((gamma_update_kernel<T, SRC_PARTIALS, WR, MINW>), grid, block, lds, st, a);
     else if (src == SRC_STRIDED) hipLaunchKernelGGL((gamma_update_kernel<T, SRC_STRIDED, WR, MINW>), grid, block, lds, st, a);
     else hipLaunchKernelGGL((gamma_update_kernel<T, SRC_DENSE, WR, MINW>), grid, block, lds, st, a);
 }
@@ -619,15 +601,6 @@ hipError_t launch_colsum_reduce(const double *part, int nblocks, int K, double *
 {
     hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)K), dim3(256), 0, st, part, nblocks, K, out, mirror,
                        mirror_is_f32);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_combine_partials(const T *partials, const int *cptr, int n, int K, int KP, T *out,
-                                   hipStream_t st)
-{
-    hipLaunchKernelGGL((combine_partials_kernel<T>), dim3(blocks_for((int64_t)n * K)), dim3(256), 0, st,
-                       partials, cptr, n, K, KP, out);
     return hipGetLastError();
 }
 
@@ -703,13 +676,13 @@ hipError_t launch_zero_rate_sum(const int *row, const int *col, int64_t n, const
     hipLaunchKernelGGL((zero_rate_sum_kernel<T>), dim3(1), dim3(256), 0, st, row, col, n, et, eb, K, KP, out);
     return hipGetLastError();
 }
-hipError_t launch_row_records_reduce(const double *rec, const int *pfirst, const int *pcount, int64_t pstride,
-                                     const int *cptr, int n, double *llh, double *gl, int64_t *cnt, hipStream_t st)
+hipError_t launch_row_records_reduce(const double *rec, const int *pfirst, const int *pcount, int64_t pstride, int n,
+                                     double *llh, double *gl, int64_t *cnt, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
-    if (!pfirst && !cptr) return hipErrorInvalidValue;
+    if (!pfirst || !pcount) return hipErrorInvalidValue;
     hipLaunchKernelGGL(row_records_reduce_kernel, dim3(blocks_for(n)), dim3(256), 0, st, rec, pfirst, pcount, pstride,
-                       cptr, n, llh, gl, cnt);
+                       n, llh, gl, cnt);
     return hipGetLastError();
 }
 template <typename T>
@@ -821,7 +794,6 @@ hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStre
 // explicit instantiations for the two model dtypes
 #define SCHPF_INSTANTIATE(T)                                                                                   \
     template hipError_t launch_gamma_update<T>(const UpdateArgs<T> &, int, int, hipStream_t);                  \
-    template hipError_t launch_combine_partials<T>(const T *, const int *, int, int, int, T *, hipStream_t);   \
     template hipError_t launch_combine_strided<T>(const T *, const int *, const int *, int64_t, int, int, int,  \
                                                   T *, hipStream_t);                                           \
     template hipError_t launch_zero_rate_sum<T>(const int *, const int *, int64_t, const T *, const T *, int,  \

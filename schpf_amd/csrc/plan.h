@@ -19,8 +19,10 @@
 //     nothing).
 //
 // A chunk's partial K-vector is written to row `natural id` of a partials matrix; the
-// natural ids of one major are consecutive (cptr), so the fused update kernel reduces
-// them in a fixed order: no atomics, run-to-run deterministic.
+// natural ids of one major are consecutive: cptr[m] .. cptr[m + 1].  The engine hands that
+// range to the kernels in the tile plan's notation for a row's partial rows (first = cptr[m],
+// count = cptr[m + 1] - cptr[m], stride 1; see pfirst / pcount / pstride below), so the one
+// fused update kernel reduces them in a fixed order: no atomics, run-to-run deterministic.
 #pragma once
 #include <algorithm>
 #include <cstdint>

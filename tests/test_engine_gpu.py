@@ -802,6 +802,73 @@ def test_sharded_protocol_two_engines_on_one_gpu(amd, oracle, flags):
         e.close()
 
 
+PACKED_ROW_LENGTHS = (0, 1, 16, 17, 64, 65, 144)   # stored entries of a shard's gene row: 0, 1, 1, 2, 4, 5, 9 chunks of 16
+
+
+def _matrix_with_gene_rows_of_pinned_lengths(shard_cells=144, ngenes=42, seed=5):
+    """Two row shards of `shard_cells` cells each.  In EACH shard gene g holds PACKED_ROW_LENGTHS[(g + 3 * shard) % 7]
+    stored entries, in distinct cells of the shard drawn at random.  144 entries need 144 cells in the shard; both
+    shards hold the same number of entries (the same lengths, rotated; 42 = 6 x 7 genes), so the nnz-balanced
+    partition cuts between them."""
+    from scipy.sparse import coo_matrix
+    rng = np.random.RandomState(seed)
+    row, col, lengths = [], [], np.zeros((2, ngenes), np.int64)
+    for shard in range(2):
+        for g in range(ngenes):
+            n = PACKED_ROW_LENGTHS[(g + 3 * shard) % len(PACKED_ROW_LENGTHS)]
+            lengths[shard, g] = n
+            row.append(shard * shard_cells + np.sort(rng.choice(shard_cells, n, replace=False)))
+            col.append(np.full(n, g))
+    row, col = np.concatenate(row).astype(np.int32), np.concatenate(col).astype(np.int32)
+    perm = rng.permutation(len(row))
+    X = coo_matrix((rng.randint(1, 6, len(row)), (row[perm], col[perm])), shape=(2 * shard_cells, ngenes))
+    return X, lengths
+
+
+@only_plans("gather")
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("K", [5, 20])
+def test_gather_shards_pack_gene_rows_of_0_to_9_chunks(amd, oracle, plan_kind, K, dtype):
+    """The packing of a sharded rank's gene-side partial rows on GATHER plans, at the row lengths its fixed-order sum
+    (kernels.h sum_strided: four terms in flight, then a tail) tells apart: gene rows of 0, 1, 1, 2, 4, 5 and 9 chunks
+    in each of two row shards on one GPU (ThreadedShards, comm="emulated").  plan_info says that these chunk counts
+    were really built.  Two iterations: all rows against the unsharded engine at the shard tests' tolerances (rtol
+    1e-11 f64 / 2e-5 f32: the sharded sum order differs) and against the oracle at the iteration tests'."""
+    from schpf_amd.sharded import ThreadedShards
+    X, lengths = _matrix_with_gene_rows_of_pinned_lengths()
+    N, a, c = X.shape[0], 0.3, 0.3
+    f32 = np.dtype(dtype) == np.float32
+    tol = 2e-5 if f32 else 1e-11
+    bp, dp, st = random_state(oracle, X, K, dtype, seed=K)
+    names = ("xi", "theta", "eta", "beta")
+    ref_states = []
+    with load_engine(amd, X, K, dtype, st, a, c, bp, dp) as eng:
+        for _ in range(2):
+            eng.step()
+            ref_states.append({n: eng.get_gamma(n) for n in names})
+    with ThreadedShards(X, K, dtype, devices=[0, 0], comm="emulated") as shards:
+        assert list(shards.bounds) == [0, N // 2, N]
+        for r, e in enumerate(shards.engines):
+            info = e.plan_info()
+            assert info["chunk_len"] == 16
+            assert info["n_chunks_gene"] == int(((lengths[r] + 15) // 16).sum())
+            assert sorted(set((lengths[r] + 15) // 16)) == [0, 1, 2, 4, 5, 9]
+        shards.set_hypers(a, c, bp, dp)
+        for name in names:
+            shards.set_gamma(name, getattr(st, name + "_shape"), getattr(st, name + "_rate"))
+        for it in range(2):
+            shards.steps(1)
+            oracle.cavi_iteration(X.data, X.row, X.col, st, a, c, bp, dp)
+            got = {n: shards.get_gamma(n) for n in names}
+            for name in names:
+                assert_allclose(got[name][0], ref_states[it][name][0], rtol=tol, err_msg="%s shape vs unsharded" % name)
+                assert_allclose(got[name][1], ref_states[it][name][1], rtol=tol, err_msg="%s rate vs unsharded" % name)
+                assert_allclose(got[name][0], getattr(st, name + "_shape"), rtol=(2e-5 * (it + 1)) if f32 else 1e-11,
+                                err_msg="%s shape vs oracle" % name)
+                assert_allclose(got[name][1], getattr(st, name + "_rate"), rtol=(2e-5 * (it + 1)) if f32 else 1e-11,
+                                err_msg="%s rate vs oracle" % name)
+
+
 @only_plans("tile", "half")
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("coo_order", ["canonical", "shuffled"])
