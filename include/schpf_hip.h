@@ -327,6 +327,24 @@ int schpf_debug_thin_counts(int64_t nnz, const int32_t *row, const int32_t *col,
                             double frac, uint64_t seed, int32_t *train, int32_t *test, int64_t stats[4]);
 int schpf_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
 
+/* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
+ * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
+ *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),
+ *   digamma(x[i]) or digamma_less_log(x[i], fast_rcp(y[i])) (= psi(shape x) - log(rate y), as the kernel pairs them).
+ *   Host arrays of n doubles; y is read by SCHPF_SPECIAL_PSI_LESS_LOG only and may be NULL otherwise.  n = 0 succeeds.
+ * schpf_debug_tables: the three [n, KP] tables of one side (SCHPF_BY_CELL: theta's, SCHPF_BY_GENE: beta's; KP =
+ *   schpf_plan_info()[0], columns k >= nfactors are padding) copied to the host in the engine's dtype: tab_e = shape /
+ *   rate, tab_log = psi(shape) - log(rate), tab_exp = exp(tab_log - float(row max of tab_log)).  Tables older than
+ *   the parameters are rebuilt first, as the next schpf_step or schpf_loss_terms would; nothing else changes.  Any of the
+ *   three pointers may be NULL. */
+#define SCHPF_SPECIAL_RCP 0
+#define SCHPF_SPECIAL_LOG 1
+#define SCHPF_SPECIAL_EXP 2
+#define SCHPF_SPECIAL_PSI 3
+#define SCHPF_SPECIAL_PSI_LESS_LOG 4
+int schpf_debug_special(int which, int64_t n, const double *x, const double *y, double *out);
+int schpf_debug_tables(schpf_ctx *ctx, int side, void *tab_e, void *tab_log, void *tab_exp);
+
 /* Test hook (host only, no GPU needed): build one sweep plan from (major, minor, val) and expand
  * it back into per-nonzero records in storage order -- the major/minor/val it will be processed
  * with, the partials row (natural chunk id) it accumulates into and the wavefront that streams

@@ -17,6 +17,8 @@ IDX_I32, IDX_I64 = 0, 1   # SCHPF_IDX_*: the index types of the device uploads
 STREAM_DEFAULT = 1   # SCHPF_STREAM_DEFAULT: the device's null stream
 FREEZE_GENES, SIMULTANEOUS, SHARDED, CELLS_FIRST, LOCAL_GENE, LOCAL_CELL = 1, 2, 4, 8, 16, 32
 BY_CELL, BY_GENE = 0, 1   # SCHPF_BY_CELL / SCHPF_BY_GENE: the axis of schpf_loss_rows
+# SCHPF_SPECIAL_*: the function schpf_debug_special evaluates
+SPECIAL_RCP, SPECIAL_LOG, SPECIAL_EXP, SPECIAL_PSI, SPECIAL_PSI_LESS_LOG = 0, 1, 2, 3, 4
 
 _vp = ctypes.c_void_p
 _i32p = ctypes.POINTER(ctypes.c_int32)
@@ -79,6 +81,8 @@ SIGNATURES = {
     "schpf_thin_counts": [_int, _i64, _vp, _vp, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
     "schpf_debug_thin_counts": [_i64, _vp, _vp, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
     "schpf_debug_philox": [_vp, _vp, _vp],
+    "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
+    "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_plan_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _i64p],
     "schpf_debug_tile_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int,

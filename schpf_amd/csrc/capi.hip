@@ -182,6 +182,7 @@ struct schpf_ctx {
     virtual void elbo_terms(double ap, double cp, double terms[5]) = 0;
     virtual void loss_rows(int by, double *llh, double *gl, int64_t *count) = 0;
     virtual void plan_info(int64_t info[16]) = 0;
+    virtual void debug_tables(int side, void *tab_e, void *tab_log, void *tab_exp) = 0;
     virtual void upload_info(int64_t info[4]) = 0;
     virtual void profile_clock(double *shader_mhz, int64_t *launches) = 0;
     virtual void sweep_bytes(int64_t info[8]) = 0;
@@ -1507,6 +1508,21 @@ template <typename T> struct Engine final : schpf_ctx {
         HIPCHK(hipStreamSynchronize(stream));
     }
 
+    // schpf_debug_tables: a side's tables as the next sweep would read them, padding columns included.  Touches what
+    // loss_terms touches before its sweep (refresh_tables) and nothing else
+    void debug_tables(int s, void *tab_e, void *tab_log, void *tab_exp) override
+    {
+        if (s != SCHPF_BY_CELL && s != SCHPF_BY_GENE) throw std::invalid_argument("side must be SCHPF_BY_CELL or SCHPF_BY_GENE");
+        refresh_tables();
+        const Side &sd = side[s];
+        const size_t bytes = (size_t)sd.n * KP * sizeof(T);
+        void *const dst[3] = {tab_e, tab_log, tab_exp};
+        const DevBuf *const src[3] = {&sd.tab_e, &sd.tab_log, &sd.tab_exp};
+        for (int i = 0; i < 3; ++i)
+            if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], src[i]->p, bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+
     // which tile plan the loss pass sweeps (policy.cpp loss_side)
     int loss_side() const
     {
@@ -1798,5 +1814,9 @@ int schpf_upload_info(schpf_ctx *ctx, int64_t info[4])
 {
     if (!info) return fail("output pointer is NULL");
     CTX_CALL(ctx->upload_info(info));
+}
+int schpf_debug_tables(schpf_ctx *ctx, int side, void *tab_e, void *tab_log, void *tab_exp)
+{
+    CTX_CALL(ctx->debug_tables(side, tab_e, tab_log, tab_exp));
 }
 }  // extern "C"

@@ -5,8 +5,15 @@
 // path hpf_numba.py:83-94.
 //
 // Plain C++ over fma / frexp / ldexp, so that the same text compiles for the host: tests/test_special_host.py builds it
-// with g++ (the hardware reciprocal seed replaced by a 24-bit one) and checks it against SciPy's values on the
-// psi_gammaln.npz grid.  Accuracy: psi within 4e-15 (relative or absolute) on [1e-4, 1e6]; log and exp within 2 ulp.
+// with g++ (the hardware reciprocal seed replaced by a 24-bit one) and checks it against SciPy and NumPy, and
+// tests/test_special_gpu.py holds that build and the DEVICE build (schpf_debug_special) to
+// tests/golden/special_edges.npz (mpmath, rounded once).  Accuracy, the bounds those tests enforce:
+//   digamma           within 4e-15, relative or absolute, on [1e-4, 1e6] and in the branch from 1e8 up
+//   digamma_less_log  |error| <= 4e-15 * max(1, |psi(shape)|, |log rate|)
+//   fast_log          within 2 ulp over the whole positive range, denormals included; exact at 0, inf, nan
+//   fast_exp          relative error <= 4.5e-16 (2 ulp) where the result is normal; the correctly rounded double (a
+//                     denormal or 0) for arguments from -745 down
+//   fast_rcp          |fast_rcp(x) * x - 1| <= 2.3e-16 for a normal x whose reciprocal is normal
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -359,6 +359,18 @@ class DeviceCAVI(object):
     def elbo(self, ap, cp):
         return self.elbo_terms(ap, cp)["elbo"]
 
+    def _debug_tables(self, by):
+        """Test hook: the tables the sweeps read for one side (by="cell": theta's, by="gene": beta's), as three
+        (n, KP) arrays of the engine's dtype, padding columns k >= nfactors included: {'e': shape / rate,
+        'log': psi(shape) - log(rate), 'exp': exp(log - float32(row max of log))}.  Tables older than the parameters are
+        rebuilt first, as the next step() or loss_terms() would; nothing else changes."""
+        if by not in _AXES:
+            raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
+        n = self.ncells if by == "cell" else self.ngenes
+        out = {k: np.empty((n, self.plan_info()["KP"]), dtype=self.dtype) for k in ("e", "log", "exp")}
+        _lib.check(self._lib.schpf_debug_tables(self._h, _AXES[by], _p(out["e"]), _p(out["log"]), _p(out["exp"])))
+        return out
+
     def synchronize(self):
         _lib.check(self._lib.schpf_synchronize(self._h))
 

@@ -1,48 +1,22 @@
 """The special functions of the fused Gamma update (schpf_amd/csrc/special.h: psi, log, exp, reciprocal -- written for
 the update kernel's instruction count) compiled for the HOST with g++ and checked against SciPy / NumPy: the header is
 plain C++ over fma / frexp / ldexp, the only device-specific piece (the hardware reciprocal seed) is replaced by a seed
-of the same 24-bit precision.  The same functions on the GPU are pinned by tests/test_ops_gpu.py (schpf_digamma) and by
-every engine parity test."""
-import ctypes
-import os
-import subprocess
-
+of the same 24-bit precision -- and, beside it, the frexp builtins and fma_c's scalar-operand v_fma_f64 by std::frexp and
+std::fma.  So this file says nothing about those device paths: the DEVICE build of the same functions is pinned by
+tests/test_special_gpu.py (schpf_debug_special: every function, on tests/golden/special_edges.npz, to the bounds below,
+beside this host build on the same points), and what the update kernel makes of them by tests/test_update_tables_gpu.py.
+tests/test_ops_gpu.py (schpf_digamma) covers psi on the psi_gammaln.npz grid only."""
 import numpy as np
 import pytest
 from scipy.special import digamma
 
-from conftest import ROOT, load_golden
-
-SRC = r"""
-#include "special.h"
-extern "C" {
-void h_psi(long n, const double *x, double *o) { for (long i = 0; i < n; ++i) o[i] = schpf::digamma(x[i]); }
-void h_psi_less_log(long n, const double *x, const double *rate, double *o)
-{ for (long i = 0; i < n; ++i) o[i] = schpf::digamma_less_log(x[i], schpf::fast_rcp(rate[i])); }
-void h_log(long n, const double *x, double *o) { for (long i = 0; i < n; ++i) o[i] = schpf::fast_log(x[i]); }
-void h_exp(long n, const double *x, double *o) { for (long i = 0; i < n; ++i) o[i] = schpf::fast_exp(x[i]); }
-void h_rcp(long n, const double *x, double *o) { for (long i = 0; i < n; ++i) o[i] = schpf::fast_rcp(x[i]); }
-}
-"""
+from conftest import load_golden
+from _special_host import build_host
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    d = tmp_path_factory.mktemp("special")
-    src = d / "h.cpp"
-    src.write_text(SRC)
-    so = d / "libspecial_host.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "schpf_amd", "csrc"), str(src), "-o", str(so)])
-    lib = ctypes.CDLL(str(so))
-
-    def call(name, *arrays):
-        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
-        out = np.empty(arrays[0].shape[0])
-        getattr(lib, name)(ctypes.c_long(out.shape[0]), *[a.ctypes.data_as(ctypes.c_void_p) for a in arrays],
-                           out.ctypes.data_as(ctypes.c_void_p))
-        return out
-    return call
+    return build_host(tmp_path_factory.mktemp("special"))
 
 
 def _abs_or_rel(got, want):
