@@ -35,7 +35,7 @@ template <typename T> struct TileArgs {
     const uint16_t *steps;         // [(block * wpb + wave) * n_windows + window]
     const int *block_rows;         // [n_blocks * gpb]
     const int *task_block, *task_w0, *task_w1;
-    // loss pass over SUB-ranges of the tasks (capi.hip loss_tasks): where the sub-task's parent task ends -- entries of
+    // loss pass over SUB-ranges of the tasks (upload.hip loss_tasks): where the sub-task's parent task ends -- entries of
     // the half-window schedule may point one sub-window beyond the sub-task, and that one is staged too; nullptr: task_w1
     const int *task_stage_end;
     const int64_t *task_wave_off;  // [task * wpb + wave] first uint4 of the wave's entries in the task
@@ -138,7 +138,7 @@ template <typename T>
 hipError_t launch_combine_strided(const T *partials, const int *pfirst, const int *pcount, int64_t pstride, int n,
                                   int K, int KP, T *out, hipStream_t st);
 hipError_t launch_sum_doubles(const double *v, int64_t n, double *out, hipStream_t st);
-// minibatch rows from a resident row-sorted copy (capi.hip keep_rows / upload_rows):
+// minibatch rows from a resident row-sorted copy (upload.hip finish_upload / upload_rows):
 //   out_col/val[j] = col/val[order[j]]  (order == nullptr: identity copy)
 hipError_t launch_gather_by_order(const int *order, const int *col, const float *val, int64_t nnz, int *out_col,
                                   float *out_val, hipStream_t st);

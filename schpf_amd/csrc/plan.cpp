@@ -575,11 +575,6 @@ std::vector<double> block_shares(const std::vector<int32_t> &count, int rows_per
     return share;
 }
 
-std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major, int rows_per_block, int64_t stride)
-{
-    return block_shares(sample_histogram(nnz, major, n_major, stride), rows_per_block);
-}
-
 RangeChoice choose_task_ranges(const int64_t blocks[2], const int64_t half_windows[2], const bool half_ok[2],
                                const std::vector<double> block_share[2],
                                double nnz, int resident, double nnz_per_second, double task_seconds,

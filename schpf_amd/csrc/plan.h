@@ -210,10 +210,9 @@ struct TileShape {
 // separate_launches: the two-launch iteration of a row shard -- each orientation scheduled on its own.
 struct RangeChoice { int ranges[2]; bool half[2]; double seconds; };
 // Shares of the nonzeros per block of `rows_per_block` rows taken in order of decreasing length, estimated
-// from every `stride`-th index of the COO (threaded histogram + counting sort).
-std::vector<double> block_shares(int64_t nnz, const int32_t *major, int n_major, int rows_per_block, int64_t stride);
-// ... in its two halves: the histogram of the sampled indices (count[m] = samples i * stride < nnz with major == m; an
-// upload from device memory builds the same integers there, upload_device.h), and everything after it
+// from every `stride`-th index of the COO (threaded histogram + counting sort).  In two halves: the histogram of the
+// sampled indices (count[m] = samples i * stride < nnz with major == m; an upload from device memory builds the same
+// integers there, upload_device.h), and everything after it
 std::vector<int32_t> sample_histogram(int64_t nnz, const int32_t *major, int n_major, int64_t stride);
 std::vector<double> block_shares(const std::vector<int32_t> &count, int rows_per_block);
 // block_share[s][b] = share of the nonzeros that block b of orientation s holds (rows go to blocks by

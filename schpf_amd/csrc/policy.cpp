@@ -129,15 +129,6 @@ void pick_workgroup(const Problem &p, const Tuning &tn, int n_major, int n_minor
 // fastest measured).  Against the former fixed counts (profiles/r02/explore_task_ranges.log), per
 // iteration: C3 f64 (6, 13) -> (1, 18) ranges -2.4 %, C3 f32 (3, 13) -> (3, 11) -3.3 %, half of C3's
 // cells -7.5 %, a quarter -3 %, the C5 share -1..2 % (f64) / -4 % (f32).
-bool choose_ranges(const Problem &p, const Tuning &tn, const int32_t *row, const int32_t *col, int ranges[2],
-                   int half[2])
-{
-    return choose_ranges(p, tn, [&](int64_t stride, std::vector<int32_t> hist[2]) {
-        hist[0] = sample_histogram(p.nnz, row, p.N, stride);
-        hist[1] = sample_histogram(p.nnz, col, p.G, stride);
-    }, ranges, half);
-}
-
 bool choose_ranges(const Problem &p, const Tuning &tn, const SampleHistograms &sample, int ranges[2], int half[2])
 {
     if (!p.expect_sharded && !tn.dual) return false;

@@ -57,10 +57,8 @@ Config choose_config(int K, int elem, const Tuning &tn);
 int per_cu(size_t window_lds_bytes);
 void pick_workgroup(const Problem &p, const Tuning &tn, int n_major, int n_minor, int &wpb, int &lds_kb);
 int pick_windows(size_t table_bytes);
-bool choose_ranges(const Problem &p, const Tuning &tn, const int32_t *row, const int32_t *col, int ranges[2],
-                   int half[2]);
-// ... with the sampled histograms made elsewhere: sample(stride, hist) fills hist[0][N] / hist[1][G] with the counts of
-// the row / col indices at the positions i * stride (plan.h sample_histogram).  Called only when the model runs
+// The sampled histograms are made where the COO lies: sample(stride, hist) fills hist[0][N] / hist[1][G] with the counts
+// of the row / col indices at the positions i * stride (plan.h sample_histogram).  Called only when the model runs
 using SampleHistograms = std::function<void(int64_t stride, std::vector<int32_t> hist[2])>;
 bool choose_ranges(const Problem &p, const Tuning &tn, const SampleHistograms &sample, int ranges[2], int half[2]);
 TileShape tile_shape(const Problem &p, const Tuning &tn, int n_major, int n_minor, int ranges = 0, int force_half = -1);
