@@ -222,6 +222,19 @@ int schpf_elbo_terms(schpf_ctx *ctx, double ap, double cp, double terms[5]);
  * (schpf_upload_rows) fails, as schpf_loss_terms does.  Definition: DESIGN.md 12. */
 int schpf_loss_rows(schpf_ctx *ctx, int by, double *llh_sum, double *gammaln_sum, int64_t *count);
 
+/* Posterior predictive check.  With the plug-in rates lambda_ig = sum_k E[theta_ik] E[beta_gk] (E = shape /
+ * rate of the state the engine holds), per major row r of the axis `by` and over ALL rows m of the other axis -- stored
+ * or not, the matrix plays no part and none need be uploaded:
+ *   zeros[r] = sum_m exp(-lambda_rm)   the expected number of zero entries of the row
+ *   rate[r]  = sum_m lambda_rm         the expected sum of the row
+ *   rate2[r] = sum_m lambda_rm^2       with n rows m: the predicted variance of an entry of the row is
+ *                                      rate/n + rate2/n - (rate/n)^2  (Poisson given lambda, law of total variance)
+ * Host arrays of ncells (SCHPF_BY_CELL) / ngenes (SCHPF_BY_GENE) doubles; a NULL output is skipped, all three NULL and
+ * any other `by` fail with a message.  Arithmetic in double from the stored shape / rate in both dtypes; reads the state
+ * only, no atomics: two calls on one state return the same bits, and the next iteration finds what it would have found.
+ * Its device scratch is made by the first call.  A shard: `by` cell covers the local cells; sum the genes' over the ranks. */
+int schpf_predictive_rows(schpf_ctx *ctx, int by, double *zeros, double *rate, double *rate2);
+
 int schpf_synchronize(schpf_ctx *ctx);
 
 /* Cells sharded over the GPUs of a node, the collective inside the library (RCCL over xGMI, bound

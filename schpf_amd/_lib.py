@@ -16,7 +16,7 @@ VAL_I32, VAL_I64, VAL_F32, VAL_F64 = 0, 1, 2, 3
 IDX_I32, IDX_I64 = 0, 1   # SCHPF_IDX_*: the index types of the device uploads
 STREAM_DEFAULT = 1   # SCHPF_STREAM_DEFAULT: the device's null stream
 FREEZE_GENES, SIMULTANEOUS, SHARDED, CELLS_FIRST, LOCAL_GENE, LOCAL_CELL = 1, 2, 4, 8, 16, 32
-BY_CELL, BY_GENE = 0, 1   # SCHPF_BY_CELL / SCHPF_BY_GENE: the axis of schpf_loss_rows
+BY_CELL, BY_GENE = 0, 1   # SCHPF_BY_CELL / SCHPF_BY_GENE: the axis of schpf_loss_rows / schpf_predictive_rows
 # SCHPF_SPECIAL_*: the function schpf_debug_special evaluates
 SPECIAL_RCP, SPECIAL_LOG, SPECIAL_EXP, SPECIAL_PSI, SPECIAL_PSI_LESS_LOG = 0, 1, 2, 3, 4
 
@@ -59,6 +59,7 @@ SIGNATURES = {
     "schpf_loss_terms": [_vp, _dblp, _dblp, _i64p],
     "schpf_elbo_terms": [_vp, _dbl, _dbl, _dblp],
     "schpf_loss_rows": [_vp, _int, _dblp, _dblp, _i64p],
+    "schpf_predictive_rows": [_vp, _int, _dblp, _dblp, _dblp],
     "schpf_synchronize": [_vp],
     "schpf_hint_sharded": [_vp, _int],
     "schpf_hint_transient": [_vp, _int],

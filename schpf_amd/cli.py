@@ -120,6 +120,10 @@ def _parser():
     score.add_argument("-i", "--input", default=None,
                        help="The count matrix the model was fitted to (same formats as `train -i`): also write the mean "
                             "negative log-likelihood of each cell and each gene (cell_loss.txt, gene_loss.txt).")
+    score.add_argument("--ppc", default=False, action="store_true",
+                       help="With -i: also write the posterior predictive check per gene and per cell (gene_ppc.txt, "
+                            "cell_ppc.txt): predicted mean, variance and fraction of zeros over all entries of the row, "
+                            "then the observed ones.")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -291,8 +295,17 @@ def _score(args, outprefix):
         print("Saving per-cell and per-gene loss.....")
         np.savetxt(outprefix + "cell_loss.txt", ls.cellmean_negative_pois_llh(data, theta=model.theta, beta=model.beta))
         np.savetxt(outprefix + "gene_loss.txt", ls.genemean_negative_pois_llh(data, theta=model.theta, beta=model.beta))
+        if args.ppc:
+            print("Saving posterior predictive checks.....")
+            for by in ("gene", "cell"):
+                ppc = ls.predictive_check(data, theta=model.theta, beta=model.beta, by=by)
+                np.savetxt(outprefix + by + "_ppc.txt", np.stack([ppc[c] for c in ls.PPC_COLUMNS], axis=1))
     else:
+        if args.ppc:
+            raise ValueError("--ppc needs the count matrix (-i)")
         del args.input   # the arguments file of a run without the matrix stays what it was
+    if not args.ppc:
+        del args.ppc     # ... and so does the arguments file of a run without the check
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

@@ -50,6 +50,7 @@ template <typename T> struct Engine final : Uploader {
     DevBuf dual_queue;                              // persistent dual launch: {next slot, workgroups done}, self-zeroing
     DevBuf clock_probe;                             // 5 x u64: shader cycles, constant-rate ticks, 2 start stamps, launches (sweep_impl.h)
     DevBuf elbo_part, elbo_sums;                    // ELBO: Gamma-term block partials, their sums (elbo_terms)
+    DevBuf ppc_e[2], ppc_out;                       // predictive_rows: E of each side as doubles; [zeros | rate | rate2] of an axis
     int beta_parity = 0;               // swaps of the sum-of-beta buffers mod 2: which cached graph fits (schpf_ctx::graphs)
     // small problems: the update kernels sum the other side's per-block column sums themselves and the
     // two reduce launches of an iteration are skipped; s_theta / s_beta are then brought up to date
@@ -670,6 +671,28 @@ template <typename T> struct Engine final : Uploader {
         HIPCHK(hipStreamSynchronize(stream));
     }
 
+    // Per major row of axis `by`, over ALL rows of the other axis: sum exp(-lambda), sum lambda, sum lambda^2 with lambda =
+    // E theta . E beta.  From the stored shape / rate, not the tables (which may be older, sums_stale /
+    // dirty, and stay so); needs no matrix; writes its own scratch only.  No clock probe, never captured, as elbo_terms.
+    void predictive_rows(int by, double *zeros, double *rate, double *rate2) override
+    {
+        if (by != SCHPF_BY_CELL && by != SCHPF_BY_GENE) throw std::invalid_argument("by is neither SCHPF_BY_CELL nor SCHPF_BY_GENE");
+        if (!zeros && !rate && !rate2) throw std::invalid_argument("zeros, rate and rate2 are all NULL: nothing to return");
+        const size_t n = (size_t)side[by].n;
+        for (int s = 0; s < 2; ++s) {
+            const size_t bytes = (size_t)schpf::predictive_pad(side[s].n) * K * sizeof(double);
+            if (ppc_e[s].bytes < bytes) ppc_e[s].alloc(bytes);
+            HIPCHK(schpf::launch_predictive_e<T>(side[s].shape.as<T>(), side[s].rate.as<T>(), side[s].n, K, ppc_e[s].as<double>(), stream));
+        }
+        if (ppc_out.bytes < 3 * n * sizeof(double)) ppc_out.alloc(3 * (size_t)std::max(N, G) * sizeof(double));
+        HIPCHK(schpf::launch_predictive_rows(ppc_e[by].as<double>(), ppc_e[1 - by].as<double>(), side[by].n, side[1 - by].n, K,
+                                             schpf::predictive_strip(side[by].n, cu_count), ppc_out.as<double>(), stream));
+        double *const dst[3] = {zeros, rate, rate2};
+        for (int i = 0; i < 3; ++i)
+            if (dst[i]) HIPCHK(hipMemcpyAsync(dst[i], ppc_out.as<double>() + i * n, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+
     // schpf_debug_tables: a side's tables as the next sweep would read them, padding columns included.  Touches what
     // loss_terms touches before its sweep (refresh_tables) and nothing else
     void debug_tables(int s, void *tab_e, void *tab_log, void *tab_exp) override
@@ -897,6 +920,10 @@ int schpf_loss_rows(schpf_ctx *ctx, int by, double *llh_sum, double *gammaln_sum
     if (!ctx) return fail("ctx is NULL");
     if (!llh_sum || !gammaln_sum || !count) return fail("output pointer is NULL");
     CTX_CALL(ctx->loss_rows(by, llh_sum, gammaln_sum, count));
+}
+int schpf_predictive_rows(schpf_ctx *ctx, int by, double *zeros, double *rate, double *rate2)
+{
+    CTX_CALL(ctx->predictive_rows(by, zeros, rate, rate2));
 }
 int schpf_synchronize(schpf_ctx *ctx) { CTX_CALL(HIPCHK(hipStreamSynchronize(ctx->stream))); }
 

@@ -68,8 +68,8 @@ struct TileDev : PlanFacts {
 // state (Engine<T>: Side's buffers, the exchange buffer, column sums, dual_queue, clock_probe) never change after
 // schpf_create.  Those of this record change only in Uploader::forget_matrix, which drops the graphs first, and during
 // the upload that follows it, when no graph exists and none can be captured (have_coo is false until the record is
-// complete; an upload that fails leaves a fresh record).  rows_rec, rows_out and zero_rows -- and the engine's elbo_part / elbo_sums -- may be made or grown by the
-// call that needs them: only the loss, ELBO and per-row passes read them, and those are never captured.
+// complete; an upload that fails leaves a fresh record).  rows_rec, rows_out and zero_rows -- and the engine's elbo_part / elbo_sums and ppc_e / ppc_out -- may be made or grown by the
+// call that needs them: only the loss, ELBO, per-row and predictive passes read them, and those are never captured.
 struct Matrix {
     struct Axis {
         DevBuf count;               // ELBO: sum of the stored counts of each row of this axis, double[n]
@@ -187,6 +187,7 @@ struct schpf_ctx {
     virtual void loss_terms(double *llh, double *gl, int64_t *nnz) = 0;
     virtual void elbo_terms(double ap, double cp, double terms[5]) = 0;
     virtual void loss_rows(int by, double *llh, double *gl, int64_t *count) = 0;
+    virtual void predictive_rows(int by, double *zeros, double *rate, double *rate2) = 0;
     virtual void plan_info(int64_t info[16]) = 0;
     virtual void debug_tables(int side, void *tab_e, void *tab_log, void *tab_exp) = 0;
     virtual void upload_info(int64_t info[4]) = 0;

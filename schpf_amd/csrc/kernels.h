@@ -197,6 +197,17 @@ template <typename T>
 hipError_t launch_elbo_gamma(const T *shape, const T *rate, const T *cap_shape, const T *cap_rate, const T *log_tab,
                              const double *counts, int n, int K, int KP, double prior, double cap_prior_shape,
                              double cap_prior_rate, double *part, int nblocks, hipStream_t st);
+// Posterior predictive row sums (predictive.hip).  launch_predictive_e: E = shape / rate of one side as
+// doubles, etab[predictive_pad(n) * K] in the blocked layout the tiles are staged from.  launch_predictive_rows: per
+// major row the sums over ALL minor rows of exp(-lambda), lambda, lambda^2 (lambda = E_major . E_minor), out = [zeros |
+// rate | rate2] of n_major doubles each; strip = major rows per workgroup, predictive_strip()'s choice
+inline int predictive_pad(int n) { return (int)(((int64_t)n + 127) / 128 * 128); }
+// 64 x 64 pairs per tile unless the strips of 64 would not give every compute unit four workgroups: then 32 x 128
+inline int predictive_strip(int n_major, int cu_count) { return (n_major + 63) / 64 >= 4 * cu_count ? 64 : 32; }
+template <typename T>
+hipError_t launch_predictive_e(const T *shape, const T *rate, int n, int K, double *etab, hipStream_t st);
+hipError_t launch_predictive_rows(const double *e_major, const double *e_minor, int n_major, int n_minor, int K, int strip,
+                                  double *out, hipStream_t st);
 hipError_t launch_digamma_array(const double *x, int64_t n, double *out, hipStream_t st);
 hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStream_t st);
 

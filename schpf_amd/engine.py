@@ -37,6 +37,14 @@ def rowmean_negative(llh, gl, count):
 _AXES = {"cell": _lib.BY_CELL, "gene": _lib.BY_GENE}
 
 ELBO_TERMS = ("data", "logfac", "rate", "cell", "gene")
+PREDICTIVE_SUMS = ("zeros", "rate", "rate2")
+
+
+def predicted_moments(sums, n):
+    """(mean, variance, fraction of zeros) of an entry of each row from its predictive sums over n entries: given
+    lambda the entry is Poisson, so its variance over the row is E[lambda] + Var[lambda] (law of total variance)."""
+    mean = sums["rate"] / n
+    return mean, mean + sums["rate2"] / n - mean * mean, sums["zeros"] / n
 
 
 def elbo_dict(data, logfac, rate, cell, gene):
@@ -347,6 +355,27 @@ class DeviceCAVI(object):
     def genemean_negative_pois_llh(self):
         """Mean negative Poisson log-likelihood of each gene's stored entries (NaN for a gene without any)."""
         return rowmean_negative(*self.loss_rows("gene"))
+
+    def predictive_rows(self, by="gene", which=PREDICTIVE_SUMS):
+        """Posterior predictive sums of the state the engine holds: per cell (by="cell") or per gene
+        (by="gene"), over ALL rows m of the other axis, with lambda = E[theta] . E[beta]: {"zeros": sum exp(-lambda),
+        "rate": sum lambda, "rate2": sum lambda^2}, float64 arrays of ncells / ngenes.  No matrix need be uploaded; the
+        state is only read, and two calls on one state return the same bits.  `which`: the sums wanted (the others are
+        not copied back)."""
+        if by in _AXES:
+            code = _AXES[by]
+        elif isinstance(by, int) and not isinstance(by, bool):
+            code = by       # an axis code of the C ABI; the library refuses what it does not know
+        else:
+            raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
+        unknown = [w for w in which if w not in PREDICTIVE_SUMS]
+        if unknown:
+            raise ValueError("which must be drawn from %s, got %r" % (PREDICTIVE_SUMS, unknown))
+        n = self.ngenes if code == _lib.BY_GENE else self.ncells
+        out = {w: np.empty(n, np.float64) for w in PREDICTIVE_SUMS if w in which}
+        ptr = [out[w].ctypes.data_as(_lib._dblp) if w in out else None for w in PREDICTIVE_SUMS]
+        _lib.check(self._lib.schpf_predictive_rows(self._h, code, *ptr))
+        return out
 
     def elbo_terms(self, ap, cp):
         """The evidence lower bound of the current state over the local cells, by term:

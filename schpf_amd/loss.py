@@ -14,7 +14,10 @@ from .hpf_hip import compute_pois_llh
 
 __all__ = ["loss_function_for_data", "projection_loss_function", "pois_llh_pointwise",
            "mean_negative_pois_llh", "elbo", "cellmean_negative_pois_llh", "genemean_negative_pois_llh",
-           "thinned_mean_negative_pois_llh"]
+           "thinned_mean_negative_pois_llh", "predictive_check"]
+
+# what predictive_check returns, in the column order of `scHPF score --ppc`
+PPC_COLUMNS = ("pred_mean", "pred_var", "pred_zero_frac", "obs_mean", "obs_var", "obs_zero_frac")
 
 
 def loss_function_for_data(loss_function, X):
@@ -173,3 +176,64 @@ def genemean_negative_pois_llh(X, *, theta, beta, device=None, **kwargs):
     """Mean negative Poisson log-likelihood of the stored entries of each gene of X (NaN for a gene without any),
     float64 [ngenes], evaluated on the GPU.  `device`: HIP device ordinal, default $SCHPF_DEVICE or 0."""
     return _rowmean_on_device(X, theta, beta, "gene", device)
+
+
+def observed_moments(X, by):
+    """Per row of the axis `by` of X ("cell": rows, "gene": columns), over ALL its entries, stored or not: (mean,
+    population variance, fraction of zeros), float64 -- from sum x, sum x^2 and the number of entries with x > 0, after
+    duplicate coordinates have been summed.  SciPy input: on the host.  A torch sparse tensor: with torch ops where it
+    lives (in GPU memory nothing of O(nnz) comes to the host)."""
+    from .device_input import is_torch_tensor
+    if by not in ("cell", "gene"):
+        raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
+    axis = 0 if by == "cell" else 1
+    n_rows, n = int(X.shape[axis]), int(X.shape[1 - axis])
+    if is_torch_tensor(X):
+        import torch
+        if X.layout != torch.sparse_coo:
+            X = X.to_sparse_coo()
+        X = X.coalesce()                       # duplicates summed
+        major, x = X.indices()[axis], X.values().to(torch.float64)
+        sums = [torch.zeros(n_rows, dtype=torch.float64, device=x.device).index_add_(0, major, v)
+                for v in (x, x * x, (x > 0).to(torch.float64))]
+        s1, s2, pos = (v.cpu().numpy() for v in sums)
+    else:
+        from scipy.sparse import coo_matrix
+        C = X.tocoo() if not hasattr(X, "row") else X
+        C = coo_matrix((np.asarray(C.data, np.float64), (C.row, C.col)), shape=C.shape)   # a copy: X stays as it is
+        C.sum_duplicates()
+        major = C.row if axis == 0 else C.col
+        s1 = np.bincount(major, weights=C.data, minlength=n_rows)
+        s2 = np.bincount(major, weights=C.data * C.data, minlength=n_rows)
+        pos = np.bincount(major, weights=(C.data > 0).astype(np.float64), minlength=n_rows)
+    mean = s1 / n
+    return mean, s2 / n - mean * mean, (n - pos) / n
+
+
+def predictive_check(X, *, theta, beta, by="gene", device=None, **kwargs):
+    """Posterior predictive check of a Poisson factor model without zero inflation: per gene (by="gene")
+    or per cell (by="cell"), what the model predicts for the mean, the variance and the fraction of zeros of the row's
+    entries -- over ALL cell x gene pairs, from lambda = E[theta] . E[beta], summed on the GPU -- next to what X shows.
+
+    Returns a dict of float64 arrays, one value per row of the axis: pred_mean, pred_var, pred_zero_frac and, unless X is
+    None, obs_mean, obs_var (population variance), obs_zero_frac.  X: a SciPy sparse matrix or a torch sparse tensor
+    (duplicate coordinates are summed first); it is not uploaded.  A theta whose rate is divided by frac / (1 - frac)
+    gives the check for the test part of thinned counts.  `device`: HIP device ordinal, default $SCHPF_DEVICE or 0."""
+    from .engine import DeviceCAVI, predicted_moments   # late import, as in projection_loss_function
+    import os
+    if by not in ("cell", "gene"):
+        raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
+    ncells, ngenes = theta.vi_shape.shape[0], beta.vi_shape.shape[0]
+    if X is not None and tuple(int(v) for v in X.shape) != (ncells, ngenes):
+        raise ValueError("X has shape %s, theta and beta describe %d cells x %d genes" % (tuple(X.shape), ncells, ngenes))
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    with DeviceCAVI(ncells, ngenes, theta.dims[1], dtype=theta.dtype, device=device) as eng:
+        eng.set_gamma("theta", theta.vi_shape, theta.vi_rate)
+        eng.set_gamma("beta", beta.vi_shape, beta.vi_rate)
+        sums = eng.predictive_rows(by)
+    out = dict(zip(PPC_COLUMNS[:3], predicted_moments(sums, ngenes if by == "cell" else ncells)))
+    if X is not None:
+        out.update(zip(PPC_COLUMNS[3:], observed_moments(X, by)))
+    return out
+

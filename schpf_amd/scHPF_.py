@@ -294,6 +294,12 @@ class scHPF(BaseEstimator):
         beta = self.beta if beta is None else beta
         return ls.genemean_negative_pois_llh(X, theta=theta, beta=beta, device=device)
 
+    def predictive_check(self, X=None, by="gene", device=None):
+        """Posterior predictive check of the fitted model (schpf_amd.loss.predictive_check; an addition to the
+        reference's surface): predicted mean, variance and fraction of zeros per gene or per cell, over all cell x gene
+        pairs, and the observed ones of X unless X is None."""
+        return ls.predictive_check(X, theta=self.theta, beta=self.beta, by=by, device=device)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
