@@ -340,6 +340,35 @@ int schpf_debug_thin_counts(int64_t nnz, const int32_t *row, const int32_t *col,
                             double frac, uint64_t seed, int32_t *train, int32_t *test, int64_t stats[4]);
 int schpf_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
 
+/* Nearest neighbours in factor space: for every row of query[n_query, nfactors] its k nearest rows of
+ * ref[n_ref, nfactors], exact (every pair is looked at), both row-major and of `dtype`.  Definition, which the result
+ * equals bit for bit however the work was scheduled:
+ *   every value is converted to double (exact);  d2(q, r) = the result of
+ *       d2 = 0;  for f = 0 .. nfactors - 1, in this order:  d = query[q][f] - ref[r][f];  d2 = fma(d, d, d2)
+ *   in double with exactly this subtraction and this fused multiply-add (not |a|^2 + |b|^2 - 2ab, which cancels);
+ *   the pairs of a query row are ordered by the key (d2, r): the smaller d2 first, equal d2 by the smaller r -- a total
+ *   order, so the k smallest are unique;
+ *   self_first >= 0 removes the one pair r == self_first + q from row q (a cell as its own neighbour: by index, not by
+ *   distance, so duplicate rows at distance 0 stay neighbours); self_first = -1 removes nothing.
+ *   idx[q * k + j] (int32) and d2[q * k + j] (double), j < k: the k smallest pairs of row q, ascending in the key.
+ * 1 <= k <= 128 and k <= the admissible reference rows of every query row; 1 <= nfactors <= 256; n_query, n_ref <
+ * 2^31 - 128.  n_query = 0 succeeds and writes nothing; n_ref = 0, a k out of range and NULL pointers fail with a message.
+ * Non-finite values are refused before anything is selected, with "scores must be finite; offending row N of query" (or
+ * "of ref"), N the smallest such row, query before ref; nothing is written then.  With finite inputs d2 is never NaN; a d2
+ * that overflows is +inf and sorts by r.  query == ref (the same pointer, n_query == n_ref) is the usual self graph, with
+ * self_first = 0.  Stateless; device memory that cannot be had returns SCHPF_ERR_NO_MEMORY.
+ * _device: query, ref, idx and d2 are DEVICE pointers on `device`; stream as in schpf_create (NULL = a stream of the
+ *   call's own), on which the inputs must be complete or ordered; synchronised before the call returns.
+ * schpf_knn: host pointers, staged through the device; the same result.
+ * schpf_debug_knn: test hook (host only, no GPU needed): the serial restatement of the definition -- a loop over the pairs
+ *   with std::fma and a partial sort on the key -- which both must match bit for bit. */
+int schpf_knn_device(int device, void *stream, int dtype, int n_query, int n_ref, int nfactors, const void *query,
+                     const void *ref, int k, int64_t self_first, int32_t *idx, double *d2);
+int schpf_knn(int device, int dtype, int n_query, int n_ref, int nfactors, const void *query, const void *ref, int k,
+              int64_t self_first, int32_t *idx, double *d2);
+int schpf_debug_knn(int dtype, int n_query, int n_ref, int nfactors, const void *query, const void *ref, int k,
+                    int64_t self_first, int32_t *idx, double *d2);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

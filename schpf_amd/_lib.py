@@ -82,6 +82,9 @@ SIGNATURES = {
     "schpf_thin_counts": [_int, _i64, _vp, _vp, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
     "schpf_debug_thin_counts": [_i64, _vp, _vp, _vp, _int, _dbl, ctypes.c_uint64, _vp, _vp, _i64p],
     "schpf_debug_philox": [_vp, _vp, _vp],
+    "schpf_knn_device": [_int, _vp, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp],
+    "schpf_knn": [_int, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp],
+    "schpf_debug_knn": [_int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_plan_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int,

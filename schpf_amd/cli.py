@@ -124,6 +124,11 @@ def _parser():
                        help="With -i: also write the posterior predictive check per gene and per cell (gene_ppc.txt, "
                             "cell_ppc.txt): predicted mean, variance and fraction of zeros over all entries of the row, "
                             "then the observed ones.")
+    score.add_argument("--knn", type=int, default=None, metavar="K",
+                       help="Also write the K nearest cells of every cell in factor space, none its own neighbour "
+                            "(knn_indices.txt, knn_distances.txt: one row per cell, nearest first).  Needs no count matrix.")
+    score.add_argument("--knn-metric", default="euclidean", choices=["euclidean", "cosine"],
+                       help="Distance of --knn between cell scores. [euclidean]")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -306,6 +311,13 @@ def _score(args, outprefix):
         del args.input   # the arguments file of a run without the matrix stays what it was
     if not args.ppc:
         del args.ppc     # ... and so does the arguments file of a run without the check
+    if args.knn is not None:
+        print("Saving nearest neighbours.....")
+        indices, distances = model.neighbors(k=args.knn, metric=args.knn_metric)
+        np.savetxt(outprefix + "knn_indices.txt", indices, fmt="%d", delimiter="\t")
+        np.savetxt(outprefix + "knn_distances.txt", distances, delimiter="\t")
+    else:
+        del args.knn, args.knn_metric   # ... and of a run without the neighbours
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

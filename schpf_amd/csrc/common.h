@@ -83,6 +83,25 @@ inline double read_count(const void *val, int kind, int64_t i)
     }
 }
 
+// What schpf_knn, schpf_knn_device and schpf_debug_knn refuse alike (include/schpf_hip.h); n_query = 0 is asked first by
+// the caller.  nullptr: the arguments are fine
+inline const char *knn_bad_args(int dtype, int n_query, int n_ref, int nfactors, const void *query, const void *ref, int k,
+                                int64_t self_first, const void *idx, const void *d2)
+{
+    if (bad_dtype(dtype)) return "dtype must be SCHPF_F32 or SCHPF_F64";
+    if (nfactors < 1 || nfactors > 256) return "nfactors must be in [1, 256]";
+    if (k < 1 || k > 128) return "k must be in [1, 128]";
+    if (self_first < -1) return "self_first must be -1 or the reference row of query row 0";
+    if (n_query < 0 || n_query > INT32_MAX - 128 || n_ref > INT32_MAX - 128) return "n_query and n_ref must be in [0, 2^31 - 128)";
+    if (n_query == 0) return nullptr;
+    if (n_ref < 1) return "n_ref must be at least 1";
+    if (!query || !ref || !idx || !d2) return "query, ref, idx and d2 must not be NULL";
+    // query row 0 loses a reference row iff self_first names one, and no row loses more than one
+    const int admissible = n_ref - (self_first >= 0 && self_first < n_ref ? 1 : 0);
+    if (k > admissible) return "k must be at most the admissible reference rows of every query row";
+    return nullptr;
+}
+
 // RAII device buffer
 struct DevBuf {
     void *p = nullptr;

@@ -1,10 +1,12 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
-// check the host builders with, the serial restatement of count thinning (thin.hip) and the SCHPF_BACKTRACE crash
-// handler.  Nothing here touches the device.
+// check the host builders with, the serial restatements of count thinning (thin.hip) and of the nearest-neighbour search
+// (knn.hip) and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <thread>
 
@@ -281,6 +283,56 @@ int schpf_debug_thin_counts(int64_t nnz, const int32_t *row, const int32_t *col,
             stats[2] += x - hits;
             stats[3] += hits;
         }
+    });
+}
+
+// knn.hip restated: per query row a plain loop over the pairs -- one subtraction and one std::fma per factor,
+// in factor order -- and a partial sort on the key (d2, r).  The query rows, independent of each other, are dealt to the
+// host threads
+int schpf_debug_knn(int dtype, int n_query, int n_ref, int nfactors, const void *query, const void *ref, int k,
+                    int64_t self_first, int32_t *idx, double *d2)
+{
+    if (const char *why = knn_bad_args(dtype, n_query, n_ref, nfactors, query, ref, k, self_first, idx, d2)) return fail("%s", why);
+    if (n_query == 0) return 0;
+    return guarded([&] {
+        const size_t K = (size_t)nfactors;
+        auto value = [&](const void *x, size_t i) { return dtype == SCHPF_F32 ? (double)((const float *)x)[i] : ((const double *)x)[i]; };
+        auto refuse = [&](const void *x, int n, const char *side) {
+            for (int r = 0; r < n; ++r)
+                for (size_t f = 0; f < K; ++f)
+                    if (!std::isfinite(value(x, (size_t)r * K + f)))
+                        throw std::invalid_argument("scores must be finite; offending row " + std::to_string(r) + " of " + side);
+        };
+        refuse(query, n_query, "query");
+        refuse(ref, n_ref, "ref");
+        std::vector<double> rd((size_t)n_ref * K);
+        for (size_t i = 0; i < rd.size(); ++i) rd[i] = value(ref, i);
+        const int nth = std::max(1, std::min(std::min(schpf::host_threads(), 16), n_query));
+        std::vector<std::thread> th;
+        for (int t = 0; t < nth; ++t)
+            th.emplace_back([&, t] {
+                std::vector<std::pair<double, int32_t>> keys;
+                std::vector<double> qd(K);
+                for (int q = t; q < n_query; q += nth) {
+                    for (size_t f = 0; f < K; ++f) qd[f] = value(query, (size_t)q * K + f);
+                    keys.clear();
+                    for (int r = 0; r < n_ref; ++r) {
+                        if (self_first >= 0 && (int64_t)r == self_first + q) continue;   // by index, not by distance
+                        double s = 0.0;
+                        for (size_t f = 0; f < K; ++f) {
+                            const double d = qd[f] - rd[(size_t)r * K + f];
+                            s = std::fma(d, d, s);
+                        }
+                        keys.emplace_back(s, r);
+                    }
+                    std::partial_sort(keys.begin(), keys.begin() + k, keys.end());   // pairs compare as the key does
+                    for (int j = 0; j < k; ++j) {
+                        d2[(size_t)q * k + j] = keys[(size_t)j].first;
+                        idx[(size_t)q * k + j] = keys[(size_t)j].second;
+                    }
+                }
+            });
+        for (auto &x : th) x.join();
     });
 }
 

@@ -208,6 +208,38 @@ template <typename T>
 hipError_t launch_predictive_e(const T *shape, const T *rate, int n, int K, double *etab, hipStream_t st);
 hipError_t launch_predictive_rows(const double *e_major, const double *e_minor, int n_major, int n_minor, int K, int strip,
                                   double *out, hipStream_t st);
+// k nearest neighbours between two sets of rows (knn.hip).  launch_knn_table: one side's rows as doubles,
+// tab[knn_pad(n) * K] in the blocked layout [row / 64][k][row % 64], padding rows 0; bad_part[knn_table_blocks(n, K)]
+// takes per block the smallest row that holds a non-finite value (INT_MAX: none).  launch_knn_bad: the minima of both
+// sides' bad_part, bad[0] query, bad[1] ref (n_*_blocks = 0: that side was not looked at).  launch_knn_select: a
+// workgroup per (strip of 64 query rows, segment of seg_tiles tiles of 64 reference rows) leaves the segment's sorted
+// best min(k, admissible) keys (d2, r) of every row at [(q * n_seg + s) * k ...) of idx / d2 and their number in
+// cnt[q * n_seg + s] (nullptr with n_seg = 1: the final lists).  launch_knn_merge: the n_seg lists of a row -> its k best
+inline int knn_pad(int n) { return (int)(((int64_t)n + 127) / 128 * 128); }
+inline int64_t knn_table_blocks(int n, int K) { return ((int64_t)knn_pad(n) * K + 255) / 256; }
+// Strips of 64 query rows alone fill the chip when there are two per compute unit.  With fewer, the reference axis is cut
+// into as many segments as bring the grid there, each at least 16 tiles (1024 rows) long, 64 at the most
+inline int knn_segments(int n_query, int n_ref, int cu_count)
+{
+    const int64_t strips = ((int64_t)n_query + 63) / 64, want = 2 * (int64_t)cu_count;
+    if (strips >= want) return 1;
+    const int64_t longest = ((int64_t)n_ref + 63) / 64 / 16;
+    int64_t s = (want + strips - 1) / strips;
+    s = s < longest ? s : longest;
+    return (int)(s < 1 ? 1 : s > 64 ? 64 : s);
+}
+// factors staged per pass of the select kernel and its LDS bytes: 32 factors unless the lists of a large k leave no room
+inline size_t knn_lds_bytes(int k, int kc) { return 8 * ((size_t)128 * kc + 64 * 64 + 64 * (size_t)k + 64) + 4 * (64 * (size_t)k + 192); }
+inline int knn_stage_factors(int k) { return knn_lds_bytes(k, 32) <= 160 * 1024 ? 32 : 16; }
+template <typename T>
+hipError_t launch_knn_table(const T *x, int n, int K, double *tab, int *bad_part, hipStream_t st);
+hipError_t launch_knn_bad(const int *part_query, int64_t n_query_blocks, const int *part_ref, int64_t n_ref_blocks, int *bad,
+                          hipStream_t st);
+hipError_t launch_knn_select(const double *qtab, const double *rtab, int n_query, int n_ref, int K, int k,
+                             int64_t self_first, int seg_tiles, int n_seg, int32_t *idx, double *d2, int *cnt,
+                             hipStream_t st);
+hipError_t launch_knn_merge(const int32_t *part_idx, const double *part_d2, const int *part_cnt, int n_query, int n_seg,
+                            int k, int32_t *idx, double *d2, hipStream_t st);
 hipError_t launch_digamma_array(const double *x, int64_t n, double *out, hipStream_t st);
 hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStream_t st);
 

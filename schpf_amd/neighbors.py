@@ -1,0 +1,150 @@
+"""Nearest neighbours of cells in factor space on the GPU: the exact k-NN graph of cell scores.
+
+The cell-score matrix of a fitted model goes straight into a k-nearest-neighbour graph (UMAP, Phenograph, Leiden), and,
+with `scHPF.project`, into label transfer: every projected cell's nearest cells of the atlas.  The search runs in the
+library (schpf_knn[_device]): every pair is looked at, nothing of size n_query x n_ref ever exists, and the result is
+defined bit for bit -- squared distances by one subtraction and one fused multiply-add per factor in double, ties by the
+smaller index.  Here are the argument plumbing, the two metrics and the assembly of the sparse graph.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["knn", "knn_graph"]
+
+METRICS = ("euclidean", "cosine")
+_DTYPES = {np.dtype(np.float32): _lib.F32, np.dtype(np.float64): _lib.F64}
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _unit_rows(x, name):
+    """Rows scaled to unit length (cosine: |a - b|^2 / 2 = 1 - cos for unit a, b); plumbing, in NumPy or torch."""
+    if _is_tensor(x):
+        import torch
+        norm = torch.linalg.vector_norm(x, dim=1, keepdim=True)
+        zero = bool((norm == 0).any())
+    else:
+        norm = np.sqrt((x * x).sum(axis=1, keepdims=True))
+        zero = bool((norm == 0).any())
+    if zero:
+        raise ValueError("metric='cosine' needs nonzero rows; %s has a zero row" % name)
+    return x / norm
+
+
+def _check(metric, k):
+    if metric not in METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (", ".join(METRICS), metric))
+    k = int(k)
+    if not 1 <= k <= 128:
+        raise ValueError("k must be in [1, 128], got %d" % k)
+    return k
+
+
+def _search_host(query, ref, k, self_first, device):
+    """schpf_knn on two C-contiguous NumPy matrices of one dtype (float32 / float64) -> (idx, d2)."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    idx = np.empty((query.shape[0], k), np.int32)
+    d2 = np.empty((query.shape[0], k), np.float64)
+    _lib.check(lib.schpf_knn(int(device), _DTYPES[query.dtype], query.shape[0], ref.shape[0], query.shape[1], _p(query),
+                             _p(ref), k, ctypes.c_int64(self_first), _p(idx), _p(d2)))
+    return idx, d2
+
+
+def knn(query, ref=None, k=15, metric="euclidean", exclude_self=None, device=None):
+    """(indices, distances) of the k nearest rows of `ref` for every row of `query`: int32 and float64, n_query x k,
+    ascending in distance, equal distances by the smaller index.
+
+    query, ref: n x K arrays of cell scores, float32 or float64 (anything else is converted to float64), NumPy or torch.
+    A torch tensor in GPU memory stays there and two torch tensors on the same GPU come back, the call running on
+    torch's current stream; NumPy in gives NumPy out.  ref=None is the self graph: query against itself.
+
+    exclude_self: leave row q of the reference out of query row q's neighbours -- a cell as its own neighbour; by index,
+    so duplicated cells at distance 0 stay neighbours.  Default: True for the self graph, False with a `ref`.
+
+    metric: "euclidean" returns the distance sqrt(d2); "cosine" normalises the rows to unit length first and returns
+    d2 / 2 = 1 - cos (a zero row raises ValueError).  Non-finite values raise ValueError naming the smallest offending
+    row.  `device`: HIP device ordinal, default the tensor's GPU, else $SCHPF_DEVICE or 0.
+    """
+    k = _check(metric, k)
+    self_graph = ref is None
+    if exclude_self is None:
+        exclude_self = self_graph
+    tensors = _is_tensor(query)
+    if not self_graph and _is_tensor(ref) != tensors:
+        raise ValueError("query and ref must both be NumPy arrays or both be torch tensors")
+    if tensors and not query.is_cuda:      # a tensor in host memory: as NumPy, and back
+        import torch
+        idx, dist = knn(query.numpy(), None if self_graph else ref.cpu().numpy(), k, metric, exclude_self, device)
+        return torch.from_numpy(idx), torch.from_numpy(dist)
+    self_first = 0 if exclude_self else -1
+
+    if not tensors:
+        query = np.asarray(query)
+        dtype = query.dtype if query.dtype in _DTYPES else np.dtype(np.float64)
+        query = np.ascontiguousarray(query, dtype=dtype)
+        ref = query if self_graph else np.ascontiguousarray(ref, dtype=dtype)
+        if query.ndim != 2 or ref.ndim != 2 or query.shape[1] != ref.shape[1]:
+            raise ValueError("query and ref must be matrices with the same number of columns")
+        if metric == "cosine":
+            query = np.ascontiguousarray(_unit_rows(query, "query"))
+            ref = query if self_graph else np.ascontiguousarray(_unit_rows(ref, "ref"))
+        idx, d2 = _search_host(query, ref, k, self_first, device)
+        return idx, (np.sqrt(d2) if metric == "euclidean" else d2 / 2)
+
+    import torch
+    lib = _lib.load()
+    _lib.require_gpu()
+    _TORCH = {torch.float32: _lib.F32, torch.float64: _lib.F64}
+    dev = query.device
+    if device is not None and int(device) != dev.index:
+        raise ValueError("query is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+    if not self_graph and ref.device != dev:
+        raise ValueError("query is on %s, ref on %s" % (dev, ref.device))
+    dtype = query.dtype if query.dtype in _TORCH else torch.float64
+    query = query.detach().to(dtype).contiguous()
+    ref = query if self_graph else ref.detach().to(dtype).contiguous()
+    if query.dim() != 2 or ref.dim() != 2 or query.shape[1] != ref.shape[1]:
+        raise ValueError("query and ref must be matrices with the same number of columns")
+    with torch.cuda.device(dev):
+        if metric == "cosine":
+            query = _unit_rows(query, "query").contiguous()
+            ref = query if self_graph else _unit_rows(ref, "ref").contiguous()
+        idx = torch.empty((query.shape[0], k), dtype=torch.int32, device=dev)
+        d2 = torch.empty((query.shape[0], k), dtype=torch.float64, device=dev)
+        # on torch's current stream: ordered after whatever produced the scores and before whatever reads the result
+        stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+        _lib.check(lib.schpf_knn_device(dev.index, ctypes.c_void_p(stream), _TORCH[dtype], query.shape[0], ref.shape[0],
+                                        query.shape[1], ptr(query), ptr(ref), k, ctypes.c_int64(self_first), ptr(idx),
+                                        ptr(d2)))
+        return idx, (torch.sqrt(d2) if metric == "euclidean" else d2 / 2)
+
+
+def knn_graph(indices, distances, n_ref):
+    """The neighbour lists as a SciPy CSR matrix n_query x n_ref that holds the distances: row q has the entries
+    (indices[q, j], distances[q, j]) -- the layout of scanpy's obsp["distances"] and of UMAP's precomputed input.
+    A neighbour at distance 0 (a duplicated cell) is stored explicitly."""
+    from scipy.sparse import csr_matrix
+    if _is_tensor(indices):
+        indices, distances = indices.cpu().numpy(), distances.cpu().numpy()
+    indices, distances = np.asarray(indices), np.asarray(distances)
+    if indices.ndim != 2 or indices.shape != distances.shape:
+        raise ValueError("indices and distances must be matrices of one shape")
+    n_query, k = indices.shape
+    if indices.size and (indices.min() < 0 or indices.max() >= n_ref):
+        raise ValueError("indices must be in [0, n_ref)")
+    indptr = np.arange(n_query + 1, dtype=np.int64) * k
+    return csr_matrix((distances.ravel(), indices.ravel(), indptr), shape=(n_query, int(n_ref)))

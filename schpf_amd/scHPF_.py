@@ -300,6 +300,19 @@ class scHPF(BaseEstimator):
         pairs, and the observed ones of X unless X is None."""
         return ls.predictive_check(X, theta=self.theta, beta=self.beta, by=by, device=device)
 
+    def neighbors(self, k=15, metric="euclidean", query=None, device=None):
+        """(indices, distances) of the k nearest cells of this model in factor space, exact and on the GPU
+        (schpf_amd.neighbors.knn on `cell_score()`; an addition to the reference's surface).  query=None: the model's own
+        cells, none its own neighbour.  query a fitted or projected scHPF, or an array of cell scores: its cells against
+        this model's -- label transfer after `project()`."""
+        from .neighbors import knn
+        ref = self.cell_score()
+        if query is None:
+            return knn(ref, k=k, metric=metric, device=device)
+        if isinstance(query, scHPF):
+            query = query.cell_score()
+        return knn(query, ref, k=k, metric=metric, device=device)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
