@@ -369,6 +369,53 @@ int schpf_knn(int device, int dtype, int n_query, int n_ref, int nfactors, const
 int schpf_debug_knn(int dtype, int n_query, int n_ref, int nfactors, const void *query, const void *ref, int k,
                     int64_t self_first, int32_t *idx, double *d2);
 
+/* Weighted neighbour graphs from k-NN lists: the exact self graph of schpf_knn (self_first = 0) turned into
+ * the symmetric n x n CSR matrix a clustering or a layout reads -- UMAP's fuzzy simplicial set (scanpy's
+ * obsp["connectivities"]) or the shared-neighbour Jaccard graph (Phenograph, Seurat).  Definition, which the result equals
+ * bit for bit however the work was scheduled:
+ * Inputs.  idx[n][k] (int32) and dist[n][k] (double), row-major: row i lists k rows j with a distance each.  1 <= k <= 128,
+ *   k <= n - 1, n < 2^31 - 128.  Refused, the outputs untouched, N the smallest offending row, lists before distances:
+ *     an index outside [0, n), equal to its own row, or twice in a row:
+ *       "neighbour lists must hold k distinct rows other than the row itself; offending row N"
+ *     (SCHPF_GRAPH_UMAP) a distance that is negative or not finite: "distances must be finite and >= 0; offending row N"
+ *   Ascending distances are NOT required; cosine distances are taken as they are.
+ * SCHPF_GRAPH_UMAP: UMAP's fuzzy simplicial set with local_connectivity = 1, bandwidth = 1, set_op_mix_ratio = 1.  All
+ *   arithmetic in double, every sum serial in column order j = 0 .. k - 1:
+ *     rho_i = the smallest strictly positive dist[i][j], 0 if there is none;  target = log2(k + 1) (std::log2 on the host;
+ *       UMAP's n_neighbors counts the cell itself: k = 14 here is scanpy's n_neighbors = 15);
+ *     W(e, s):  t = e / s (IEEE division);  W = t > 708 ? 0.0 : fast_exp(-t)  (csrc/special.h; the cut keeps denormals out);
+ *     sigma_i by bisection:  lo = 0, hi = inf, mid = 1;  at most 64 rounds of
+ *         psum = sum_j (dist[i][j] - rho_i > 0 ? W(dist[i][j] - rho_i, mid) : 1.0);
+ *         if fabs(psum - target) < 1e-5: stop;
+ *         if psum > target:  hi = mid, mid = (lo + hi) / 2;
+ *         else:  lo = mid, mid = (hi == inf) ? mid * 2 : (lo + hi) / 2;
+ *       sigma_i = mid;  then, if rho_i > 0 and sigma_i < 1e-3 * mean_i (mean_i = the row's sum of distances / k):
+ *       sigma_i = 1e-3 * mean_i  (a row with rho_i = 0 has all distances 0 and all weights 1: its sigma is what the loop left);
+ *     directed weight  w_ij = (dist[i][j] - rho_i <= 0) ? 1.0 : W(dist[i][j] - rho_i, sigma_i);
+ *     union: for every unordered pair {i, j} with an edge either way, a = w_ij (0 if j is not in row i), b = w_ji likewise,
+ *       c = fma(-a, b, a + b) -- symmetric in a and b bit for bit.
+ * SCHPF_GRAPH_JACCARD: N+(i) = {i} and row i (a cell belongs to its own neighbourhood, Seurat's convention); for the same
+ *   pairs m = |N+(i) ^ N+(j)| and c = (double)m / (double)(2 * (k + 1) - m).  dist is not read and may be NULL.
+ * Output: the CSR matrix of c.  indptr[n + 1] (int64); indices (int32) and data (double), both of capacity 2 * n * k, the
+ *   bound; nnz = indptr[n].  Columns strictly ascending within a row, no diagonal, every pair in both rows with the same
+ *   bits; an edge whose c is exactly 0 is still stored (the structure depends on idx alone).  rho[n], sigma[n]: optional
+ *   outputs of SCHPF_GRAPH_UMAP, may be NULL (not written by SCHPF_GRAPH_JACCARD).
+ * n = 0 succeeds and writes nothing; bad arguments fail with a message.  Stateless; device memory that cannot be had
+ * returns SCHPF_ERR_NO_MEMORY (scratch: about 72 n k bytes for umap, 52 n k for jaccard, and the sort's own).
+ * _device: idx, dist and the outputs are DEVICE pointers on `device`; stream as in schpf_knn_device; synchronised before
+ *   the call returns.
+ * schpf_knn_graph: host pointers, staged through the device; the same result.
+ * schpf_debug_knn_graph: test hook (host only, no GPU needed): the serial restatement of the definition, which both must
+ *   match bit for bit. */
+#define SCHPF_GRAPH_UMAP 0
+#define SCHPF_GRAPH_JACCARD 1
+int schpf_knn_graph_device(int device, void *stream, int method, int n, int k, const int32_t *idx, const double *dist,
+                           int64_t *indptr, int32_t *indices, double *data, double *rho, double *sigma);
+int schpf_knn_graph(int device, int method, int n, int k, const int32_t *idx, const double *dist, int64_t *indptr,
+                    int32_t *indices, double *data, double *rho, double *sigma);
+int schpf_debug_knn_graph(int method, int n, int k, const int32_t *idx, const double *dist, int64_t *indptr,
+                          int32_t *indices, double *data, double *rho, double *sigma);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

@@ -16,6 +16,7 @@ VAL_I32, VAL_I64, VAL_F32, VAL_F64 = 0, 1, 2, 3
 IDX_I32, IDX_I64 = 0, 1   # SCHPF_IDX_*: the index types of the device uploads
 STREAM_DEFAULT = 1   # SCHPF_STREAM_DEFAULT: the device's null stream
 FREEZE_GENES, SIMULTANEOUS, SHARDED, CELLS_FIRST, LOCAL_GENE, LOCAL_CELL = 1, 2, 4, 8, 16, 32
+GRAPH_UMAP, GRAPH_JACCARD = 0, 1   # SCHPF_GRAPH_*: the method of schpf_knn_graph
 BY_CELL, BY_GENE = 0, 1   # SCHPF_BY_CELL / SCHPF_BY_GENE: the axis of schpf_loss_rows / schpf_predictive_rows
 # SCHPF_SPECIAL_*: the function schpf_debug_special evaluates
 SPECIAL_RCP, SPECIAL_LOG, SPECIAL_EXP, SPECIAL_PSI, SPECIAL_PSI_LESS_LOG = 0, 1, 2, 3, 4
@@ -85,6 +86,9 @@ SIGNATURES = {
     "schpf_knn_device": [_int, _vp, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp],
     "schpf_knn": [_int, _int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp],
     "schpf_debug_knn": [_int, _int, _int, _int, _vp, _vp, _int, _i64, _vp, _vp],
+    "schpf_knn_graph_device": [_int, _vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "schpf_knn_graph": [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "schpf_debug_knn_graph": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_plan_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int,
@@ -221,7 +225,7 @@ def check(status):
     if status != 0:
         msg = load().schpf_last_error().decode("utf-8", "replace")
         if status != ERR_NO_MEMORY and ("must be" in msg or "out of range" in msg or "unknown" in msg
-                                        or "thinning needs" in msg):
+                                        or "thinning needs" in msg or "neighbour lists must hold" in msg):
             raise ValueError(msg)
         raise SchpfHipError(msg, status)
 

@@ -129,6 +129,10 @@ def _parser():
                             "(knn_indices.txt, knn_distances.txt: one row per cell, nearest first).  Needs no count matrix.")
     score.add_argument("--knn-metric", default="euclidean", choices=["euclidean", "cosine"],
                        help="Distance of --knn between cell scores. [euclidean]")
+    score.add_argument("--knn-graph", default=None, choices=["umap", "jaccard"],
+                       help="With --knn: also write the weighted symmetric graph of the neighbour lists as "
+                            "knn_connectivities.mtx: UMAP's fuzzy simplicial set (scanpy's connectivities) or the "
+                            "shared-neighbour Jaccard graph.")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -316,8 +320,16 @@ def _score(args, outprefix):
         indices, distances = model.neighbors(k=args.knn, metric=args.knn_metric)
         np.savetxt(outprefix + "knn_indices.txt", indices, fmt="%d", delimiter="\t")
         np.savetxt(outprefix + "knn_distances.txt", distances, delimiter="\t")
+        if args.knn_graph is not None:
+            from scipy.io import mmwrite
+            from .neighbors import knn_connectivities
+            mmwrite(outprefix + "knn_connectivities.mtx", knn_connectivities(indices, distances, method=args.knn_graph))
     else:
+        if args.knn_graph is not None:
+            raise ValueError("--knn-graph needs the neighbour lists (--knn K)")
         del args.knn, args.knn_metric   # ... and of a run without the neighbours
+    if args.knn_graph is None:
+        del args.knn_graph              # ... and without their graph
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

@@ -102,6 +102,26 @@ inline const char *knn_bad_args(int dtype, int n_query, int n_ref, int nfactors,
     return nullptr;
 }
 
+// What schpf_knn_graph, schpf_knn_graph_device and schpf_debug_knn_graph refuse alike (include/schpf_hip.h); n = 0 is asked
+// next by the caller.  nullptr: the arguments are fine
+inline const char *graph_bad_args(int method, int n, int k, const void *idx, const void *dist, const void *indptr,
+                                  const void *indices, const void *data)
+{
+    if (method != SCHPF_GRAPH_UMAP && method != SCHPF_GRAPH_JACCARD) return "method must be SCHPF_GRAPH_UMAP or SCHPF_GRAPH_JACCARD";
+    if (k < 1 || k > 128) return "k must be in [1, 128]";
+    if (n < 0 || n > INT32_MAX - 128) return "n must be in [0, 2^31 - 128)";
+    if (n == 0) return nullptr;
+    if (k > n - 1) return "k must be at most n - 1: the rows other than the row itself";
+    if (!idx || !indptr || !indices || !data) return "idx, indptr, indices and data must not be NULL";
+    if (method == SCHPF_GRAPH_UMAP && !dist) return "dist must not be NULL for SCHPF_GRAPH_UMAP";
+    return nullptr;
+}
+inline std::string graph_bad_lists(int64_t row)
+{
+    return "neighbour lists must hold k distinct rows other than the row itself; offending row " + std::to_string(row);
+}
+inline std::string graph_bad_distances(int64_t row) { return "distances must be finite and >= 0; offending row " + std::to_string(row); }
+
 // RAII device buffer
 struct DevBuf {
     void *p = nullptr;

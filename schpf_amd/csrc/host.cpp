@@ -1,6 +1,6 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
-// check the host builders with, the serial restatements of count thinning (thin.hip) and of the nearest-neighbour search
-// (knn.hip) and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
+// check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
+// (knn.hip) and of the neighbour graphs (knn_graph.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -13,6 +13,7 @@
 #include "common.h"
 #include "philox.h"
 #include "policy.h"
+#include "special.h"
 
 using namespace schpf;
 
@@ -333,6 +334,118 @@ int schpf_debug_knn(int dtype, int n_query, int n_ref, int nfactors, const void 
                 }
             });
         for (auto &x : th) x.join();
+    });
+}
+
+// knn_graph.hip restated: the definition of include/schpf_hip.h line by line, one row after the other, then
+// one std::sort of the 2 n k (row, col, direction) records
+int schpf_debug_knn_graph(int method, int n, int k, const int32_t *idx, const double *dist, int64_t *indptr,
+                          int32_t *indices, double *data, double *rho, double *sigma)
+{
+    if (const char *why = graph_bad_args(method, n, k, idx, dist, indptr, indices, data)) return fail("%s", why);
+    if (n == 0) return 0;
+    return guarded([&] {
+        const bool umap = method == SCHPF_GRAPH_UMAP;
+        const size_t K = (size_t)k;
+        std::vector<int32_t> sorted((size_t)n * K);
+        for (int i = 0; i < n; ++i) {
+            int32_t *s = sorted.data() + (size_t)i * K;
+            std::copy(idx + (size_t)i * K, idx + (size_t)i * K + K, s);
+            std::sort(s, s + K);
+            bool wrong = s[0] < 0 || s[K - 1] >= n;
+            for (size_t j = 0; j < K; ++j) wrong |= s[j] == i || (j > 0 && s[j] == s[j - 1]);
+            if (wrong) throw std::invalid_argument(graph_bad_lists(i));
+        }
+        std::vector<double> w, rho_v, sigma_v;
+        if (umap) {
+            for (int i = 0; i < n; ++i)
+                for (size_t j = 0; j < K; ++j)
+                    if (!(dist[(size_t)i * K + j] >= 0.0 && std::isfinite(dist[(size_t)i * K + j])))
+                        throw std::invalid_argument(graph_bad_distances(i));
+            w.resize((size_t)n * K);
+            rho_v.resize((size_t)n);
+            sigma_v.resize((size_t)n);
+            const double target = std::log2((double)(k + 1));
+            auto W = [](double e, double s) {
+                const double t = e / s;
+                return t > 708.0 ? 0.0 : schpf::fast_exp(-t);
+            };
+            for (int i = 0; i < n; ++i) {
+                const double *d = dist + (size_t)i * K;
+                double r = HUGE_VAL, sum = 0.0;
+                for (size_t j = 0; j < K; ++j) {
+                    if (d[j] > 0.0 && d[j] < r) r = d[j];
+                    sum += d[j];
+                }
+                if (r == HUGE_VAL) r = 0.0;
+                double lo = 0.0, hi = HUGE_VAL, mid = 1.0;
+                for (int round = 0; round < 64; ++round) {
+                    double psum = 0.0;
+                    for (size_t j = 0; j < K; ++j) {
+                        const double e = d[j] - r;
+                        psum += e > 0.0 ? W(e, mid) : 1.0;
+                    }
+                    if (std::fabs(psum - target) < 1e-5) break;
+                    if (psum > target) {
+                        hi = mid;
+                        mid = (lo + hi) / 2.0;
+                    } else {
+                        lo = mid;
+                        mid = hi == HUGE_VAL ? mid * 2.0 : (lo + hi) / 2.0;
+                    }
+                }
+                double s = mid;
+                if (r > 0.0) {
+                    const double mean = sum / (double)k;
+                    const double least = 1e-3 * mean;
+                    if (s < least) s = least;
+                }
+                for (size_t j = 0; j < K; ++j) {
+                    const double e = d[j] - r;
+                    w[(size_t)i * K + j] = e <= 0.0 ? 1.0 : W(e, s);
+                }
+                rho_v[(size_t)i] = r;
+                sigma_v[(size_t)i] = s;
+            }
+        }
+        struct Rec { uint64_t key; double w; };
+        std::vector<Rec> rec(2 * (size_t)n * K);
+        for (size_t e = 0; e < (size_t)n * K; ++e) {
+            const uint64_t i = e / K, j = (uint64_t)idx[e];
+            const double v = umap ? w[e] : 0.0;
+            rec[2 * e] = Rec{(i * (uint64_t)n + j) << 1, v};
+            rec[2 * e + 1] = Rec{((j * (uint64_t)n + i) << 1) | 1, v};
+        }
+        std::sort(rec.begin(), rec.end(), [](const Rec &a, const Rec &b) { return a.key < b.key; });   // all keys differ
+        int64_t nnz = 0;
+        int64_t row_done = -1;
+        for (size_t p = 0; p < rec.size();) {
+            const uint64_t cell = rec[p].key >> 1;
+            const bool both = p + 1 < rec.size() && (rec[p + 1].key >> 1) == cell;
+            const bool out = !(rec[p].key & 1), in = (rec[p].key & 1) || both;
+            const int64_t row = (int64_t)(cell / (uint64_t)n), col = (int64_t)(cell % (uint64_t)n);
+            while (row_done < row) indptr[++row_done] = nnz;
+            indices[nnz] = (int32_t)col;
+            if (umap) {
+                const double a = out ? rec[p].w : 0.0;
+                const double b = !out ? rec[p].w : both ? rec[p + 1].w : 0.0;
+                data[nnz] = std::fma(-a, b, a + b);
+            } else {
+                const int32_t *x = sorted.data() + (size_t)row * K, *y = sorted.data() + (size_t)col * K;
+                int m = (out ? 1 : 0) + (in ? 1 : 0);
+                for (size_t ix = 0, iy = 0; ix < K && iy < K;) {
+                    if (x[ix] == y[iy]) { ++m; ++ix; ++iy; }
+                    else if (x[ix] < y[iy]) ++ix;
+                    else ++iy;
+                }
+                data[nnz] = (double)m / (double)(2 * (k + 1) - m);
+            }
+            ++nnz;
+            p += both ? 2 : 1;
+        }
+        indptr[n] = nnz;
+        if (umap && rho) std::copy(rho_v.begin(), rho_v.end(), rho);
+        if (umap && sigma) std::copy(sigma_v.begin(), sigma_v.end(), sigma);
     });
 }
 

@@ -240,6 +240,22 @@ hipError_t launch_knn_select(const double *qtab, const double *rtab, int n_query
                              hipStream_t st);
 hipError_t launch_knn_merge(const int32_t *part_idx, const double *part_d2, const int *part_cnt, int n_query, int n_seg,
                             int k, int32_t *idx, double *d2, hipStream_t st);
+// Weighted neighbour graphs from k-NN lists (knn_graph.hip).  launch_graph_rows: one thread per row, 64 rows
+// per workgroup: bad_idx / bad_dist[graph_row_blocks(n)] take per workgroup the smallest row whose list (an index out of
+// range, the row itself, an index twice) or whose distances (negative, not finite) are refused, INT_MAX: none -- reduced by
+// launch_knn_bad; dist != nullptr (umap): rho[n], sigma[n] and the directed weights w[n * k]; sorted != nullptr: the rows'
+// indices ascending.  launch_graph_keys: the 2 n k records of the directed edges, key = ((row * n + col) << 1) | direction,
+// val (may be nullptr) the edge's weight.  launch_graph_heads: head[p] = 1 where the SORTED key p starts a new (row, col).
+// launch_graph_fill: pos = the exclusive scan of head; writes indptr[n + 1], indices and data; val (the sorted weights:
+// umap) or sorted (the ascending lists: jaccard), exactly one of them
+inline int64_t graph_row_blocks(int n) { return ((int64_t)n + 63) / 64; }
+inline size_t graph_row_lds_bytes(int k) { return (size_t)64 * (size_t)k * sizeof(double); }
+hipError_t launch_graph_rows(const int32_t *idx, const double *dist, int n, int k, double target, double *w, double *rho,
+                             double *sigma, int32_t *sorted, int *bad_idx, int *bad_dist, hipStream_t st);
+hipError_t launch_graph_keys(const int32_t *idx, const double *w, int n, int k, uint64_t *key, double *val, hipStream_t st);
+hipError_t launch_graph_heads(const uint64_t *key, int64_t n_keys, int64_t *head, hipStream_t st);
+hipError_t launch_graph_fill(const uint64_t *key, const double *val, const int64_t *pos, const int32_t *sorted, int64_t n_keys,
+                             int n, int k, int64_t *indptr, int32_t *indices, double *data, hipStream_t st);
 hipError_t launch_digamma_array(const double *x, int64_t n, double *out, hipStream_t st);
 hipError_t launch_gammaln_array(const double *x, int64_t n, double *out, hipStream_t st);
 

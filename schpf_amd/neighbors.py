@@ -13,9 +13,10 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["knn", "knn_graph"]
+__all__ = ["knn", "knn_graph", "knn_connectivities"]
 
 METRICS = ("euclidean", "cosine")
+GRAPH_METHODS = {"umap": _lib.GRAPH_UMAP, "jaccard": _lib.GRAPH_JACCARD}
 _DTYPES = {np.dtype(np.float32): _lib.F32, np.dtype(np.float64): _lib.F64}
 
 
@@ -148,3 +149,88 @@ def knn_graph(indices, distances, n_ref):
         raise ValueError("indices must be in [0, n_ref)")
     indptr = np.arange(n_query + 1, dtype=np.int64) * k
     return csr_matrix((distances.ravel(), indices.ravel(), indptr), shape=(n_query, int(n_ref)))
+
+
+def _graph_host(method, idx, dist, device):
+    """schpf_knn_graph on C-contiguous NumPy lists (dist None: jaccard) -> (indptr, indices, data) of the CSR matrix, cut
+    to nnz."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    n, k = idx.shape
+    indptr = np.zeros(n + 1, np.int64)
+    indices = np.empty(2 * n * k, np.int32)
+    data = np.empty(2 * n * k, np.float64)
+    _lib.check(lib.schpf_knn_graph(int(device), method, n, k, _p(idx), _p(dist) if dist is not None else None, _p(indptr),
+                                   _p(indices), _p(data), None, None))
+    nnz = int(indptr[n])
+    return indptr, indices[:nnz], data[:nnz]
+
+
+def knn_connectivities(indices, distances=None, method="umap", device=None):
+    """The weighted, symmetric neighbour graph of the k-NN lists `knn(x, k=k)` returned (the self graph, no cell its own
+    neighbour): n x n CSR, every pair stored in both rows with the same bits, no diagonal.
+
+    method="umap": UMAP's fuzzy simplicial set (local_connectivity 1, set_op_mix_ratio 1) -- scanpy's
+    obsp["connectivities"], the input of sc.tl.umap / leiden / louvain.  UMAP's n_neighbors counts the cell itself:
+    knn(k=14) and this is scanpy's n_neighbors=15.  Needs the distances.
+    method="jaccard": the shared-neighbour graph of Phenograph / Seurat, |N(i) & N(j)| / |N(i) | N(j)| with a cell in its
+    own neighbourhood; the distances are not read.
+
+    NumPy in gives a SciPy CSR matrix out (umap: without explicit zeros).  Two torch tensors on a GPU give a
+    torch.sparse_csr_tensor on that GPU, computed on torch's current stream; nothing but two integers crosses to the
+    host.  Lists that name a row outside [0, n), the row itself or a row twice, and distances that are negative or not
+    finite, raise ValueError naming the smallest offending row."""
+    if method not in GRAPH_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(GRAPH_METHODS), method))
+    if method == "umap" and distances is None:
+        raise ValueError("method='umap' needs the distances of the neighbour lists")
+    code = GRAPH_METHODS[method]
+    if _is_tensor(indices) and indices.is_cuda:
+        import torch
+        lib = _lib.load()
+        _lib.require_gpu()
+        dev = indices.device
+        if device is not None and int(device) != dev.index:
+            raise ValueError("indices are on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+        if method == "umap" and (not _is_tensor(distances) or distances.device != dev):
+            raise ValueError("indices and distances must be on the same GPU")
+        if indices.dim() != 2 or (method == "umap" and distances.shape != indices.shape):
+            raise ValueError("indices and distances must be matrices of one shape")
+        n, k = indices.shape
+        with torch.cuda.device(dev):
+            idx = indices.detach().to(torch.int32).contiguous()
+            dist = distances.detach().to(torch.float64).contiguous() if method == "umap" else None
+            indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            cols = torch.empty(2 * n * k, dtype=torch.int32, device=dev)
+            data = torch.empty(2 * n * k, dtype=torch.float64, device=dev)
+            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+            _lib.check(lib.schpf_knn_graph_device(dev.index, ctypes.c_void_p(stream), code, n, k, ptr(idx), ptr(dist),
+                                                  ptr(indptr), ptr(cols), ptr(data), None, None))
+            nnz = int(indptr[n]) if n else 0
+            # one index type for both, as torch's kernels expect: int32 where it holds nnz
+            indptr, cols = (indptr.to(torch.int32), cols[:nnz]) if nnz < 2 ** 31 else (indptr, cols[:nnz].to(torch.int64))
+            import warnings
+            with warnings.catch_warnings():          # torch announces that its CSR tensors are in beta, once per process
+                warnings.filterwarnings("ignore", message="Sparse CSR tensor support is in beta")
+                return torch.sparse_csr_tensor(indptr, cols, data[:nnz], size=(n, n))
+
+    from scipy.sparse import csr_matrix
+    if _is_tensor(indices):
+        indices = indices.cpu().numpy()
+    if distances is not None and _is_tensor(distances):
+        distances = distances.cpu().numpy()
+    idx = np.ascontiguousarray(indices, dtype=np.int32)
+    dist = np.ascontiguousarray(distances, dtype=np.float64) if method == "umap" else None
+    if idx.ndim != 2 or (dist is not None and dist.shape != idx.shape):
+        raise ValueError("indices and distances must be matrices of one shape")
+    n = idx.shape[0]
+    indptr, cols, data = _graph_host(code, idx, dist, device)
+    if len(cols) < 2 ** 31:
+        indptr = indptr.astype(np.int32)
+    G = csr_matrix((data, cols, indptr), shape=(n, n))
+    if method == "umap":
+        G.eliminate_zeros()
+    return G

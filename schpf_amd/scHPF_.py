@@ -313,6 +313,16 @@ class scHPF(BaseEstimator):
             query = query.cell_score()
         return knn(query, ref, k=k, metric=metric, device=device)
 
+    def neighbor_graph(self, k=15, metric="euclidean", method="umap", device=None):
+        """(distances, connectivities) of this model's cells in factor space: two SciPy CSR matrices n x n, scanpy's two
+        obsp entries -- the k-NN distances (`neighbors` + schpf_amd.knn_graph) and the weighted symmetric graph made of
+        them on the GPU (schpf_amd.knn_connectivities; method "umap" or "jaccard").  An addition to the reference's
+        surface."""
+        from .neighbors import knn_connectivities, knn_graph
+        indices, distances = self.neighbors(k=k, metric=metric, device=device)
+        return (knn_graph(indices, distances, indices.shape[0]),
+                knn_connectivities(indices, distances, method=method, device=device))
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
