@@ -458,6 +458,13 @@ int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *mi
                             int32_t *out_minor, float *out_val, int32_t *out_prow, int32_t *out_task,
                             int32_t *out_pfirst, int32_t *out_pcount, int64_t stats[8]);
 
+/* Test hook (host only, no GPU needed, no environment read): the sweep shape an engine of `dtype` with `nfactors`
+ * factors runs on -- the library's own choice (policy.cpp choose_config) under plan = 0 (the library picks the plan),
+ * 1 (the tile plan forced, SCHPF_PLAN=tile) or 2 (the gather plan forced).  out = {1 tile / 0 gather, LPC (lanes per
+ * row), NV (16-byte vectors per lane), KL (values per lane), KP (padded row length)}.  Fails with the library's
+ * message where nfactors is outside [1, 256] or no instantiated shape fits. */
+int schpf_debug_choose_config(int dtype, int nfactors, int plan, int out[5]);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus

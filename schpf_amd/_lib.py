@@ -91,6 +91,7 @@ SIGNATURES = {
     "schpf_debug_knn_graph": [_int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
+    "schpf_debug_choose_config": [_int, _int, _int, ctypes.POINTER(_int)],
     "schpf_debug_plan_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _i64p],
     "schpf_debug_tile_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int,

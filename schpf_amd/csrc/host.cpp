@@ -239,6 +239,21 @@ int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *mi
     });
 }
 
+// the shape the engine would sweep `nfactors` factors with: choose_config itself, asked with a Tuning that sets the
+// plan and nothing else (no environment is read)
+int schpf_debug_choose_config(int dtype, int nfactors, int plan, int out[5])
+{
+    if (!out) return fail("out is NULL");
+    if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
+    if (plan < 0 || plan > 2) return fail("plan must be 0 (auto), 1 (tile) or 2 (gather)");
+    return guarded([&] {
+        schpf::Tuning tn;
+        tn.plan = plan == 1 ? schpf::Tuning::PLAN_TILE : plan == 2 ? schpf::Tuning::PLAN_GATHER : schpf::Tuning::PLAN_AUTO;
+        const schpf::Config c = schpf::choose_config(nfactors, dtype == SCHPF_F32 ? 4 : 8, tn);
+        out[0] = c.tile ? 1 : 0; out[1] = c.LPC; out[2] = c.NV; out[3] = c.KL; out[4] = c.KP;
+    });
+}
+
 int schpf_debug_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4])
 {
     if (!counter || !key || !out) return fail("counter, key and out must not be NULL");
