@@ -416,6 +416,54 @@ int schpf_knn_graph(int device, int method, int n, int k, const int32_t *idx, co
 int schpf_debug_knn_graph(int method, int n, int k, const int32_t *idx, const double *dist, int64_t *indptr,
                           int32_t *indices, double *data, double *rho, double *sigma);
 
+/* Louvain clustering of a weighted neighbour graph: the labels a clustering of the cells reads off the
+ * matrix schpf_knn_graph made.  The weights are quantised once to int64, so every sum below is an integer sum, exact in any
+ * order; doubles appear in one score per candidate, a fixed expression of exact integers; moves are synchronous.  The result
+ * is one well-defined labelling, equal bit for bit however the work was scheduled:
+ * Input.  A CSR matrix n x n: indptr[n + 1] (int64), indices (int32), data (double), nnz = indptr[n] < 2^32; columns strictly
+ *   ascending within a row, entries finite and >= 0, a diagonal allowed; symmetric in structure and in bits -- what
+ *   schpf_knn_graph returns.  SYMMETRY IS THE CALLER'S CONTRACT AND IS NOT CHECKED: an asymmetric matrix is clustered as
+ *   it stands, every row by its own entries.  gamma: the resolution, finite and > 0.  n < 2^31 - 128.
+ *   Refused, the outputs untouched, N the smallest offending row, structure before values, indptr before columns:
+ *     "indptr must be 0 at row 0 and must be non-decreasing; offending row N"  (indptr[0] != 0: row 0; indptr[N + 1] <
+ *       indptr[N]: row N)
+ *     "columns must be in [0, n) and strictly ascending within a row; offending row N"
+ *     "values must be finite and >= 0; offending row N"
+ * Quantisation.  wmax = the largest entry;  q_e = llrint(ldexp(data_e / wmax, 30)) with IEEE division, round to nearest
+ *   even.  wmax == 0, n == 0 or nnz == 0: every vertex is its own community, labels[i] = i, 0 levels, 0 rounds, W2 = 0.
+ *   nnz < 2^32 keeps every sum below 2^62.
+ * A level has n_l vertices and an int64-weighted CSR; level 0 is the quantised input.  k_i = the sum of row i, diagonal
+ *   included;  W2 = the sum of all k_i;  communities start as c[i] = i;  tot[d] = the sum of k_i over the members of d.
+ *   Rounds r = 0, 1, .., at most 32 per level; a round reads c and tot as they stood at its start.  For vertex i, a = c[i],
+ *   and every community d among c[j] of the row's entries with j != i (an entry with q = 0 counts):
+ *       K(d) = the integer sum of those entries' q;  K(a) = 0 if no neighbour is in a;
+ *       base(d) = tot[d] - (d == a ? k_i : 0);
+ *       p = (double)k_i * (double)base(d);  t = p / (double)W2;  score(d) = fma(-gamma, t, (double)K(d))
+ *   -- one multiply, one IEEE division, one fused multiply-add, nothing else contracted.  Vertex i is eligible in round r
+ *   when (((uint64)i * 2654435761) >> 16 & 1) == (r & 1) and k_i > 0.  An eligible vertex takes the candidate d != a that
+ *   is best by the key (score descending, then d ascending) and moves there iff score(d) > score(a), strictly.  All moves
+ *   of a round are applied together.  The level ends after a round without a move, or after round 31.
+ * Aggregation.  The communities that still have members are renumbered 0 .. n' - 1 in ascending id; entry (c', d') of the
+ *   next level is the integer sum of all entries (i, j) with c[i] -> c' and c[j] -> d' (the diagonal is kept: the row sums
+ *   are the old tot); labels is composed through the renumbering.  The algorithm stops when a level made no move, and
+ *   after 32 levels.
+ * Output.  labels[n] (int32) in [0, C);  stats[4] (int64): C, the levels that moved something, the rounds run in all
+ *   (the round without a move that ends a level included), W2 of level 0.
+ * n = 0 succeeds, writes stats = 0 and does not read the other pointers; bad arguments fail with a message.  Stateless;
+ * device memory that cannot be had returns SCHPF_ERR_NO_MEMORY (scratch: about 60 nnz + 60 n bytes, the sorts' own -- about
+ * 16 nnz -- and the aggregated levels, at most 40 nnz).
+ * _device: indptr, indices, data and labels are DEVICE pointers on `device`, stats is a HOST pointer; stream as in
+ *   schpf_knn_device; synchronised before the call returns.
+ * schpf_louvain: host pointers, staged through the device; the same result.
+ * schpf_debug_louvain: test hook (host only, no GPU needed): the serial restatement of the definition with std::fma, which
+ *   both must match bit for bit. */
+int schpf_louvain_device(int device, void *stream, int n, const int64_t *indptr, const int32_t *indices, const double *data,
+                         double gamma, int32_t *labels, int64_t stats[4]);
+int schpf_louvain(int device, int n, const int64_t *indptr, const int32_t *indices, const double *data, double gamma,
+                  int32_t *labels, int64_t stats[4]);
+int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, const double *data, double gamma,
+                        int32_t *labels, int64_t stats[4]);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

@@ -133,6 +133,11 @@ def _parser():
                        help="With --knn: also write the weighted symmetric graph of the neighbour lists as "
                             "knn_connectivities.mtx: UMAP's fuzzy simplicial set (scanpy's connectivities) or the "
                             "shared-neighbour Jaccard graph.")
+    score.add_argument("--clusters", default=False, action="store_true",
+                       help="With --knn-graph: also write the Louvain clusters of that graph as clusters.txt, one label "
+                            "per cell.")
+    score.add_argument("--resolution", type=float, default=None, metavar="R",
+                       help="Resolution of --clusters: larger values give more, smaller clusters. [1.0]")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -322,14 +327,25 @@ def _score(args, outprefix):
         np.savetxt(outprefix + "knn_distances.txt", distances, delimiter="\t")
         if args.knn_graph is not None:
             from scipy.io import mmwrite
-            from .neighbors import knn_connectivities
-            mmwrite(outprefix + "knn_connectivities.mtx", knn_connectivities(indices, distances, method=args.knn_graph))
+            from .neighbors import knn_connectivities, louvain
+            graph = knn_connectivities(indices, distances, method=args.knn_graph)
+            mmwrite(outprefix + "knn_connectivities.mtx", graph)
+            if args.clusters:
+                print("Saving clusters.....")
+                args.resolution = 1.0 if args.resolution is None else args.resolution
+                np.savetxt(outprefix + "clusters.txt", louvain(graph, resolution=args.resolution), fmt="%d")
     else:
         if args.knn_graph is not None:
             raise ValueError("--knn-graph needs the neighbour lists (--knn K)")
         del args.knn, args.knn_metric   # ... and of a run without the neighbours
     if args.knn_graph is None:
+        if args.clusters:
+            raise ValueError("--clusters needs the neighbour graph (--knn K --knn-graph M)")
         del args.knn_graph              # ... and without their graph
+    if not args.clusters:
+        if args.resolution is not None:
+            raise ValueError("--resolution belongs to --clusters")
+        del args.clusters, args.resolution   # ... and without its clusters
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

@@ -122,6 +122,34 @@ inline std::string graph_bad_lists(int64_t row)
 }
 inline std::string graph_bad_distances(int64_t row) { return "distances must be finite and >= 0; offending row " + std::to_string(row); }
 
+// What schpf_louvain, schpf_louvain_device and schpf_debug_louvain refuse alike (include/schpf_hip.h); n = 0 is asked next
+// by the caller.  nullptr: the arguments are fine
+inline const char *louvain_bad_args(int n, const void *indptr, double gamma, const void *labels, const void *stats)
+{
+    if (n < 0 || n > INT32_MAX - 128) return "n must be in [0, 2^31 - 128)";
+    if (!(gamma > 0.0 && gamma <= 1.7976931348623157e308)) return "gamma must be finite and > 0";
+    if (!stats) return "stats must not be NULL";
+    if (n == 0) return nullptr;
+    if (!indptr || !labels) return "indptr and labels must not be NULL";
+    return nullptr;
+}
+inline const char *louvain_bad_nnz(int64_t nnz, const void *indices, const void *data)
+{
+    if (nnz >= (int64_t)1 << 32) return "nnz must be below 2^32";
+    if (nnz > 0 && (!indices || !data)) return "indices and data must not be NULL";
+    return nullptr;
+}
+inline std::string louvain_bad_indptr(int64_t row)
+{
+    return "indptr must be 0 at row 0 and must be non-decreasing; offending row " + std::to_string(row);
+}
+inline std::string louvain_bad_columns(int64_t row)
+{
+    return "columns must be in [0, n) and strictly ascending within a row; offending row " + std::to_string(row);
+}
+inline std::string louvain_bad_values(int64_t row) { return "values must be finite and >= 0; offending row " + std::to_string(row); }
+constexpr int LOUVAIN_ROUNDS = 32, LOUVAIN_LEVELS = 32;   // the caps of the definition
+
 // RAII device buffer
 struct DevBuf {
     void *p = nullptr;

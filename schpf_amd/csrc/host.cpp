@@ -1,6 +1,7 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
 // check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
-// (knn.hip) and of the neighbour graphs (knn_graph.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
+// (knn.hip), of the neighbour graphs (knn_graph.hip) and of the Louvain clustering (louvain.hip), and the SCHPF_BACKTRACE
+// crash handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -461,6 +462,144 @@ int schpf_debug_knn_graph(int method, int n, int k, const int32_t *idx, const do
         indptr[n] = nnz;
         if (umap && rho) std::copy(rho_v.begin(), rho_v.end(), rho);
         if (umap && sigma) std::copy(sigma_v.begin(), sigma_v.end(), sigma);
+    });
+}
+
+// louvain.hip restated: the definition of include/schpf_hip.h line by line -- one vertex after the other
+// within a round, every vertex reading the communities as the round found them, and one std::sort per aggregation
+int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, const double *data, double gamma,
+                        int32_t *labels, int64_t stats[4])
+{
+    if (const char *why = louvain_bad_args(n, indptr, gamma, labels, stats)) return fail("%s", why);
+    return guarded([&] {
+        if (n == 0) {
+            std::fill(stats, stats + 4, (int64_t)0);
+            return;
+        }
+        if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
+        for (int i = 0; i < n; ++i)
+            if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
+        const int64_t nnz = indptr[n];
+        if (const char *why = louvain_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= n || (e > indptr[i] && indices[e - 1] >= indices[e]))
+                    throw std::invalid_argument(louvain_bad_columns(i));
+        double wmax = 0.0;
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                if (!(data[e] >= 0.0 && std::isfinite(data[e]))) throw std::invalid_argument(louvain_bad_values(i));
+                wmax = data[e] > wmax ? data[e] : wmax;
+            }
+        std::vector<int32_t> lab((size_t)n);
+        for (int i = 0; i < n; ++i) lab[(size_t)i] = i;
+        int64_t n_comm = n, levels = 0, rounds = 0, w2_first = 0;
+        if (nnz > 0 && wmax > 0.0) {
+            // the level's graph
+            int64_t nl = n;
+            std::vector<int64_t> ip(indptr, indptr + n + 1), q((size_t)nnz);
+            std::vector<int32_t> ix(indices, indices + nnz);
+            for (int64_t e = 0; e < nnz; ++e) q[(size_t)e] = std::llrint(std::ldexp(data[e] / wmax, 30));
+            auto score = [gamma](int64_t k, int64_t base, int64_t w2, int64_t among) {
+                const double p = (double)k * (double)base;
+                const double t = p / (double)w2;
+                return std::fma(-gamma, t, (double)among);
+            };
+            for (int level = 0; level < LOUVAIN_LEVELS; ++level) {
+                std::vector<int64_t> k((size_t)nl, 0);
+                int64_t w2 = 0;
+                for (int64_t i = 0; i < nl; ++i) {
+                    for (int64_t e = ip[(size_t)i]; e < ip[(size_t)i + 1]; ++e) k[(size_t)i] += q[(size_t)e];
+                    w2 += k[(size_t)i];
+                }
+                if (level == 0) w2_first = w2;
+                std::vector<int32_t> c((size_t)nl), next;
+                for (int64_t i = 0; i < nl; ++i) c[(size_t)i] = (int32_t)i;
+                std::vector<int64_t> tot(k);
+                bool level_moved = false;
+                std::vector<std::pair<int32_t, int64_t>> seen;   // (community, weight) of a row's entries
+                for (int r = 0; r < LOUVAIN_ROUNDS; ++r) {
+                    ++rounds;
+                    next = c;
+                    int64_t moves = 0;
+                    for (int64_t i = 0; i < nl; ++i) {
+                        const int64_t ki = k[(size_t)i];
+                        if (((((uint64_t)i * 2654435761ull) >> 16) & 1) != (uint64_t)(r & 1) || ki <= 0) continue;
+                        const int32_t a = c[(size_t)i];
+                        seen.clear();
+                        for (int64_t e = ip[(size_t)i]; e < ip[(size_t)i + 1]; ++e)
+                            if (ix[(size_t)e] != i) seen.emplace_back(c[(size_t)ix[(size_t)e]], q[(size_t)e]);
+                        std::sort(seen.begin(), seen.end());
+                        int64_t among_own = 0;
+                        bool have = false;
+                        double best = 0.0;
+                        int32_t best_d = 0;
+                        for (size_t x = 0; x < seen.size();) {
+                            const int32_t d = seen[x].first;
+                            int64_t among = 0;
+                            for (; x < seen.size() && seen[x].first == d; ++x) among += seen[x].second;
+                            if (d == a) {
+                                among_own = among;
+                                continue;
+                            }
+                            const double s = score(ki, tot[(size_t)d], w2, among);
+                            if (!have || s > best) {   // d ascends: an equal score keeps the smaller id
+                                have = true;
+                                best = s;
+                                best_d = d;
+                            }
+                        }
+                        if (have && best > score(ki, tot[(size_t)a] - ki, w2, among_own)) {
+                            next[(size_t)i] = best_d;
+                            ++moves;
+                        }
+                    }
+                    if (moves == 0) break;
+                    level_moved = true;
+                    c.swap(next);
+                    std::fill(tot.begin(), tot.end(), (int64_t)0);
+                    for (int64_t i = 0; i < nl; ++i) tot[(size_t)c[(size_t)i]] += k[(size_t)i];
+                }
+                if (!level_moved) break;
+                ++levels;
+                // the communities that still have members, renumbered in ascending id
+                std::vector<int32_t> renum((size_t)nl, 0);
+                for (int64_t i = 0; i < nl; ++i) renum[(size_t)c[(size_t)i]] = 1;
+                int32_t n_next = 0;
+                for (int64_t d = 0; d < nl; ++d) {
+                    const int32_t present = renum[(size_t)d];
+                    renum[(size_t)d] = n_next;
+                    n_next += present;
+                }
+                struct Rec { uint64_t key; int64_t q; };
+                std::vector<Rec> rec(q.size());
+                for (int64_t i = 0; i < nl; ++i)
+                    for (int64_t e = ip[(size_t)i]; e < ip[(size_t)i + 1]; ++e)
+                        rec[(size_t)e] = Rec{(uint64_t)renum[(size_t)c[(size_t)i]] * (uint64_t)n_next +
+                                                 (uint64_t)renum[(size_t)c[(size_t)ix[(size_t)e]]], q[(size_t)e]};
+                std::sort(rec.begin(), rec.end(), [](const Rec &x, const Rec &y) { return x.key < y.key; });
+                ip.assign((size_t)n_next + 1, 0);
+                ix.clear();
+                q.clear();
+                for (size_t p = 0; p < rec.size();) {
+                    const uint64_t key = rec[p].key;
+                    int64_t sum = 0;
+                    for (; p < rec.size() && rec[p].key == key; ++p) sum += rec[p].q;
+                    ix.push_back((int32_t)(key % (uint64_t)n_next));
+                    q.push_back(sum);
+                    ++ip[(size_t)(key / (uint64_t)n_next) + 1];
+                }
+                for (int32_t d = 0; d < n_next; ++d) ip[(size_t)d + 1] += ip[(size_t)d];
+                for (int i = 0; i < n; ++i) lab[(size_t)i] = renum[(size_t)c[(size_t)lab[(size_t)i]]];
+                nl = n_next;
+                n_comm = n_next;
+            }
+        }
+        std::copy(lab.begin(), lab.end(), labels);
+        stats[0] = n_comm;
+        stats[1] = levels;
+        stats[2] = rounds;
+        stats[3] = w2_first;
     });
 }
 

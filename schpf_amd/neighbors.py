@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["knn", "knn_graph", "knn_connectivities"]
+__all__ = ["knn", "knn_graph", "knn_connectivities", "louvain", "modularity"]
 
 METRICS = ("euclidean", "cosine")
 GRAPH_METHODS = {"umap": _lib.GRAPH_UMAP, "jaccard": _lib.GRAPH_JACCARD}
@@ -234,3 +234,109 @@ def knn_connectivities(indices, distances=None, method="umap", device=None):
     if method == "umap":
         G.eliminate_zeros()
     return G
+
+
+def _louvain_host(indptr, indices, data, gamma, device):
+    """schpf_louvain on the three C-contiguous arrays of a CSR matrix (int64, int32, float64) -> (labels, stats)."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    n = len(indptr) - 1
+    labels = np.empty(n, np.int32)
+    stats = np.zeros(4, np.int64)
+    _lib.check(lib.schpf_louvain(int(device), n, _p(indptr), _p(indices), _p(data), float(gamma), _p(labels),
+                                 stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+    return labels, stats
+
+
+def _resolution(resolution):
+    gamma = float(resolution)
+    if not (gamma > 0 and np.isfinite(gamma)):
+        raise ValueError("resolution must be finite and > 0, got %r" % (resolution,))
+    return gamma
+
+
+def louvain(graph, resolution=1.0, device=None, return_stats=False):
+    """Louvain clusters of a weighted symmetric graph -- `knn_connectivities(...)`, or any n x n CSR matrix with finite
+    entries >= 0 that equals its transpose -- as int32 labels 0 .. C - 1, one per row.
+
+    The weights are quantised once to integers (30 bits below the largest), every sum of the algorithm is then an integer
+    sum, and the moves of a round are applied together: the same graph gives the same labels bit for bit, on any GPU and
+    however the work was scheduled.  `resolution` multiplies the null model's term: larger values give more, smaller
+    clusters.  Symmetry is the caller's contract and is not checked.
+
+    A SciPy sparse matrix in gives a NumPy array out.  A torch.sparse_csr_tensor on a GPU gives a tensor on that GPU,
+    computed on torch's current stream; nothing but four integers crosses to the host.  return_stats=True: also
+    {"communities", "levels", "rounds", "total_weight"} (the levels that moved a vertex, the rounds of all levels, the sum
+    of the quantised weights).  A matrix the library refuses -- columns out of range, negative or non-finite values --
+    raises ValueError naming the smallest offending row."""
+    gamma = _resolution(resolution)
+    names = ("communities", "levels", "rounds", "total_weight")
+    if _is_tensor(graph) and graph.is_cuda:
+        import torch
+        if graph.layout != torch.sparse_csr:
+            raise ValueError("a graph on the GPU must be a torch.sparse_csr_tensor")
+        if graph.dim() != 2 or graph.shape[0] != graph.shape[1]:
+            raise ValueError("graph must be a square matrix")
+        lib = _lib.load()
+        _lib.require_gpu()
+        dev = graph.device
+        if device is not None and int(device) != dev.index:
+            raise ValueError("graph is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+        n = graph.shape[0]
+        with torch.cuda.device(dev):
+            indptr = graph.crow_indices().detach().to(torch.int64).contiguous()
+            cols = graph.col_indices().detach().to(torch.int32).contiguous()
+            data = graph.values().detach().to(torch.float64).contiguous()
+            labels = torch.empty(n, dtype=torch.int32, device=dev)
+            stats = np.zeros(4, np.int64)
+            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+            _lib.check(lib.schpf_louvain_device(dev.index, ctypes.c_void_p(stream), n, ptr(indptr), ptr(cols), ptr(data), gamma,
+                                                ptr(labels), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return (labels, dict(zip(names, stats.tolist()))) if return_stats else labels
+
+    from scipy.sparse import csr_matrix, issparse
+    back_to_torch = _is_tensor(graph)
+    if back_to_torch:
+        import torch
+        graph = graph.to_sparse_csr()
+        graph = csr_matrix((graph.values().numpy(), graph.col_indices().numpy(), graph.crow_indices().numpy()),
+                           shape=tuple(graph.shape))
+    G = graph.tocsr() if issparse(graph) else csr_matrix(np.asarray(graph))
+    if G.shape[0] != G.shape[1]:
+        raise ValueError("graph must be a square matrix")
+    if not G.has_canonical_format:          # columns ascending, no entry twice: on a copy
+        G = G.copy()
+        G.sum_duplicates()
+    labels, stats = _louvain_host(np.ascontiguousarray(G.indptr, dtype=np.int64), np.ascontiguousarray(G.indices, dtype=np.int32),
+                                  np.ascontiguousarray(G.data, dtype=np.float64), gamma, device)
+    if back_to_torch:
+        labels = torch.from_numpy(labels)
+    return (labels, dict(zip(names, np.asarray(stats).tolist()))) if return_stats else labels
+
+
+def modularity(graph, labels, resolution=1.0):
+    """Newman's modularity of a labelling of a weighted symmetric graph, in plain double arithmetic on the host:
+    sum over the communities of  in_c / W - resolution * (tot_c / W)^2,  W the sum of all entries, in_c the sum of the
+    entries with both ends in c, tot_c the sum of the rows of c.  0 for a graph without weight."""
+    from scipy.sparse import coo_matrix, issparse
+    gamma = _resolution(resolution)
+    if _is_tensor(graph):
+        graph = graph.cpu().to_dense().numpy()
+    if _is_tensor(labels):
+        labels = labels.cpu().numpy()
+    A = graph.tocoo() if issparse(graph) else coo_matrix(np.asarray(graph))
+    labels = np.asarray(labels).astype(np.int64).ravel()
+    if A.shape[0] != A.shape[1] or len(labels) != A.shape[0]:
+        raise ValueError("graph must be square, with one label per row")
+    if len(labels) and labels.min() < 0:
+        raise ValueError("labels must be >= 0")
+    data = A.data.astype(np.float64)
+    total = data.sum()
+    if not total > 0:
+        return 0.0
+    inside = data[labels[A.row] == labels[A.col]].sum()
+    tot = np.bincount(labels[A.row], weights=data)
+    return float(inside / total - gamma * (tot * tot).sum() / (total * total))

@@ -323,6 +323,14 @@ class scHPF(BaseEstimator):
         return (knn_graph(indices, distances, indices.shape[0]),
                 knn_connectivities(indices, distances, method=method, device=device))
 
+    def clusters(self, k=15, metric="euclidean", method="jaccard", resolution=1.0, device=None):
+        """The Louvain clusters of this model's cells: int32 labels 0 .. C - 1, one per cell, from the weighted graph of
+        `neighbor_graph(k, metric, method)` on the GPU (schpf_amd.louvain; a larger `resolution` gives more clusters).
+        The same model gives the same labels, bit for bit.  An addition to the reference's surface."""
+        from .neighbors import louvain
+        graph = self.neighbor_graph(k=k, metric=metric, method=method, device=device)[1]
+        return louvain(graph, resolution=resolution, device=device)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
