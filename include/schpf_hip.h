@@ -464,6 +464,48 @@ int schpf_louvain(int device, int n, const int64_t *indptr, const int32_t *indic
 int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, const double *data, double gamma,
                         int32_t *labels, int64_t stats[4]);
 
+/* Wilcoxon rank sums of every gene for every group of cells: the exact integers behind "which genes mark
+ * each cluster".  With average ranks for ties, twice a rank is an integer; every output below is an integer sum, exact in
+ * any order, and is equal bit for bit however the work was scheduled.
+ * Input.  The count matrix gene-major (CSC of cells x genes), ncells = N cells and ngenes = J genes: indptr[J + 1] (int64),
+ *   indices (int32: cell ids, strictly ascending within a gene), data (float32, finite and >= 0; -0.0 counts as 0; stored
+ *   zeros are allowed and are zeros like the implicit ones), nnz = indptr[J] < 2^32.  labels[N] (int32) in [-1, G), G =
+ *   ngroups: -1 means the cell is ranked with all the others but belongs to no group.  G >= 1, G * J < 2^31 and N < 2^21
+ *   (the tie term is a sum of cubes and stays under 2^63); these are refused before anything is read.
+ *   Refused, the outputs untouched, M the smallest offending gene (for labels: cell), structure before values, indptr before
+ *   the cell ids, the matrix before the labels:
+ *     "indptr must be 0 at gene 0 and must be non-decreasing; offending gene M"  (indptr[0] != 0: gene 0; indptr[M + 1] <
+ *       indptr[M]: gene M)
+ *     "cell ids must be in [0, ncells) and strictly ascending within a gene; offending gene M"
+ *     "values must be finite and >= 0; offending gene M"
+ *     "labels must be in [-1, ngroups); offending cell M"
+ * Definition.  For gene j:  z_j = N minus the number of stored entries with value > 0 -- all the cells that tie at zero.
+ *   For a stored entry with value v > 0:  lo = z_j + the number of stored entries of the gene with 0 < value < v;  t = the
+ *   number of stored entries of the gene with value == v (float32 equality);  twice the average rank is r2 = 2 lo + t + 1.
+ *   Every zero cell has r2 = z_j + 1.
+ * Output, all int64.  n[G]: the cells per group.  zeros[J] = z_j.  ties[J] = (z_j^3 - z_j) + the sum over the distinct positive
+ *   values of (t^3 - t).  nexpr[G x J], row-major by group: the cells of group g with a positive value in gene j.
+ *   rank2[G x J]: the sum of r2 over the cells of group g, zeros included = n_g (z_j + 1) + the sum over the group's positive
+ *   entries of (r2 - z_j - 1).  An empty group has zeros in its rows of nexpr and rank2.
+ *   (The Mann-Whitney U of group g against the rest is (rank2 - n_g (n_g + 1)) / 2.)
+ * N = 0 or J = 0 succeeds and reads no input: every output that is not NULL is written as zeros.  Bad arguments fail with a
+ * message.  Stateless; device memory that cannot be had returns SCHPF_ERR_NO_MEMORY (scratch: about 32 nnz bytes and the
+ * sort's own, about 12 nnz).
+ * _device: indptr, indices, data, labels and the five outputs are DEVICE pointers on `device`; stream as in
+ *   schpf_knn_device; synchronised before the call returns.
+ * schpf_rank_sums: host pointers, staged through the device; the same result.
+ * schpf_debug_rank_sums: test hook (host only, no GPU needed): the serial restatement of the definition, one std::sort per
+ *   gene, which both must match bit for bit. */
+int schpf_rank_sums_device(int device, void *stream, int ncells, int ngenes, const int64_t *indptr, const int32_t *indices,
+                           const float *data, const int32_t *labels, int ngroups, int64_t *n, int64_t *zeros, int64_t *ties,
+                           int64_t *nexpr, int64_t *rank2);
+int schpf_rank_sums(int device, int ncells, int ngenes, const int64_t *indptr, const int32_t *indices, const float *data,
+                    const int32_t *labels, int ngroups, int64_t *n, int64_t *zeros, int64_t *ties, int64_t *nexpr,
+                    int64_t *rank2);
+int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const int32_t *indices, const float *data,
+                          const int32_t *labels, int ngroups, int64_t *n, int64_t *zeros, int64_t *ties, int64_t *nexpr,
+                          int64_t *rank2);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

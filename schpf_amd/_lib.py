@@ -92,6 +92,9 @@ SIGNATURES = {
     "schpf_louvain_device": [_int, _vp, _int, _vp, _vp, _vp, _dbl, _vp, _i64p],
     "schpf_louvain": [_int, _int, _vp, _vp, _vp, _dbl, _vp, _i64p],
     "schpf_debug_louvain": [_int, _vp, _vp, _vp, _dbl, _vp, _i64p],
+    "schpf_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
+    "schpf_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
+    "schpf_debug_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_choose_config": [_int, _int, _int, ctypes.POINTER(_int)],

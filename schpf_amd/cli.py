@@ -138,6 +138,10 @@ def _parser():
                             "per cell.")
     score.add_argument("--resolution", type=float, default=None, metavar="R",
                        help="Resolution of --clusters: larger values give more, smaller clusters. [1.0]")
+    score.add_argument("--markers", default=False, action="store_true",
+                       help="With -i and --clusters: also write the Wilcoxon rank-sum test of every gene, each cluster "
+                            "against all the other cells, as marker_scores.txt and marker_pvals_adj.txt (genes x clusters); "
+                            "with --genefile also ranked_markers.txt, the gene names by descending score per cluster.")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -317,6 +321,8 @@ def _score(args, outprefix):
     else:
         if args.ppc:
             raise ValueError("--ppc needs the count matrix (-i)")
+        if args.markers:
+            raise ValueError("--markers needs the count matrix (-i)")
         del args.input   # the arguments file of a run without the matrix stays what it was
     if not args.ppc:
         del args.ppc     # ... and so does the arguments file of a run without the check
@@ -333,7 +339,18 @@ def _score(args, outprefix):
             if args.clusters:
                 print("Saving clusters.....")
                 args.resolution = 1.0 if args.resolution is None else args.resolution
-                np.savetxt(outprefix + "clusters.txt", louvain(graph, resolution=args.resolution), fmt="%d")
+                labels = louvain(graph, resolution=args.resolution)
+                np.savetxt(outprefix + "clusters.txt", labels, fmt="%d")
+                if args.markers:
+                    from .markers import rank_genes_groups
+                    print("Saving marker genes.....")
+                    found = rank_genes_groups(data, labels)
+                    np.savetxt(outprefix + "marker_scores.txt", found["scores"].T, delimiter="\t")
+                    np.savetxt(outprefix + "marker_pvals_adj.txt", found["pvals_adj"].T, delimiter="\t")
+                    if args.genefile is not None:
+                        ranks = np.argsort(found["scores"].T, axis=0)[::-1]
+                        ranked = np.stack([genes[ranks[:, c], name_col] for c in range(ranks.shape[1])]).T
+                        np.savetxt(outprefix + "ranked_markers.txt", ranked, fmt="%s", delimiter="\t")
     else:
         if args.knn_graph is not None:
             raise ValueError("--knn-graph needs the neighbour lists (--knn K)")
@@ -345,7 +362,11 @@ def _score(args, outprefix):
     if not args.clusters:
         if args.resolution is not None:
             raise ValueError("--resolution belongs to --clusters")
+        if args.markers:
+            raise ValueError("--markers needs the clusters (--knn K --knn-graph M --clusters)")
         del args.clusters, args.resolution   # ... and without its clusters
+    if not args.markers:
+        del args.markers                     # ... and without their marker genes
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

@@ -150,6 +150,38 @@ inline std::string louvain_bad_columns(int64_t row)
 inline std::string louvain_bad_values(int64_t row) { return "values must be finite and >= 0; offending row " + std::to_string(row); }
 constexpr int LOUVAIN_ROUNDS = 32, LOUVAIN_LEVELS = 32;   // the caps of the definition
 
+// What schpf_rank_sums, schpf_rank_sums_device and schpf_debug_rank_sums refuse alike (include/schpf_hip.h), before anything
+// is read; ncells = 0 or ngenes = 0 is asked next by the caller.  nullptr: the arguments are fine
+constexpr int RANK_SUMS_MAX_CELLS = 1 << 21;   // the tie term, a sum of cubes, stays under 2^63
+inline const char *rank_sums_bad_args(int ncells, int ngenes, int ngroups, const void *indptr, const void *labels, const void *n,
+                                      const void *zeros, const void *ties, const void *nexpr, const void *rank2)
+{
+    if (ncells < 0 || ncells >= RANK_SUMS_MAX_CELLS) return "ncells must be in [0, 2^21)";
+    if (ngenes < 0) return "ngenes must be >= 0";
+    if (ngroups < 1) return "ngroups must be at least 1";
+    if ((int64_t)ngroups * (int64_t)ngenes >= (int64_t)1 << 31) return "ngroups * ngenes must be below 2^31";
+    if (ncells == 0 || ngenes == 0) return nullptr;
+    if (!indptr || !labels) return "indptr and labels must not be NULL";
+    if (!n || !zeros || !ties || !nexpr || !rank2) return "n, zeros, ties, nexpr and rank2 must not be NULL";
+    return nullptr;
+}
+inline const char *rank_sums_bad_nnz(int64_t nnz, const void *indices, const void *data)
+{
+    if (nnz >= (int64_t)1 << 32) return "nnz must be below 2^32";
+    if (nnz > 0 && (!indices || !data)) return "indices and data must not be NULL";
+    return nullptr;
+}
+inline std::string rank_sums_bad_indptr(int64_t gene)
+{
+    return "indptr must be 0 at gene 0 and must be non-decreasing; offending gene " + std::to_string(gene);
+}
+inline std::string rank_sums_bad_cells(int64_t gene)
+{
+    return "cell ids must be in [0, ncells) and strictly ascending within a gene; offending gene " + std::to_string(gene);
+}
+inline std::string rank_sums_bad_values(int64_t gene) { return "values must be finite and >= 0; offending gene " + std::to_string(gene); }
+inline std::string rank_sums_bad_labels(int64_t cell) { return "labels must be in [-1, ngroups); offending cell " + std::to_string(cell); }
+
 // RAII device buffer
 struct DevBuf {
     void *p = nullptr;

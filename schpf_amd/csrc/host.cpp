@@ -1,7 +1,7 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
 // check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
-// (knn.hip), of the neighbour graphs (knn_graph.hip) and of the Louvain clustering (louvain.hip), and the SCHPF_BACKTRACE
-// crash handler.  Nothing here touches the device.
+// (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip) and of the rank sums
+// (rank_sums.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -600,6 +600,73 @@ int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, co
         stats[1] = levels;
         stats[2] = rounds;
         stats[3] = w2_first;
+    });
+}
+
+// rank_sums.hip restated: the definition of include/schpf_hip.h gene by gene -- the positive entries of a
+// gene sorted by value with one std::sort, then one walk over the runs of equal values
+int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const int32_t *indices, const float *data,
+                          const int32_t *labels, int ngroups, int64_t *n, int64_t *zeros, int64_t *ties, int64_t *nexpr,
+                          int64_t *rank2)
+{
+    if (const char *why = rank_sums_bad_args(ncells, ngenes, ngroups, indptr, labels, n, zeros, ties, nexpr, rank2))
+        return fail("%s", why);
+    return guarded([&] {
+        const int64_t N = ncells, J = ngenes, G = ngroups;
+        if (N == 0 || J == 0) {
+            if (n) std::fill(n, n + G, (int64_t)0);
+            if (zeros) std::fill(zeros, zeros + J, (int64_t)0);
+            if (ties) std::fill(ties, ties + J, (int64_t)0);
+            if (nexpr) std::fill(nexpr, nexpr + G * J, (int64_t)0);
+            if (rank2) std::fill(rank2, rank2 + G * J, (int64_t)0);
+            return;
+        }
+        if (indptr[0] != 0) throw std::invalid_argument(rank_sums_bad_indptr(0));
+        for (int64_t j = 0; j < J; ++j)
+            if (indptr[j + 1] < indptr[j]) throw std::invalid_argument(rank_sums_bad_indptr(j));
+        const int64_t nnz = indptr[J];
+        if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
+        for (int64_t j = 0; j < J; ++j)
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= N || (e > indptr[j] && indices[e - 1] >= indices[e]))
+                    throw std::invalid_argument(rank_sums_bad_cells(j));
+        for (int64_t j = 0; j < J; ++j)
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (!(data[e] >= 0.0f && std::isfinite(data[e]))) throw std::invalid_argument(rank_sums_bad_values(j));
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] < -1 || labels[i] >= G) throw std::invalid_argument(rank_sums_bad_labels(i));
+
+        std::vector<int64_t> cnt((size_t)G, 0), z((size_t)J), tie((size_t)J), expr((size_t)(G * J), 0), r((size_t)(G * J), 0);
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] >= 0) ++cnt[(size_t)labels[i]];
+        std::vector<std::pair<float, int32_t>> pos;   // (value, group of the cell) of a gene's positive entries
+        for (int64_t j = 0; j < J; ++j) {
+            pos.clear();
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (data[e] > 0.0f) pos.emplace_back(data[e], labels[indices[e]]);
+            std::sort(pos.begin(), pos.end());
+            const int64_t zj = N - (int64_t)pos.size();
+            z[(size_t)j] = zj;
+            tie[(size_t)j] = zj * zj * zj - zj;
+            for (int64_t g = 0; g < G; ++g) r[(size_t)(g * J + j)] = cnt[(size_t)g] * (zj + 1);
+            for (size_t x = 0; x < pos.size();) {
+                size_t y = x;
+                while (y < pos.size() && pos[y].first == pos[x].first) ++y;
+                const int64_t t = (int64_t)(y - x), r2 = 2 * (zj + (int64_t)x) + t + 1;
+                tie[(size_t)j] += t * t * t - t;
+                for (; x < y; ++x) {
+                    const int32_t g = pos[x].second;
+                    if (g < 0) continue;
+                    ++expr[(size_t)(g * J + j)];
+                    r[(size_t)(g * J + j)] += r2 - zj - 1;
+                }
+            }
+        }
+        std::copy(cnt.begin(), cnt.end(), n);
+        std::copy(z.begin(), z.end(), zeros);
+        std::copy(tie.begin(), tie.end(), ties);
+        std::copy(expr.begin(), expr.end(), nexpr);
+        std::copy(r.begin(), r.end(), rank2);
     });
 }
 

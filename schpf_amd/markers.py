@@ -1,0 +1,250 @@
+"""Marker genes per cluster on the GPU: exact Wilcoxon rank sums of every gene for every group of cells.
+
+"Which genes mark each cluster?" is a rank-sum test of every gene, each group of cells against the rest.  With average
+ranks for ties, twice a rank is an integer: the library (schpf_rank_sums[_device]) returns the rank sums, the tie terms and
+the counts as exact int64 sums, the same bits however the work was scheduled.  `rank_sums` hands the count matrix over;
+`rank_genes_groups` turns the integers into z-scores, p-values, Benjamini-Hochberg adjusted p-values, fold changes and
+the fractions of expressing cells -- plain NumPy / SciPy on G x J numbers, not part of the bit contract.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from . import _lib
+from .device_input import is_torch_tensor, on_gpu
+
+__all__ = ["rank_sums", "rank_genes_groups", "benjamini_hochberg"]
+
+NAMES = ("n", "zeros", "ties", "nexpr", "rank2")
+STATISTICS = ("scores", "pvals", "pvals_adj", "logfoldchanges", "pct_in", "pct_out", "mean_in", "mean_out")
+MAX_CELLS = 1 << 21
+
+
+def _p(a):
+    return None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _rank_sums_host(ncells, ngenes, indptr, indices, data, labels, ngroups, device):
+    """schpf_rank_sums on the C-contiguous arrays of a CSC matrix (int64, int32, float32) and int32 labels -> the five int64
+    arrays n[G], zeros[J], ties[J], nexpr[G, J], rank2[G, J]."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if device is None:
+        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    out = _outputs(ngroups, ngenes)
+    _lib.check(lib.schpf_rank_sums(int(device), ncells, ngenes, _p(indptr), _p(indices), _p(data), _p(labels), ngroups,
+                                   *[_p(a) for a in out]))
+    return out
+
+
+def _outputs(ngroups, ngenes):
+    return (np.zeros(ngroups, np.int64), np.zeros(ngenes, np.int64), np.zeros(ngenes, np.int64),
+            np.zeros((ngroups, ngenes), np.int64), np.zeros((ngroups, ngenes), np.int64))
+
+
+def _groups(labels, ngroups, ncells):
+    """(labels as they are, G): one label per cell, G = ngroups or the largest label + 1, at least 1."""
+    if len(labels.shape) != 1 or labels.shape[0] != ncells:
+        raise ValueError("labels must hold one label per cell: %d, got shape %s" % (ncells, tuple(labels.shape)))
+    if ngroups is None:
+        ngroups = max(1, int(labels.max()) + 1) if ncells else 1
+    ngroups = int(ngroups)
+    if ngroups < 1:
+        raise ValueError("ngroups must be at least 1, got %d" % ngroups)
+    return ngroups
+
+
+def _check_sizes(ncells, ngenes, ngroups):
+    if ncells >= MAX_CELLS:          # what the library refuses before it reads anything, said before anything is converted
+        raise ValueError("ncells must be in [0, 2^21), got %d" % ncells)
+    if ngroups * ngenes >= 2 ** 31:
+        raise ValueError("ngroups * ngenes must be below 2^31, got %d * %d" % (ngroups, ngenes))
+
+
+def _gpu_coo(X):
+    """A sparse COO / CSR tensor on a GPU -> (rows, cols, values) of its coalesced COO form: duplicates summed, row-major."""
+    import torch
+    if X.layout not in (torch.sparse_coo, torch.sparse_csr):
+        raise TypeError("a matrix on the GPU must be a torch sparse COO or CSR tensor, got layout %s" % X.layout)
+    if X.dim() != 2:
+        raise ValueError("X must be a 2-d cell x gene matrix, got a tensor of shape %s" % (tuple(X.shape),))
+    X = X.detach()
+    if X.layout == torch.sparse_csr:
+        crow = X.crow_indices().to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(X.shape[0], device=X.device), crow[1:] - crow[:-1])
+        X = torch.sparse_coo_tensor(torch.stack([rows, X.col_indices().to(torch.int64)]), X.values(), size=tuple(X.shape))
+    X = X.coalesce()
+    return X.indices()[0], X.indices()[1], X.values()
+
+
+def _gpu_csc(X):
+    """A sparse COO / CSR tensor on a GPU -> (indptr int64, cell ids int32, values float32) of its CSC form, duplicates
+    summed, with torch on that GPU."""
+    import torch
+    rows, cols, values = _gpu_coo(X)
+    N, J = int(X.shape[0]), int(X.shape[1])
+    order = torch.argsort(cols * N + rows)              # gene-major, the cells ascending within a gene
+    indptr = torch.zeros(J + 1, dtype=torch.int64, device=X.device)
+    if J:
+        indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=J), 0)
+    return indptr, rows[order].to(torch.int32).contiguous(), values[order].to(torch.float32).contiguous()
+
+
+def rank_sums(X, labels, ngroups=None, device=None):
+    """The exact integers of the rank-sum test of every gene for every group of cells: a dict of int64 arrays
+    n[G] (cells per group), zeros[J] (cells that tie at zero), ties[J] (the sum of t^3 - t over the tie groups, the zeros
+    included), nexpr[G, J] (cells of the group with a positive value) and rank2[G, J] (twice the sum of the group's average
+    ranks).  Twice the Mann-Whitney U of group g against the rest is rank2[g] - n[g] (n[g] + 1).
+
+    X: cells x genes.  A SciPy sparse matrix is converted with tocsc() on a copy, duplicates summed; NumPy arrays come back.
+    A torch sparse COO or CSR tensor on a GPU is converted to CSC with torch on that GPU and ranked on torch's current
+    stream; tensors on that GPU come back.  Values are ranked as float32 (counts up to 2^24 are exact), must be finite and
+    >= 0; stored zeros are zeros like the implicit ones.
+
+    labels: one integer per cell in [-1, G), NumPy or a tensor; -1 ranks the cell with all the others but puts it in no
+    group.  ngroups: G, default the largest label + 1.  Fewer than 2^21 cells, and G * J < 2^31.  What the library refuses
+    raises ValueError naming the smallest offending gene or cell."""
+    if on_gpu(X):
+        import torch
+        lib = _lib.load()
+        _lib.require_gpu()
+        dev = X.device
+        if device is not None and int(device) != dev.index:
+            raise ValueError("X is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+        N, J = int(X.shape[0]), int(X.shape[1])
+        with torch.cuda.device(dev):
+            lab = (labels if is_torch_tensor(labels) else torch.tensor(np.asarray(labels))).detach()
+            G = _groups(lab, ngroups, N)
+            _check_sizes(N, J, G)
+            lab = lab.to(device=dev, dtype=torch.int32).contiguous()
+            indptr, cells, values = _gpu_csc(X)
+            out = [torch.zeros(s, dtype=torch.int64, device=dev) for s in ((G,), (J,), (J,), (G, J), (G, J))]
+            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+            _lib.check(lib.schpf_rank_sums_device(dev.index, ctypes.c_void_p(stream), N, J, ptr(indptr), ptr(cells), ptr(values),
+                                                  ptr(lab), G, *[ptr(t) for t in out]))
+        return dict(zip(NAMES, out))
+
+    from scipy.sparse import csc_matrix, issparse
+    if is_torch_tensor(X):                # a tensor in host memory: as SciPy
+        from .device_input import classify
+        X = classify(X).matrix
+    if is_torch_tensor(labels):
+        labels = labels.detach().cpu().numpy()
+    labels = np.asarray(labels)
+    C = csc_matrix(X) if not issparse(X) else X.tocsc()
+    if C is X:
+        C = C.copy()
+    C.sum_duplicates()                    # also sorts the cells of every gene
+    N, J = C.shape
+    G = _groups(labels, ngroups, N)
+    _check_sizes(N, J, G)
+    if labels.size and (labels.min() < np.iinfo(np.int32).min or labels.max() > np.iinfo(np.int32).max):
+        raise ValueError("labels must be in [-1, ngroups)")
+    out = _rank_sums_host(N, J, np.ascontiguousarray(C.indptr, dtype=np.int64), np.ascontiguousarray(C.indices, dtype=np.int32),
+                          np.ascontiguousarray(C.data, dtype=np.float32), np.ascontiguousarray(labels, dtype=np.int32), G, device)
+    return dict(zip(NAMES, out))
+
+
+def benjamini_hochberg(pvals):
+    """Benjamini-Hochberg adjusted p-values along the last axis: p_(i) J / i, made monotone from the largest down, at most 1.
+    A row that holds a NaN is NaN."""
+    p = np.asarray(pvals, dtype=np.float64)
+    J = p.shape[-1]
+    if J == 0:
+        return p.copy()
+    order = np.argsort(p, axis=-1)
+    ranked = np.take_along_axis(p, order, axis=-1) * (float(J) / np.arange(1, J + 1))
+    ranked = np.minimum(np.minimum.accumulate(ranked[..., ::-1], axis=-1)[..., ::-1], 1.0)
+    out = np.empty_like(p)
+    np.put_along_axis(out, order, ranked, axis=-1)
+    out[np.isnan(p).any(axis=-1)] = np.nan
+    return out
+
+
+def _scaled(X, target_sum):
+    """Every cell's counts scaled to `target_sum` ("median": the median depth of the cells), in float32."""
+    if on_gpu(X):
+        import torch
+        rows, cols, values = _gpu_coo(X)
+        values = values.to(torch.float32)
+        depth = torch.zeros(X.shape[0], dtype=torch.float32, device=X.device).index_add_(0, rows, values)
+        target = float(torch.median(depth)) if isinstance(target_sum, str) and target_sum == "median" else float(target_sum)
+        factor = torch.where(depth > 0, torch.tensor(target, dtype=torch.float32, device=X.device) / depth, torch.zeros_like(depth))
+        return torch.sparse_coo_tensor(torch.stack([rows, cols]), values * factor[rows], size=tuple(X.shape)).coalesce()
+    from scipy.sparse import csr_matrix
+    R = csr_matrix(X, dtype=np.float32, copy=True)
+    R.sum_duplicates()
+    depth = np.asarray(R.sum(axis=1), dtype=np.float32).ravel()
+    target = np.float32(np.median(depth)) if isinstance(target_sum, str) and target_sum == "median" else np.float32(target_sum)
+    factor = np.zeros_like(depth)
+    np.divide(target, depth, out=factor, where=depth > 0)
+    R.data *= np.repeat(factor, np.diff(R.indptr))
+    return R
+
+
+def _group_sums(X, labels, G):
+    """sums[g, j] = the sum of X[i, j] over the cells of group g, and the sums over all cells: one sparse product with the
+    group indicator."""
+    if on_gpu(X):
+        import torch
+        lab = (labels if is_torch_tensor(labels) else torch.tensor(np.asarray(labels))).to(X.device).to(torch.int64)
+        rows, cols, values = _gpu_coo(X)
+        values = values.to(torch.float64)
+        onehot = torch.zeros((X.shape[0], G + 1), dtype=torch.float64, device=X.device)
+        onehot[torch.arange(X.shape[0], device=X.device), torch.where(lab >= 0, lab, torch.full_like(lab, G))] = 1.0
+        both = torch.sparse.mm(torch.sparse_coo_tensor(torch.stack([cols, rows]), values, size=(X.shape[1], X.shape[0])), onehot)
+        both = both.t().cpu().numpy()
+        return both[:G], both.sum(axis=0)
+    from scipy.sparse import csr_matrix
+    labels = np.asarray(labels)
+    inside = np.flatnonzero(labels >= 0)
+    indicator = csr_matrix((np.ones(len(inside)), (labels[inside], inside)), shape=(G, len(labels)))
+    Xd = csr_matrix(X, dtype=np.float64)
+    return np.asarray((indicator @ Xd).todense()), np.asarray(Xd.sum(axis=0)).ravel()
+
+
+def rank_genes_groups(X, labels, tie_correct=True, target_sum=None, device=None):
+    """The Wilcoxon rank-sum test of every gene, each group of cells against all the other cells: a dict of (G, J) float64
+    arrays `scores`, `pvals`, `pvals_adj`, `logfoldchanges`, `pct_in`, `pct_out`, `mean_in`, `mean_out`, and `n`, the cells
+    per group.  G is the largest label + 1; cells labelled -1 are in no group and count among "all the others".
+
+    From the exact integers of `rank_sums`, with n_o = N - n_g:
+        d = rank2 - n_g (N + 1);  var = n_g n_o ((N + 1) - tie) / 12,  tie = ties / (N (N - 1)) if tie_correct else 0
+        scores = d / (2 sqrt(var)), 0 where var == 0;  pvals = erfc(|scores| / sqrt 2)
+    -- the normal approximation of scipy.stats.mannwhitneyu without continuity correction; tie_correct=False is the
+    z-score of scanpy's default.  pvals_adj: Benjamini-Hochberg within each group.  pct_in / pct_out: the fraction of
+    cells with a positive value inside and outside the group; mean_in / mean_out the mean values;
+    logfoldchanges = log2((mean_in + 1e-9) / (mean_out + 1e-9)).  A group that is empty or holds all the cells gets NaN.
+
+    target_sum: scale every cell's counts to that total before ranking ("median": the median depth), in float32."""
+    if is_torch_tensor(X) and not on_gpu(X):      # a tensor in host memory: as SciPy
+        from .device_input import classify
+        X = classify(X).matrix
+    if is_torch_tensor(labels) and not on_gpu(X):
+        labels = labels.detach().cpu().numpy()
+    if target_sum is not None:
+        X = _scaled(X, target_sum)
+    sums = rank_sums(X, labels, device=device)
+    n, zeros, ties, nexpr, rank2 = [np.asarray(sums[k].cpu() if is_torch_tensor(sums[k]) else sums[k]) for k in NAMES]
+    G, J = rank2.shape
+    N = int(X.shape[0])
+    n_g = n.astype(np.float64)[:, None]
+    n_o = N - n_g
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tie = ties.astype(np.float64)[None, :] / (float(N) * (N - 1)) if tie_correct and N > 1 else 0.0
+        var = n_g * n_o * ((N + 1) - tie) / 12.0
+        d = rank2.astype(np.float64) - n_g * (N + 1)      # exact: both are below 2^53
+        scores = np.where(var > 0, d / (2.0 * np.sqrt(np.where(var > 0, var, 1.0))), 0.0)
+        scores = np.where((n_g > 0) & (n_o > 0), scores, np.nan)
+        from scipy.special import erfc
+        pvals = erfc(np.abs(scores) / np.sqrt(2.0))
+        group_sums, all_sums = _group_sums(X, labels, G)
+        mean_in = group_sums / n_g
+        mean_out = (all_sums[None, :] - group_sums) / n_o
+        pct_in = nexpr / n_g
+        pct_out = ((N - zeros)[None, :] - nexpr) / n_o
+        logfoldchanges = np.log2((mean_in + 1e-9) / (mean_out + 1e-9))
+    return {"scores": scores, "pvals": pvals, "pvals_adj": benjamini_hochberg(pvals), "logfoldchanges": logfoldchanges,
+            "pct_in": pct_in, "pct_out": pct_out, "mean_in": mean_in, "mean_out": mean_out, "n": n}

@@ -331,6 +331,17 @@ class scHPF(BaseEstimator):
         graph = self.neighbor_graph(k=k, metric=metric, method=method, device=device)[1]
         return louvain(graph, resolution=resolution, device=device)
 
+    def markers(self, X, labels=None, k=15, metric="euclidean", method="jaccard", resolution=1.0, **kwargs):
+        """The marker genes of clusters of this model's cells: the Wilcoxon rank-sum test of every gene of the count matrix
+        X (cells x genes, what `fit` took), each cluster against all the other cells, on the GPU -- the dict of
+        schpf_amd.rank_genes_groups (scores, pvals, pvals_adj, logfoldchanges, ...; kwargs go there: tie_correct,
+        target_sum, device).  labels=None: the clusters are `clusters(k, metric, method, resolution)`.  An addition to the
+        reference's surface."""
+        from .markers import rank_genes_groups
+        if labels is None:
+            labels = self.clusters(k=k, metric=metric, method=method, resolution=resolution, device=kwargs.get("device"))
+        return rank_genes_groups(X, labels, **kwargs)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
