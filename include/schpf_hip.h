@@ -506,6 +506,51 @@ int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const i
                           const int32_t *labels, int ngroups, int64_t *n, int64_t *zeros, int64_t *ties, int64_t *nexpr,
                           int64_t *rank2);
 
+/* Simulated doublets: rows that are the sum of two observed cells, the first step of Scrublet's doublet
+ * score.  Integer work whose result is fully determined: every schedule gives the same bits.
+ * Parents.  Simulated row s has the parents (a, b):  w = philox4x32_10(counter (s & 0xffffffff, s >> 32, 0, 1), key (low,
+ *   high word of seed));  a = (uint64(w[0]) * ncells) >> 32,  b = (uint64(w[1]) * ncells) >> 32.  Thinning's counters end in
+ *   0, so one seed gives unrelated streams.  a == b is allowed.  The draw depends on (seed, ncells, s) alone.
+ *   parents: int32[n_sim, 2], the rows s = first, first + 1, ..., first + n_sim - 1.  first >= 0, 0 <= n_sim < 2^31,
+ *   0 < ncells < 2^31.  schpf_doublet_parents is host only and needs no GPU; _device writes the same bits to DEVICE memory
+ *   from a kernel (stream as in schpf_thin_counts_device; synchronised before the call returns).
+ * Sum of a pair.  Input: a CSR matrix of ncells x ngenes with nnz stored entries, the columns strictly ascending within a
+ *   row (canonical, no duplicates), every value a non-negative integer <= 2^24 (what thinning accepts); parents int32[n_pairs,
+ *   2].  Row s of the result holds one entry for every column stored in parent a or in parent b, columns ascending, the value
+ *   the sum of the stored values as int32; a column stored in either parent is stored in the result even where the sum is 0,
+ *   so the structure depends on the indices alone.  out_indptr int64[n_pairs + 1], out_indices int32, out_values int32.
+ *   With out_indices == NULL and out_values == NULL only out_indptr is written: the caller reads out_indptr[n_pairs],
+ *   allocates, and calls again with capacity = the entries the two arrays hold; capacity < out_indptr[n_pairs] is refused
+ *   ("capacity must be at least ..."; the outputs are then unspecified).
+ *   Refused before anything is written, M the smallest offender, in this order:
+ *     "doublets: indptr must be 0 at row 0, must be non-decreasing and must end at nnz; offending row M"  (indptr[ncells] !=
+ *       nnz: row ncells)
+ *     "doublets: column index out of range at entry M"  (outside [0, ngenes), or an int64 beyond int32)
+ *     "doublets: columns must be strictly ascending within a row; offending row M"
+ *     "doublets: values must be integer counts in [0, 2^24]; offending entry M"
+ *     "doublets: parents must be in [0, ncells); offending pair M"
+ *   n_pairs == 0 or nnz == 0 succeeds without reading any input: out_indptr, where given, is written as zeros.  Sizes
+ *   outside [0, 2^31) and NULL pointers otherwise are refused.
+ * _device: indptr (of indptr_kind), indices (of idx_kind: SCHPF_IDX_*), val (of val_kind), parents and the outputs are DEVICE
+ *   pointers on `device`, read and written in place; stream as in schpf_thin_counts_device; synchronised before the call
+ *   returns.  Scratch: 8 (n_pairs + 1) bytes and the scan's own.
+ * schpf_doublet_rows: host pointers (int64 indptr, int32 indices), staged through the device; the same result.
+ * schpf_debug_doublet_rows: test hook (host only, no GPU needed): the serial restatement, a two-pointer merge per pair, which
+ *   both must match bit for bit. */
+int schpf_doublet_parents(int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed, int32_t *parents);
+int schpf_doublet_parents_device(int device, void *stream, int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed,
+                                 int32_t *parents);
+int schpf_doublet_rows_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const void *indptr,
+                              int indptr_kind, const void *indices, int idx_kind, const void *val, int val_kind, int64_t n_pairs,
+                              const int32_t *parents, int64_t *out_indptr, int32_t *out_indices, int32_t *out_values,
+                              int64_t capacity);
+int schpf_doublet_rows(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                       const void *val, int val_kind, int64_t n_pairs, const int32_t *parents, int64_t *out_indptr,
+                       int32_t *out_indices, int32_t *out_values, int64_t capacity);
+int schpf_debug_doublet_rows(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                             const void *val, int val_kind, int64_t n_pairs, const int32_t *parents, int64_t *out_indptr,
+                             int32_t *out_indices, int32_t *out_values, int64_t capacity);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

@@ -95,6 +95,11 @@ SIGNATURES = {
     "schpf_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
+    "schpf_doublet_parents": [_i64, _i64, _i64, ctypes.c_uint64, _vp],
+    "schpf_doublet_parents_device": [_int, _vp, _i64, _i64, _i64, ctypes.c_uint64, _vp],
+    "schpf_doublet_rows_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
+    "schpf_doublet_rows": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
+    "schpf_debug_doublet_rows": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_choose_config": [_int, _int, _int, ctypes.POINTER(_int)],

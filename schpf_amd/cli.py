@@ -142,6 +142,20 @@ def _parser():
                        help="With -i and --clusters: also write the Wilcoxon rank-sum test of every gene, each cluster "
                             "against all the other cells, as marker_scores.txt and marker_pvals_adj.txt (genes x clusters); "
                             "with --genefile also ranked_markers.txt, the gene names by descending score per cluster.")
+    score.add_argument("--doublets", default=False, action="store_true",
+                       help="With -i: also write Scrublet's doublet score of every cell, from simulated doublets projected "
+                            "onto the model together with the cells (doublet_scores.txt: score, standard error and the "
+                            "simulated rows among the neighbours, one row per cell; doublet_scores_sim.txt: score, "
+                            "neighbours and the two parents of every simulated row).")
+    score.add_argument("--doublet-ratio", type=float, default=None, metavar="R",
+                       help="With --doublets: simulated rows per observed cell. [2.0]")
+    score.add_argument("--doublet-rate", type=float, default=None, metavar="RHO",
+                       help="With --doublets: the expected doublet rate. [0.06]")
+    score.add_argument("--doublet-k", type=int, default=None, metavar="K",
+                       help="With --doublets: neighbours before the adjustment for the simulated rows. "
+                            "[round(0.5 sqrt(ncells))]")
+    score.add_argument("--doublet-seed", type=int, default=None, metavar="S",
+                       help="With --doublets: seed of the draw of the pairs. [0]")
     score.add_argument("--name-col", type=int, default=1, help="Zero-indexed column of --genefile with the names. [1]")
 
     proj = sub.add_parser("project", help="Project new cells onto a trained model.")
@@ -323,7 +337,9 @@ def _score(args, outprefix):
             raise ValueError("--ppc needs the count matrix (-i)")
         if args.markers:
             raise ValueError("--markers needs the count matrix (-i)")
-        del args.input   # the arguments file of a run without the matrix stays what it was
+        if args.doublets:
+            raise ValueError("--doublets needs the count matrix (-i)")
+        del args.input  # the arguments file of a run without the matrix stays what it was
     if not args.ppc:
         del args.ppc     # ... and so does the arguments file of a run without the check
     if args.knn is not None:
@@ -367,6 +383,24 @@ def _score(args, outprefix):
         del args.clusters, args.resolution   # ... and without its clusters
     if not args.markers:
         del args.markers                     # ... and without their marker genes
+    if args.doublets:
+        from .doublets import doublet_scores
+        print("Saving doublet scores.....")
+        args.doublet_ratio = 2.0 if args.doublet_ratio is None else args.doublet_ratio
+        args.doublet_rate = 0.06 if args.doublet_rate is None else args.doublet_rate
+        args.doublet_seed = 0 if args.doublet_seed is None else args.doublet_seed
+        found = doublet_scores(model, data, ratio=args.doublet_ratio, expected_rate=args.doublet_rate, k=args.doublet_k,
+                               seed=args.doublet_seed, verbose=False)
+        np.savetxt(outprefix + "doublet_scores.txt", np.stack([found["scores"], found["se"], found["k_sim"]], axis=1),
+                   delimiter="\t", header="score\tse\tk_sim")
+        np.savetxt(outprefix + "doublet_scores_sim.txt",
+                   np.concatenate([np.stack([found["scores_sim"], found["k_sim_sim"]], axis=1), found["parents"]], axis=1),
+                   delimiter="\t", header="score\tk_sim\tparent_a\tparent_b")
+    else:
+        for name in ("doublet_ratio", "doublet_rate", "doublet_k", "doublet_seed"):
+            if getattr(args, name) is not None:
+                raise ValueError("--%s belongs to --doublets" % name.replace("_", "-"))
+        del args.doublets, args.doublet_ratio, args.doublet_rate, args.doublet_k, args.doublet_seed   # ... or doublet scores
     _write_args(args, "{}score_commandline_args.json".format(outprefix))
 
 

@@ -1,0 +1,396 @@
+// Simulated doublets on the device (schpf_doublet_parents_device, schpf_doublet_rows[_device]): row s of the
+// result is the sum of the two rows of a canonical CSR count matrix that `parents` names.  Integer arithmetic only and
+// every output entry written by exactly one lane: host.cpp's serial restatement gives the same bits, whatever the grid.
+//
+//   doublet_parents_kernel   one simulated row per thread: the draw of doublets.h
+//   doublet_indptr_kernel    indptr starts at 0, does not decrease and ends at nnz: the smallest offending row
+//   doublet_entries_kernel   a wavefront per row of the matrix: every column in [0, ngenes) and above its left neighbour,
+//                            every value a count thinning accepts: the smallest offending entry / row
+//   doublet_pairs_kernel     one pair per thread: both parents in [0, ncells)
+//   doublet_length_kernel    a wavefront per pair: |A| + |B| - the columns they share, which the lanes find by bisection
+//   (rocPRIM exclusive scan of the lengths: out_indptr)
+//   doublet_fill_kernel      a wavefront per pair walks A, then B, in pieces of DOUBLET_PIECE = 64 entries.  A lane bisects
+//                            the other parent for its column: the rank there, plus its rank at home, minus the shared
+//                            columns before it -- a ballot, a popcount below the lane, and the count carried over from the
+//                            earlier pieces -- is its place in the output.  A writes every entry (with B's value added
+//                            where the column is shared), B the entries A does not hold.  No sort, no atomics; a row of
+//                            any length is a longer loop.
+// The other parent is read where it lies: a piece's window in it has no bound, and its few KiB stay in the vector cache
+// over the ten or so steps of a bisection.
+#include <climits>
+#include <cstdint>
+#include <memory>
+#include <string>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "common.h"
+#include "doublets.h"
+
+namespace schpf {
+namespace {
+
+constexpr int DB_THREADS = 256;
+constexpr int DOUBLET_PIECE = 64;   // entries of a parent per pass of a wavefront: one per lane
+constexpr unsigned long long NONE = ~0ull;
+// the smallest offenders, in device memory, in the order they are reported
+enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_PARENT, W_COUNT };
+
+__device__ __forceinline__ long long load_index(const void *p, int kind, int64_t j)
+{
+    return kind == SCHPF_IDX_I64 ? static_cast<const long long *>(p)[j] : (long long)static_cast<const int *>(p)[j];
+}
+// entry j of a value array of kind SCHPF_VAL_* (common.h read_count)
+__device__ __forceinline__ double load_value(const void *p, int kind, int64_t j)
+{
+    switch (kind) {
+    case SCHPF_VAL_I32: return (double)static_cast<const int *>(p)[j];
+    case SCHPF_VAL_I64: return (double)static_cast<const long long *>(p)[j];
+    case SCHPF_VAL_F32: return (double)static_cast<const float *>(p)[j];
+    default: return static_cast<const double *>(p)[j];
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(v, off);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(DB_THREADS) void doublet_parents_kernel(uint64_t first, int64_t n_sim, uint32_t N, uint32_t k0,
+                                                                     uint32_t k1, int32_t *__restrict__ parents)
+{
+    for (int64_t t = blockIdx.x * (int64_t)DB_THREADS + threadIdx.x; t < n_sim; t += (int64_t)gridDim.x * DB_THREADS) {
+        int32_t a, b;
+        doublet_parents_of(first + (uint64_t)t, N, k0, k1, &a, &b);
+        parents[2 * t] = a;
+        parents[2 * t + 1] = b;
+    }
+}
+
+// Every lane of a wavefront leaves the loop before the reduction: no early return
+__global__ __launch_bounds__(DB_THREADS) void doublet_indptr_kernel(const void *__restrict__ indptr, int indptr_kind, int64_t ncells,
+                                                                    int64_t nnz, unsigned long long *__restrict__ words)
+{
+    unsigned long long bad = NONE;
+    for (int64_t r = blockIdx.x * (int64_t)DB_THREADS + threadIdx.x; r <= ncells; r += (int64_t)gridDim.x * DB_THREADS) {
+        const long long here = load_index(indptr, indptr_kind, r);
+        const bool wrong = (r == 0 && here != 0) || (r == ncells ? here != nnz : load_index(indptr, indptr_kind, r + 1) < here);
+        if (wrong && (unsigned long long)r < bad) bad = (unsigned long long)r;
+    }
+    bad = wave_min(bad);
+    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_INDPTR, bad);
+}
+
+struct Matrix {   // a CSR in device memory whose indptr has been checked: every row lies in [0, nnz)
+    int64_t ncells, ngenes;
+    const void *indptr, *indices, *val;
+    int indptr_kind, idx_kind, val_kind;
+};
+
+__global__ __launch_bounds__(DB_THREADS) void doublet_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (DB_THREADS / 64);
+    unsigned long long bad_index = NONE, bad_order = NONE, bad_value = NONE;
+    for (int64_t r = blockIdx.x * (int64_t)(DB_THREADS / 64) + (threadIdx.x >> 6); r < m.ncells; r += waves) {
+        const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
+        for (int64_t e = from + lane; e < to; e += 64) {
+            const long long c = load_index(m.indices, m.idx_kind, e);
+            if ((c < 0 || c >= m.ngenes) && (unsigned long long)e < bad_index) bad_index = (unsigned long long)e;
+            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c && (unsigned long long)r < bad_order)
+                bad_order = (unsigned long long)r;
+            if (thin_value_bad(load_value(m.val, m.val_kind, e)) && (unsigned long long)e < bad_value) bad_value = (unsigned long long)e;
+        }
+    }
+    bad_index = wave_min(bad_index);
+    bad_order = wave_min(bad_order);
+    bad_value = wave_min(bad_value);
+    if (lane == 0) {
+        if (bad_index != NONE) atomicMin(words + W_BAD_INDEX, bad_index);
+        if (bad_order != NONE) atomicMin(words + W_BAD_ORDER, bad_order);
+        if (bad_value != NONE) atomicMin(words + W_BAD_VALUE, bad_value);
+    }
+}
+
+__global__ __launch_bounds__(DB_THREADS) void doublet_pairs_kernel(const int32_t *__restrict__ parents, int64_t n_pairs, int64_t ncells,
+                                                                   unsigned long long *__restrict__ words)
+{
+    unsigned long long bad = NONE;
+    for (int64_t s = blockIdx.x * (int64_t)DB_THREADS + threadIdx.x; s < n_pairs; s += (int64_t)gridDim.x * DB_THREADS) {
+        const int64_t a = parents[2 * s], b = parents[2 * s + 1];
+        if ((a < 0 || a >= ncells || b < 0 || b >= ncells) && (unsigned long long)s < bad) bad = (unsigned long long)s;
+    }
+    bad = wave_min(bad);
+    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_PARENT, bad);
+}
+
+// how many of the n ascending columns at p are below `key`
+template <typename I> __device__ __forceinline__ int64_t rank_in(const I *__restrict__ p, int64_t n, long long key)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((long long)p[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+struct Row {
+    int64_t from, len;
+};
+__device__ __forceinline__ Row row_of(const Matrix &m, int64_t r)
+{
+    const int64_t from = load_index(m.indptr, m.indptr_kind, r);
+    return Row{from, load_index(m.indptr, m.indptr_kind, r + 1) - from};
+}
+
+// len[s] = the stored columns of parent a or parent b; len[n_pairs] = 0, the scan's last input.  The shorter parent is
+// walked, the longer one bisected
+template <typename I>
+__global__ __launch_bounds__(DB_THREADS) void doublet_length_kernel(Matrix m, const int32_t *__restrict__ parents, int64_t n_pairs,
+                                                                    int64_t *__restrict__ len)
+{
+    const I *const indices = static_cast<const I *>(m.indices);
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (DB_THREADS / 64);
+    for (int64_t s = blockIdx.x * (int64_t)(DB_THREADS / 64) + (threadIdx.x >> 6); s <= n_pairs; s += waves) {
+        if (s == n_pairs) {   // wave-uniform
+            if (lane == 0) len[s] = 0;
+            continue;
+        }
+        Row A = row_of(m, parents[2 * s]), B = row_of(m, parents[2 * s + 1]);
+        if (A.len > B.len) { const Row t = A; A = B; B = t; }
+        int64_t shared = 0;   // wave-uniform
+        for (int64_t base = 0; base < A.len; base += DOUBLET_PIECE) {
+            const int64_t i = base + lane;
+            bool match = false;
+            if (i < A.len) {
+                const long long c = (long long)indices[A.from + i];
+                const int64_t pos = rank_in(indices + B.from, B.len, c);
+                match = pos < B.len && (long long)indices[B.from + pos] == c;
+            }
+            shared += __popcll(__ballot(match));
+        }
+        if (lane == 0) len[s] = A.len + B.len - shared;
+    }
+}
+
+// One parent's share of output row s.  `home` is walked; a lane's entry goes to out + its rank at home + its rank in
+// `other` - the shared columns before it.  first: write every entry, a shared one with the other parent's value added;
+// else: only the entries the other parent does not hold
+template <typename I, bool first>
+__device__ __forceinline__ void doublet_place(const Matrix &m, const I *__restrict__ indices, const Row home, const Row other, int lane,
+                                              int64_t out, int32_t *__restrict__ out_indices, int32_t *__restrict__ out_values)
+{
+    int64_t carry = 0;   // the shared columns of the earlier pieces: wave-uniform
+    for (int64_t base = 0; base < home.len; base += DOUBLET_PIECE) {
+        const int64_t i = base + lane;
+        const bool active = i < home.len;
+        long long c = 0;
+        int64_t pos = 0;
+        bool match = false;
+        int32_t v = 0;
+        if (active) {
+            c = (long long)indices[home.from + i];
+            v = (int32_t)load_value(m.val, m.val_kind, home.from + i);   // asked for before the search, not behind it
+            pos = rank_in(indices + other.from, other.len, c);
+            match = pos < other.len && (long long)indices[other.from + pos] == c;
+        }
+        const unsigned long long mask = __ballot(match);
+        if (active && (first || !match)) {
+            const int64_t before = carry + __popcll(mask & ((1ull << lane) - 1ull));
+            const int64_t o = out + i + pos - before;   // < out + the row's length: the entries below this one, counted once
+            if (first && match) v += (int32_t)load_value(m.val, m.val_kind, other.from + pos);
+            out_indices[o] = (int32_t)c;
+            out_values[o] = v;
+        }
+        carry += __popcll(mask);
+    }
+}
+
+template <typename I>
+__global__ __launch_bounds__(DB_THREADS) void doublet_fill_kernel(Matrix m, const int32_t *__restrict__ parents, int64_t n_pairs,
+                                                                  const int64_t *__restrict__ out_indptr,
+                                                                  int32_t *__restrict__ out_indices, int32_t *__restrict__ out_values)
+{
+    const I *const indices = static_cast<const I *>(m.indices);
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (DB_THREADS / 64);
+    for (int64_t s = blockIdx.x * (int64_t)(DB_THREADS / 64) + (threadIdx.x >> 6); s < n_pairs; s += waves) {
+        const Row A = row_of(m, parents[2 * s]), B = row_of(m, parents[2 * s + 1]);
+        const int64_t out = out_indptr[s];
+        doublet_place<I, true>(m, indices, A, B, lane, out, out_indices, out_values);
+        doublet_place<I, false>(m, indices, B, A, lane, out, out_indices, out_values);
+    }
+}
+
+unsigned grid_for(int64_t n, int per_block)
+{
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 1 << 20));
+}
+
+void use_device(int device)
+{
+    int n = 0;
+    HIPCHK(hipGetDeviceCount(&n));
+    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
+    HIPCHK(hipSetDevice(device));
+}
+
+hipStream_t pick_stream(void *stream, std::unique_ptr<TempStream> &own)
+{
+    // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
+    if (!stream) {
+        own.reset(new TempStream);
+        return own->st;
+    }
+    return stream == SCHPF_STREAM_DEFAULT ? nullptr : (hipStream_t)stream;
+}
+
+#define LAUNCH(kernel, n, per_block, st, ...)                                                               \
+    do {                                                                                                    \
+        hipLaunchKernelGGL(kernel, dim3(grid_for(n, per_block)), dim3(DB_THREADS), 0, st, __VA_ARGS__);     \
+        HIPCHK(hipGetLastError());                                                                          \
+    } while (0)
+
+void parents_on_device(hipStream_t st, int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed, int32_t *parents)
+{
+    LAUNCH(doublet_parents_kernel, n_sim, DB_THREADS, st, (uint64_t)first, n_sim, (uint32_t)ncells, (uint32_t)seed,
+           (uint32_t)(seed >> 32), parents);
+    HIPCHK(hipStreamSynchronize(st));
+}
+
+// Everything on `st`, which is synchronised when this returns; all pointers are device memory, nnz and n_pairs are at least 1.
+// The checks come first, indptr before anything that follows it into the entries: a refused call has written nothing.
+// Returns the entries of the result; out_indices == nullptr: out_indptr alone is written
+int64_t rows_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_t n_pairs, const int32_t *parents, int64_t *out_indptr,
+                       int32_t *out_indices, int32_t *out_values, int64_t capacity)
+{
+    const int per_wave = DB_THREADS / 64;
+    DevBuf d_words, len, temp;
+    d_words.alloc(W_COUNT * sizeof(unsigned long long));
+    unsigned long long *const words = d_words.as<unsigned long long>();
+    unsigned long long h[W_COUNT];
+    HIPCHK(hipMemsetAsync(words, 0xFF, W_COUNT * sizeof(unsigned long long), st));   // NONE
+    LAUNCH(doublet_indptr_kernel, m.ncells + 1, DB_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, words);
+    d2h(h, d_words, sizeof h, st);
+    if (h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(doublet_bad_indptr((int64_t)h[W_BAD_INDPTR]));
+    LAUNCH(doublet_entries_kernel, m.ncells, per_wave, st, m, words);
+    LAUNCH(doublet_pairs_kernel, n_pairs, DB_THREADS, st, parents, n_pairs, m.ncells, words);
+    d2h(h, d_words, sizeof h, st);
+    if (h[W_BAD_INDEX] != NONE) throw std::invalid_argument(doublet_bad_index((int64_t)h[W_BAD_INDEX]));
+    if (h[W_BAD_ORDER] != NONE) throw std::invalid_argument(doublet_bad_order((int64_t)h[W_BAD_ORDER]));
+    if (h[W_BAD_VALUE] != NONE) throw std::invalid_argument(doublet_bad_value((int64_t)h[W_BAD_VALUE]));
+    if (h[W_BAD_PARENT] != NONE) throw std::invalid_argument(doublet_bad_parent((int64_t)h[W_BAD_PARENT]));
+
+    const bool wide = m.idx_kind == SCHPF_IDX_I64;
+    len.alloc((size_t)(n_pairs + 1) * sizeof(int64_t));
+    if (wide) LAUNCH(doublet_length_kernel<long long>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
+    else LAUNCH(doublet_length_kernel<int>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
+    size_t bytes = 0;
+    HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, len.as<int64_t>(), out_indptr, (int64_t)0, (size_t)(n_pairs + 1),
+                                   rocprim::plus<int64_t>(), st));
+    temp.alloc(bytes);
+    HIPCHK(rocprim::exclusive_scan(temp.p, bytes, len.as<int64_t>(), out_indptr, (int64_t)0, (size_t)(n_pairs + 1),
+                                   rocprim::plus<int64_t>(), st));
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, out_indptr + n_pairs, sizeof total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (!out_indices) return total;
+    if (capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+    if (total > 0) {
+        if (wide) LAUNCH(doublet_fill_kernel<long long>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
+        else LAUNCH(doublet_fill_kernel<int>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
+    }
+    HIPCHK(hipStreamSynchronize(st));   // before the scratch is released
+    return total;
+}
+
+size_t value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
+
+}  // namespace
+}  // namespace schpf
+
+using namespace schpf;
+
+extern "C" {
+
+int schpf_doublet_parents_device(int device, void *stream, int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed,
+                                 int32_t *parents)
+{
+    if (const char *why = doublet_parents_bad_args(first, n_sim, ncells, parents)) return fail("%s", why);
+    return guarded([&] {
+        use_device(device);
+        if (n_sim == 0) return;
+        std::unique_ptr<TempStream> own;
+        parents_on_device(pick_stream(stream, own), first, n_sim, ncells, seed, parents);
+    });
+}
+
+int schpf_doublet_rows_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const void *indptr,
+                              int indptr_kind, const void *indices, int idx_kind, const void *val, int val_kind, int64_t n_pairs,
+                              const int32_t *parents, int64_t *out_indptr, int32_t *out_indices, int32_t *out_values,
+                              int64_t capacity)
+{
+    if (const char *why = doublet_rows_bad_args(ncells, ngenes, nnz, indptr, indices, val, n_pairs, parents, out_indptr, out_indices,
+                                                out_values, capacity))
+        return fail("%s", why);
+    return guarded([&] {
+        if (doublet_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        use_device(device);
+        std::unique_ptr<TempStream> own;
+        if (n_pairs == 0 || nnz == 0) {   // every row of the result is empty: no input is read
+            if (!out_indptr) return;
+            hipStream_t st = pick_stream(stream, own);
+            HIPCHK(hipMemsetAsync(out_indptr, 0, (size_t)(n_pairs + 1) * sizeof(int64_t), st));
+            HIPCHK(hipStreamSynchronize(st));
+            return;
+        }
+        const Matrix m{ncells, ngenes, indptr, indices, val, indptr_kind, idx_kind, val_kind};
+        rows_on_device(pick_stream(stream, own), m, nnz, n_pairs, parents, out_indptr, out_indices, out_values, capacity);
+    });
+}
+
+int schpf_doublet_rows(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                       const void *val, int val_kind, int64_t n_pairs, const int32_t *parents, int64_t *out_indptr,
+                       int32_t *out_indices, int32_t *out_values, int64_t capacity)
+{
+    if (const char *why = doublet_rows_bad_args(ncells, ngenes, nnz, indptr, indices, val, n_pairs, parents, out_indptr, out_indices,
+                                                out_values, capacity))
+        return fail("%s", why);
+    return guarded([&] {
+        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        use_device(device);
+        if (n_pairs == 0 || nnz == 0) {
+            if (out_indptr) std::fill(out_indptr, out_indptr + n_pairs + 1, (int64_t)0);
+            return;
+        }
+        TempStream ts;
+        DevBuf d_indptr, d_indices, d_val, d_parents, d_out_indptr, d_out_indices, d_out_values;
+        h2d<int64_t>(d_indptr, indptr, (size_t)ncells + 1, ts.st);
+        h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);
+        h2d<char>(d_val, val, (size_t)nnz * value_size(val_kind), ts.st);
+        h2d<int32_t>(d_parents, parents, (size_t)n_pairs * 2, ts.st);
+        d_out_indptr.alloc((size_t)(n_pairs + 1) * sizeof(int64_t));
+        if (out_indices) {
+            d_out_indices.alloc((size_t)capacity * sizeof(int32_t));
+            d_out_values.alloc((size_t)capacity * sizeof(int32_t));
+        }
+        const Matrix m{ncells, ngenes, d_indptr.p, d_indices.p, d_val.p, SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind};
+        const int64_t total = rows_on_device(ts.st, m, nnz, n_pairs, d_parents.as<int32_t>(), d_out_indptr.as<int64_t>(),
+                                             out_indices ? d_out_indices.as<int32_t>() : nullptr,
+                                             out_indices ? d_out_values.as<int32_t>() : nullptr, capacity);
+        if (out_indices && total > 0) {
+            HIPCHK(hipMemcpyAsync(out_indices, d_out_indices.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ts.st));
+            HIPCHK(hipMemcpyAsync(out_values, d_out_values.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, ts.st));
+        }
+        d2h(out_indptr, d_out_indptr, (size_t)(n_pairs + 1) * sizeof(int64_t), ts.st);
+    });
+}
+
+}  // extern "C"

@@ -1,7 +1,8 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
 // check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
-// (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip) and of the rank sums
-// (rank_sums.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
+// (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the rank sums
+// (rank_sums.hip) and of the simulated doublets (doublets.hip) with the draw of their parents, and the SCHPF_BACKTRACE
+// crash handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -12,6 +13,7 @@
 #include <thread>
 
 #include "common.h"
+#include "doublets.h"
 #include "philox.h"
 #include "policy.h"
 #include "special.h"
@@ -667,6 +669,80 @@ int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const i
         std::copy(tie.begin(), tie.end(), ties);
         std::copy(expr.begin(), expr.end(), nexpr);
         std::copy(r.begin(), r.end(), rank2);
+    });
+}
+
+// the draw of doublets.h, one simulated row after the other: row first + t for t < n_sim
+int schpf_doublet_parents(int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed, int32_t *parents)
+{
+    if (const char *why = doublet_parents_bad_args(first, n_sim, ncells, parents)) return fail("%s", why);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int64_t t = 0; t < n_sim; ++t)
+        doublet_parents_of((uint64_t)first + (uint64_t)t, (uint32_t)ncells, k0, k1, parents + 2 * t, parents + 2 * t + 1);
+    return 0;
+}
+
+// doublets.hip restated: the same refusals in the same order, then every pair as a two-pointer merge of its parents
+int schpf_debug_doublet_rows(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                             const void *val, int val_kind, int64_t n_pairs, const int32_t *parents, int64_t *out_indptr,
+                             int32_t *out_indices, int32_t *out_values, int64_t capacity)
+{
+    if (const char *why = doublet_rows_bad_args(ncells, ngenes, nnz, indptr, indices, val, n_pairs, parents, out_indptr, out_indices,
+                                                out_values, capacity))
+        return fail("%s", why);
+    return guarded([&] {
+        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (n_pairs == 0 || nnz == 0) {
+            if (out_indptr) std::fill(out_indptr, out_indptr + n_pairs + 1, (int64_t)0);
+            return;
+        }
+        for (int64_t r = 0; r <= ncells; ++r)
+            if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
+                throw std::invalid_argument(doublet_bad_indptr(r));
+        int64_t bad_index = -1, bad_order = -1, bad_value = -1;
+        for (int64_t r = 0; r < ncells; ++r)
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
+                if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
+                if (schpf::thin_value_bad(read_count(val, val_kind, e)) && bad_value < 0) bad_value = e;
+            }
+        if (bad_index >= 0) throw std::invalid_argument(doublet_bad_index(bad_index));
+        if (bad_order >= 0) throw std::invalid_argument(doublet_bad_order(bad_order));
+        if (bad_value >= 0) throw std::invalid_argument(doublet_bad_value(bad_value));
+        for (int64_t s = 0; s < n_pairs; ++s)
+            if (parents[2 * s] < 0 || parents[2 * s] >= ncells || parents[2 * s + 1] < 0 || parents[2 * s + 1] >= ncells)
+                throw std::invalid_argument(doublet_bad_parent(s));
+
+        // the lengths first: out_indptr is written, the entries only where the capacity will do
+        std::vector<int64_t> ptr((size_t)n_pairs + 1, 0);
+        for (int64_t s = 0; s < n_pairs; ++s) {
+            int64_t i = indptr[parents[2 * s]], j = indptr[parents[2 * s + 1]], n = 0;
+            const int64_t i_end = indptr[parents[2 * s] + 1], j_end = indptr[parents[2 * s + 1] + 1];
+            while (i < i_end && j < j_end) {
+                const int32_t ci = indices[i], cj = indices[j];
+                i += ci <= cj;
+                j += cj <= ci;
+                ++n;
+            }
+            ptr[(size_t)s + 1] = ptr[(size_t)s] + n + (i_end - i) + (j_end - j);
+        }
+        const int64_t total = ptr[(size_t)n_pairs];
+        std::copy(ptr.begin(), ptr.end(), out_indptr);
+        if (out_indices && capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+        if (!out_indices) return;
+        for (int64_t s = 0; s < n_pairs; ++s) {
+            int64_t i = indptr[parents[2 * s]], j = indptr[parents[2 * s + 1]], o = ptr[(size_t)s];
+            const int64_t i_end = indptr[parents[2 * s] + 1], j_end = indptr[parents[2 * s + 1] + 1];
+            while (i < i_end || j < j_end) {
+                const bool take_a = i < i_end && (j == j_end || indices[i] <= indices[j]);
+                const bool take_b = j < j_end && (i == i_end || indices[j] <= indices[i]);
+                out_indices[o] = take_a ? indices[i] : indices[j];
+                out_values[o] = (take_a ? (int32_t)read_count(val, val_kind, i) : 0) + (take_b ? (int32_t)read_count(val, val_kind, j) : 0);
+                i += take_a;
+                j += take_b;
+                ++o;
+            }
+        }
     });
 }
 

@@ -342,6 +342,16 @@ class scHPF(BaseEstimator):
             labels = self.clusters(k=k, metric=metric, method=method, resolution=resolution, device=kwargs.get("device"))
         return rank_genes_groups(X, labels, **kwargs)
 
+    def doublets(self, X, **kwargs):
+        """Scrublet's doublet score of every cell of the count matrix X (cells x genes, what `fit` took) under this model:
+        simulated doublets -- sums of random pairs of rows of X, made on the GPU -- are projected onto the frozen gene
+        factors together with the cells, and a cell is scored by the simulated rows among its nearest neighbours.  The dict
+        of schpf_amd.doublet_scores (scores, se, k_sim, scores_sim, ...; kwargs go there: ratio, expected_rate, k, seed,
+        threshold, device and what `project` takes).  Run it before `clusters` and `markers`.  An addition to the
+        reference's surface."""
+        from .doublets import doublet_scores
+        return doublet_scores(self, X, **kwargs)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
