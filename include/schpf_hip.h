@@ -551,6 +551,65 @@ int schpf_debug_doublet_rows(int64_t ncells, int64_t ngenes, int64_t nnz, const 
                              const void *val, int val_kind, int64_t n_pairs, const int32_t *parents, int64_t *out_indptr,
                              int32_t *out_indices, int32_t *out_values, int64_t capacity);
 
+/* Cell and gene filtering: the sums a quality filter asks of a count matrix, and X[rows][:, kept genes].
+ * Integer work whose result is fully determined: every schedule gives the same bits.
+ * Axis statistics.  Input: a CSR matrix of ncells x ngenes with nnz stored entries, as schpf_doublet_rows takes it: indptr 0 at
+ *   row 0, non-decreasing, ending at nnz; the columns in [0, ngenes) and strictly ascending within a row; every value an
+ *   integer count in [0, 2^24].  gene_flags uint32[ngenes]: bit s is set where gene j belongs to gene set s, 0 <= n_sets <= 32;
+ *   with n_sets == 0, gene_flags and cell_set_total may be NULL.  All outputs int64:
+ *     cell_n[i]      the stored entries of row i with a value > 0 (a stored zero is no expression)
+ *     cell_total[i]  their sum
+ *     cell_set_total[s * ncells + i]  the sum of the entries of row i whose gene has bit s
+ *     gene_n[j], gene_total[j]  the same per column;  gene_sumsq[j]  the sum of the squared values of column j
+ *   Totals stay below 2^55.  Refused before anything is written, M the smallest offender, in this order:
+ *     "qc: indptr must be 0 at row 0, must be non-decreasing and must end at nnz; offending row M"
+ *     "qc: column index out of range at entry M"
+ *     "qc: columns must be strictly ascending within a row; offending row M"
+ *     "qc: values must be integer counts in [0, 2^24]; offending entry M"
+ *     "qc: sum of squares may overflow: largest value M over N cells"  (M the largest stored value, M^2 * ncells >= 2^63)
+ *   nnz == 0 succeeds without reading the matrix: the outputs are zeros.  Sizes outside [0, 2^31), n_sets outside [0, 32],
+ *   unknown kinds and NULL pointers otherwise are refused.
+ * Submatrix.  Input: a CSR matrix with indptr as above and the columns in [0, ngenes); no order within a row is asked,
+ *   duplicates may occur, and the values are not interpreted.  rows int32[n_rows]: row numbers in [0, ncells), in any order,
+ *   repeats allowed; NULL: the rows 0 .. ncells - 1, and n_rows must be ncells.  gene_keep uint8[ngenes]: gene j is kept where
+ *   gene_keep[j] != 0; NULL keeps every gene.  The kept genes are renumbered in ascending order; *out_ngenes (a HOST pointer
+ *   in all three entry points) is their number.  Row r of the result holds the entries of row rows[r] whose gene is kept, in
+ *   their stored order, the columns renumbered, the bytes of the values unchanged (-0.0, NaN payloads and stored zeros
+ *   survive).  out_indptr int64[n_rows + 1], out_indices int32, out_values of val_kind.  With out_indices == NULL and
+ *   out_values == NULL only *out_ngenes and out_indptr are written: the caller reads out_indptr[n_rows], allocates, and calls
+ *   again with capacity = the entries the two arrays hold.  Every call validates afresh.
+ *   Refused before anything is written, M the smallest offender, in this order: the indptr and the column range as above,
+ *     "qc: rows must be in [0, ncells); offending position M"
+ *     "capacity must be at least the T entries of the result, got C"
+ *   nnz == 0 or n_rows == 0: the matrix is not read and out_indptr is zeros; gene_keep is still counted and rows checked.
+ * _device: indptr (of indptr_kind), indices (of idx_kind: SCHPF_IDX_*), val (of val_kind), gene_flags, rows, gene_keep and the
+ *   outputs but out_ngenes are DEVICE pointers on `device`, read and written in place; stream as in
+ *   schpf_thin_counts_device; synchronised before the call returns.  Scratch: the submatrix 16 (n_rows + 1) + 8 (ngenes + 1)
+ *   bytes and the scans' own, the statistics a few words.
+ * schpf_axis_stats, schpf_submatrix: host pointers (int64 indptr, int32 indices), staged through the device; the same result.
+ * schpf_debug_axis_stats, schpf_debug_submatrix: test hooks (host only, no GPU needed): the serial restatements, one entry
+ *   after the other, which the others must match bit for bit. */
+int schpf_axis_stats_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const void *indptr,
+                            int indptr_kind, const void *indices, int idx_kind, const void *val, int val_kind, int n_sets,
+                            const uint32_t *gene_flags, int64_t *cell_n, int64_t *cell_total, int64_t *cell_set_total,
+                            int64_t *gene_n, int64_t *gene_total, int64_t *gene_sumsq);
+int schpf_axis_stats(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                     const void *val, int val_kind, int n_sets, const uint32_t *gene_flags, int64_t *cell_n, int64_t *cell_total,
+                     int64_t *cell_set_total, int64_t *gene_n, int64_t *gene_total, int64_t *gene_sumsq);
+int schpf_debug_axis_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                           const void *val, int val_kind, int n_sets, const uint32_t *gene_flags, int64_t *cell_n,
+                           int64_t *cell_total, int64_t *cell_set_total, int64_t *gene_n, int64_t *gene_total, int64_t *gene_sumsq);
+int schpf_submatrix_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const void *indptr,
+                           int indptr_kind, const void *indices, int idx_kind, const void *val, int val_kind, int64_t n_rows,
+                           const int32_t *rows, const uint8_t *gene_keep, int64_t *out_ngenes, int64_t *out_indptr,
+                           int32_t *out_indices, void *out_values, int64_t capacity);
+int schpf_submatrix(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                    const void *val, int val_kind, int64_t n_rows, const int32_t *rows, const uint8_t *gene_keep,
+                    int64_t *out_ngenes, int64_t *out_indptr, int32_t *out_indices, void *out_values, int64_t capacity);
+int schpf_debug_submatrix(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                          const void *val, int val_kind, int64_t n_rows, const int32_t *rows, const uint8_t *gene_keep,
+                          int64_t *out_ngenes, int64_t *out_indptr, int32_t *out_indices, void *out_values, int64_t capacity);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

@@ -13,6 +13,7 @@ from .thinning import thin_counts
 from .neighbors import knn, knn_graph, knn_connectivities, louvain, modularity
 from .markers import rank_sums, rank_genes_groups
 from .doublets import simulate_doublets, doublet_scores
+from .qc import qc_metrics, submatrix, filter_counts
 
 # make the pickle module path of the classes (schpf.scHPF_) resolvable
 import schpf.scHPF_  # noqa: E402,F401
@@ -20,4 +21,4 @@ import schpf.scHPF_  # noqa: E402,F401
 __all__ = ["__version__", "hpf_hip", "loss", "preprocessing", "DeviceCAVI", "HPF_Gamma", "scHPF", "load_model",
            "save_model", "combine_across_cells", "run_trials", "run_trials_pool", "thin_counts", "knn", "knn_graph",
            "knn_connectivities", "louvain", "modularity", "rank_sums", "rank_genes_groups", "simulate_doublets",
-           "doublet_scores"]
+           "doublet_scores", "qc_metrics", "submatrix", "filter_counts"]

@@ -100,6 +100,12 @@ SIGNATURES = {
     "schpf_doublet_rows_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
     "schpf_doublet_rows": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
     "schpf_debug_doublet_rows": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
+    "schpf_axis_stats_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "schpf_axis_stats": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "schpf_debug_axis_stats": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "schpf_submatrix_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _i64, _vp, _vp, _i64p, _vp, _vp, _vp, _i64],
+    "schpf_submatrix": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _i64p, _vp, _vp, _vp, _i64],
+    "schpf_debug_submatrix": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _i64p, _vp, _vp, _vp, _i64],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_choose_config": [_int, _int, _int, ctypes.POINTER(_int)],
@@ -237,7 +243,7 @@ def check(status):
     if status != 0:
         msg = load().schpf_last_error().decode("utf-8", "replace")
         if status != ERR_NO_MEMORY and ("must be" in msg or "out of range" in msg or "unknown" in msg
-                                        or "thinning needs" in msg or "neighbour lists must hold" in msg):
+                                        or "thinning needs" in msg or "neighbour lists must hold" in msg or "may overflow" in msg):
             raise ValueError(msg)
         raise SchpfHipError(msg, status)
 

@@ -1,4 +1,4 @@
-"""`scHPF prep | prep-like | train | train-pool | score | project`: command-line entry points over
+"""`scHPF prep | prep-like | train | train-pool | score | project | qc`: command-line entry points over
 the loaders, run_trials and the model methods -- argument plumbing only, no logic of its own.
 
 Same sub-commands, options, defaults and output file names as the reference's script
@@ -168,6 +168,23 @@ def _parser():
     proj.add_argument("--min-iter", type=int, default=10, help="[10]")
     proj.add_argument("--epsilon", type=float, default=0.001, help="[0.001]")
     proj.add_argument("--check-freq", type=int, default=10, help="[10]")
+
+    qc = sub.add_parser("qc", help="Per-cell and per-gene quality sums of a count matrix, and optionally the filtered "
+                                   "matrix (this build's addition).")
+    qc.add_argument("-i", "--input", required=True, help="The count matrix (same formats as `train -i`).")
+    qc.add_argument("-o", "--outdir", help="Output directory (created if missing; default: the input's).")
+    qc.add_argument("-p", "--prefix", default="", help="Prefix for output files.")
+    qc.add_argument("--min-cells", type=float, default=0, metavar="M",
+                    help="Keep genes observed in at least this many cells; a value in (0, 1) is a proportion of the cells. [0]")
+    qc.add_argument("--min-genes", type=int, default=0, metavar="G", help="Keep cells with at least this many genes observed. [0]")
+    qc.add_argument("--min-counts", type=int, default=0, metavar="C", help="Keep cells with at least this many counts. [0]")
+    qc.add_argument("--max-counts", type=int, default=None, metavar="C", help="Keep cells with at most this many counts.")
+    qc.add_argument("--gene-set", action="append", default=[], metavar="NAME=FILE",
+                    help="A gene set whose counts are summed per cell (a column of cell_qc.txt): FILE holds one 0-based gene "
+                         "index per line.  May be given up to 32 times.")
+    qc.add_argument("--write-filtered", default=False, action="store_true",
+                    help="Also write the filtered matrix (filtered.mtx) and the 0-based indices of the cells and genes it "
+                         "keeps (kept_cells.txt, kept_genes.txt).")
     return parser
 
 
@@ -419,6 +436,39 @@ def _project(args, outprefix):
     _write_args(args, "{}project_commandline_args.json".format(outprefix))
 
 
+def _qc(args, outprefix):
+    from .qc import filter_counts
+    print("Loading data.....")
+    data = _load_matrix(args.input)
+    gene_sets = {}
+    for spec in args.gene_set:
+        name, sep, path = spec.partition("=")
+        if not sep or not name or not path:
+            raise ValueError("--gene-set takes NAME=FILE, got {}".format(spec))
+        gene_sets[name] = np.loadtxt(path, dtype=np.int64, ndmin=1)
+    print("Computing quality sums.....")
+    filtered, cell_keep, gene_keep, found = filter_counts(data, min_cells=args.min_cells, min_genes=args.min_genes,
+                                                          min_counts=args.min_counts, max_counts=args.max_counts,
+                                                          gene_sets=gene_sets)
+    names = list(gene_sets)
+    np.savetxt(outprefix + "cell_qc.txt",
+               np.stack([found["cell_n_genes"], found["cell_total"]] + [found["cell_set_total"][n] for n in names], axis=1),
+               fmt="%d", delimiter="\t", header="\t".join(["n_genes", "total"] + names), comments="")
+    with open(outprefix + "gene_qc.txt", "w") as fh:
+        fh.write("n_cells\ttotal\tsumsq\tmean\tvar\n")
+        for j in range(len(found["gene_n_cells"])):
+            fh.write("{}\t{}\t{}\t{!r}\t{!r}\n".format(found["gene_n_cells"][j], found["gene_total"][j], found["gene_sumsq"][j],
+                                                     float(found["gene_mean"][j]), float(found["gene_var"][j])))
+    print(".....{} of {} cells and {} of {} genes pass".format(int(cell_keep.sum()), len(cell_keep), int(gene_keep.sum()),
+                                                                len(gene_keep)))
+    if args.write_filtered:
+        print("Writing filtered data to file.....")
+        _write_matrix(outprefix + "filtered.mtx", filtered)
+        np.savetxt(outprefix + "kept_cells.txt", np.flatnonzero(cell_keep), fmt="%d")
+        np.savetxt(outprefix + "kept_genes.txt", np.flatnonzero(gene_keep), fmt="%d")
+    _write_args(args, "{}qc_commandline_args.json".format(outprefix))
+
+
 def main(argv=None):
     parser = _parser()
     args = parser.parse_args(argv)
@@ -426,7 +476,7 @@ def main(argv=None):
         parser.print_help(sys.stderr)
         return 1
     if args.outdir is None:     # the reference's defaults (bin/scHPF:305-311)
-        if args.cmd in ("prep", "prep-like", "train", "train-pool"):
+        if args.cmd in ("prep", "prep-like", "train", "train-pool", "qc"):
             args.outdir = args.input.rsplit("/", 1)[0] if "/" in args.input else "."
         elif args.cmd == "project":
             args.outdir = args.model.rsplit("/", 1)[0] if "/" in args.model else "."
@@ -438,7 +488,7 @@ def main(argv=None):
     prefix = args.prefix.rstrip(".") + "." if args.prefix else ""
     outprefix = args.outdir + "/" + prefix
     {"prep": _prep, "prep-like": _prep_like, "train": _train, "train-pool": _train, "score": _score,
-     "project": _project}[args.cmd](args, outprefix)
+     "project": _project, "qc": _qc}[args.cmd](args, outprefix)
     return 0
 
 

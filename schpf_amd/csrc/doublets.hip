@@ -25,6 +25,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "common.h"
+#include "csr_device.h"
 #include "doublets.h"
 
 namespace schpf {
@@ -35,30 +36,6 @@ constexpr int DOUBLET_PIECE = 64;   // entries of a parent per pass of a wavefro
 constexpr unsigned long long NONE = ~0ull;
 // the smallest offenders, in device memory, in the order they are reported
 enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_PARENT, W_COUNT };
-
-__device__ __forceinline__ long long load_index(const void *p, int kind, int64_t j)
-{
-    return kind == SCHPF_IDX_I64 ? static_cast<const long long *>(p)[j] : (long long)static_cast<const int *>(p)[j];
-}
-// entry j of a value array of kind SCHPF_VAL_* (common.h read_count)
-__device__ __forceinline__ double load_value(const void *p, int kind, int64_t j)
-{
-    switch (kind) {
-    case SCHPF_VAL_I32: return (double)static_cast<const int *>(p)[j];
-    case SCHPF_VAL_I64: return (double)static_cast<const long long *>(p)[j];
-    case SCHPF_VAL_F32: return (double)static_cast<const float *>(p)[j];
-    default: return static_cast<const double *>(p)[j];
-    }
-}
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(DB_THREADS) void doublet_parents_kernel(uint64_t first, int64_t n_sim, uint32_t N, uint32_t k0,
                                                                      uint32_t k1, int32_t *__restrict__ parents)
@@ -84,12 +61,6 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_indptr_kernel(const void *
     bad = wave_min(bad);
     if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_INDPTR, bad);
 }
-
-struct Matrix {   // a CSR in device memory whose indptr has been checked: every row lies in [0, nnz)
-    int64_t ncells, ngenes;
-    const void *indptr, *indices, *val;
-    int indptr_kind, idx_kind, val_kind;
-};
 
 __global__ __launch_bounds__(DB_THREADS) void doublet_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
 {
@@ -138,15 +109,6 @@ template <typename I> __device__ __forceinline__ int64_t rank_in(const I *__rest
         else hi = mid;
     }
     return lo;
-}
-
-struct Row {
-    int64_t from, len;
-};
-__device__ __forceinline__ Row row_of(const Matrix &m, int64_t r)
-{
-    const int64_t from = load_index(m.indptr, m.indptr_kind, r);
-    return Row{from, load_index(m.indptr, m.indptr_kind, r + 1) - from};
 }
 
 // len[s] = the stored columns of parent a or parent b; len[n_pairs] = 0, the scan's last input.  The shorter parent is
@@ -229,29 +191,6 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_fill_kernel(Matrix m, cons
     }
 }
 
-unsigned grid_for(int64_t n, int per_block)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 1 << 20));
-}
-
-void use_device(int device)
-{
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
-    HIPCHK(hipSetDevice(device));
-}
-
-hipStream_t pick_stream(void *stream, std::unique_ptr<TempStream> &own)
-{
-    // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
-    if (!stream) {
-        own.reset(new TempStream);
-        return own->st;
-    }
-    return stream == SCHPF_STREAM_DEFAULT ? nullptr : (hipStream_t)stream;
-}
-
 #define LAUNCH(kernel, n, per_block, st, ...)                                                               \
     do {                                                                                                    \
         hipLaunchKernelGGL(kernel, dim3(grid_for(n, per_block)), dim3(DB_THREADS), 0, st, __VA_ARGS__);     \
@@ -310,8 +249,6 @@ int64_t rows_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_t n_p
     HIPCHK(hipStreamSynchronize(st));   // before the scratch is released
     return total;
 }
-
-size_t value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
 
 }  // namespace
 }  // namespace schpf

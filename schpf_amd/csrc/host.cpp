@@ -1,8 +1,8 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
 // check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
 // (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the rank sums
-// (rank_sums.hip) and of the simulated doublets (doublets.hip) with the draw of their parents, and the SCHPF_BACKTRACE
-// crash handler.  Nothing here touches the device.
+// (rank_sums.hip), of the simulated doublets (doublets.hip) with the draw of their parents and of the axis statistics and
+// the submatrix (qc.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -16,6 +16,7 @@
 #include "doublets.h"
 #include "philox.h"
 #include "policy.h"
+#include "qc.h"
 #include "special.h"
 
 using namespace schpf;
@@ -740,6 +741,105 @@ int schpf_debug_doublet_rows(int64_t ncells, int64_t ngenes, int64_t nnz, const 
                 out_values[o] = (take_a ? (int32_t)read_count(val, val_kind, i) : 0) + (take_b ? (int32_t)read_count(val, val_kind, j) : 0);
                 i += take_a;
                 j += take_b;
+                ++o;
+            }
+        }
+    });
+}
+
+// qc.hip restated: the same refusals in the same order, then one entry after the other
+int schpf_debug_axis_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                           const void *val, int val_kind, int n_sets, const uint32_t *gene_flags, int64_t *cell_n,
+                           int64_t *cell_total, int64_t *cell_set_total, int64_t *gene_n, int64_t *gene_total, int64_t *gene_sumsq)
+{
+    if (const char *why = qc_stats_bad_args(ncells, ngenes, nnz, indptr, indices, val, n_sets, gene_flags, cell_n, cell_total,
+                                            cell_set_total, gene_n, gene_total, gene_sumsq))
+        return fail("%s", why);
+    return guarded([&] {
+        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        const size_t N = (size_t)ncells, J = (size_t)ngenes, S = (size_t)n_sets;
+        if (nnz > 0) {
+            for (int64_t r = 0; r <= ncells; ++r)
+                if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
+                    throw std::invalid_argument(qc_bad_indptr(r));
+            int64_t bad_index = -1, bad_order = -1, bad_value = -1;
+            uint64_t vmax = 0;
+            for (int64_t r = 0; r < ncells; ++r)
+                for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                    if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
+                    if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
+                    const double v = read_count(val, val_kind, e);
+                    if (schpf::thin_value_bad(v)) {
+                        if (bad_value < 0) bad_value = e;
+                    } else {
+                        vmax = std::max(vmax, (uint64_t)v);
+                    }
+                }
+            if (bad_index >= 0) throw std::invalid_argument(qc_bad_index(bad_index));
+            if (bad_order >= 0) throw std::invalid_argument(qc_bad_order(bad_order));
+            if (bad_value >= 0) throw std::invalid_argument(qc_bad_value(bad_value));
+            if (qc_sumsq_overflows(vmax, ncells)) throw std::invalid_argument(qc_bad_sumsq(vmax, ncells));
+        }
+        for (int64_t *p : {cell_n, cell_total}) std::fill(p, p + N, (int64_t)0);
+        if (N && S) std::fill(cell_set_total, cell_set_total + N * S, (int64_t)0);
+        for (int64_t *p : {gene_n, gene_total, gene_sumsq}) std::fill(p, p + J, (int64_t)0);
+        if (nnz == 0) return;
+        for (int64_t r = 0; r < ncells; ++r)
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                const int64_t v = (int64_t)read_count(val, val_kind, e), j = indices[e];
+                if (v == 0) continue;   // a stored zero is no expression
+                ++cell_n[r];
+                cell_total[r] += v;
+                for (int s = 0; s < n_sets; ++s)
+                    if ((gene_flags[j] >> s) & 1u) cell_set_total[(size_t)s * N + (size_t)r] += v;
+                ++gene_n[j];
+                gene_total[j] += v;
+                gene_sumsq[j] += v * v;
+            }
+    });
+}
+
+int schpf_debug_submatrix(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                          const void *val, int val_kind, int64_t n_rows, const int32_t *rows, const uint8_t *gene_keep,
+                          int64_t *out_ngenes, int64_t *out_indptr, int32_t *out_indices, void *out_values, int64_t capacity)
+{
+    if (const char *why = qc_submatrix_bad_args(ncells, ngenes, nnz, indptr, indices, val, n_rows, rows, out_ngenes, out_indptr,
+                                                out_indices, out_values, capacity))
+        return fail("%s", why);
+    return guarded([&] {
+        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        const bool empty = nnz == 0 || n_rows == 0;
+        if (!empty) {
+            for (int64_t r = 0; r <= ncells; ++r)
+                if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
+                    throw std::invalid_argument(qc_bad_indptr(r));
+            for (int64_t e = 0; e < nnz; ++e)
+                if (indices[e] < 0 || indices[e] >= ngenes) throw std::invalid_argument(qc_bad_index(e));
+        }
+        for (int64_t s = 0; rows && s < n_rows; ++s)
+            if (rows[s] < 0 || rows[s] >= ncells) throw std::invalid_argument(qc_bad_rows(s));
+        std::vector<int32_t> colmap((size_t)ngenes + 1, 0);   // the kept genes before gene j
+        for (int64_t j = 0; j < ngenes; ++j) colmap[(size_t)j + 1] = colmap[(size_t)j] + (!gene_keep || gene_keep[j] != 0);
+        std::vector<int64_t> ptr((size_t)n_rows + 1, 0);
+        for (int64_t s = 0; !empty && s < n_rows; ++s) {
+            const int64_t r = rows ? rows[s] : s;
+            int64_t n = 0;
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) n += colmap[(size_t)indices[e] + 1] != colmap[(size_t)indices[e]];
+            ptr[(size_t)s + 1] = ptr[(size_t)s] + n;
+        }
+        const int64_t total = ptr[(size_t)n_rows];
+        if (out_indices && capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+        *out_ngenes = colmap[(size_t)ngenes];
+        std::copy(ptr.begin(), ptr.end(), out_indptr);
+        if (!out_indices || total == 0) return;
+        const size_t width = val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8;
+        for (int64_t s = 0, o = 0; s < n_rows; ++s) {
+            const int64_t r = rows ? rows[s] : s;
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                const size_t j = (size_t)indices[e];
+                if (colmap[j + 1] == colmap[j]) continue;
+                out_indices[o] = colmap[j];
+                std::memcpy((char *)out_values + (size_t)o * width, (const char *)val + (size_t)e * width, width);   // the bytes as they are
                 ++o;
             }
         }

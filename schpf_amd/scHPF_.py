@@ -352,6 +352,16 @@ class scHPF(BaseEstimator):
         from .doublets import doublet_scores
         return doublet_scores(self, X, **kwargs)
 
+    @staticmethod
+    def qc(X, gene_sets=None, **kwargs):
+        """The sums a quality filter asks of the count matrix X (cells x genes) before a fit, on the GPU: the dict of
+        schpf_amd.qc_metrics (cell_n_genes, cell_total, cell_set_total, gene_n_cells, gene_total, gene_sumsq, gene_mean,
+        gene_var; kwargs go there: device).  `schpf_amd.filter_counts` applies thresholds to them and
+        `schpf_amd.submatrix(X, cells=~calls)` takes the doublets `doublets` called out of X for a refit.  An addition to
+        the reference's surface."""
+        from .qc import qc_metrics
+        return qc_metrics(X, gene_sets=gene_sets, **kwargs)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
