@@ -610,6 +610,45 @@ int schpf_debug_submatrix(int64_t ncells, int64_t ngenes, int64_t nnz, const int
                           const void *val, int val_kind, int64_t n_rows, const int32_t *rows, const uint8_t *gene_keep,
                           int64_t *out_ngenes, int64_t *out_indptr, int32_t *out_indices, void *out_values, int64_t capacity);
 
+/* Pseudobulk: per group of cells and gene, the cells that express the gene, the sum of their counts and the
+ * sum of the squares.  Integer work whose result is fully determined: every schedule gives the same bits.
+ * Input: the canonical count CSR that schpf_axis_stats takes -- indptr 0 at row 0, non-decreasing, ending at nnz; the columns
+ *   in [0, ngenes) and strictly ascending within a row; every value an integer count in [0, 2^24]; a stored zero counts as a
+ *   zero.  labels int32[ncells] in [-1, ngroups): the group of every cell, -1 for a cell in no group.  ngroups >= 1.
+ *   All outputs int64, row-major, written in full (zeros where nothing falls):
+ *     group_cells[g]            the cells with label g
+ *     nexpr[g * ngenes + j]     the cells of group g whose entry of gene j is > 0
+ *     total[g * ngenes + j]     the sum of those entries
+ *     sumsq[g * ngenes + j]     the sum of their squares; sumsq may be NULL: then it is neither computed nor checked for overflow
+ *   Refused before anything is written, M the smallest offender, in this order:
+ *     "group_stats: indptr must be 0 at row 0, must be non-decreasing and must end at nnz; offending row M"
+ *     "group_stats: column index out of range at entry M"
+ *     "group_stats: columns must be strictly ascending within a row; offending row M"
+ *     "group_stats: values must be integer counts in [0, 2^24]; offending entry M"
+ *     "group_stats: labels must be in [-1, ngroups); offending cell M"
+ *     "group_stats: sum of squares may overflow: largest value M over N cells"  (where sumsq is given; M the largest stored
+ *       value, M^2 * ncells >= 2^63: a group holds at most ncells cells)
+ *   nnz == 0 succeeds without reading the matrix: the labels are still checked, group_cells is counted, the rest is zeros.
+ *   Sizes outside [0, 2^31), ngroups outside [1, 2^31), ngroups * ngenes >= 2^31, unknown kinds and NULL pointers otherwise
+ *   are refused.
+ * _device: indptr (of indptr_kind), indices (of idx_kind: SCHPF_IDX_*), val (of val_kind), labels and the outputs are DEVICE
+ *   pointers on `device`, read and written in place; stream as in schpf_thin_counts_device; synchronised before the call
+ *   returns.  Scratch: 16 ncells + 24 (ngroups + 1) bytes, 12 bytes per slab of 2048 cells of one group (at most
+ *   ncells / 2048 + min(ngroups, ncells) slabs), the radix sort's and the scan's own, and a few words.
+ * schpf_group_stats: host pointers (int64 indptr, int32 indices), staged through the device; the same result.
+ * schpf_debug_group_stats: test hook (host only, no GPU needed): the serial restatement, one entry after the other, which
+ *   the others must match bit for bit. */
+int schpf_group_stats_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const void *indptr,
+                             int indptr_kind, const void *indices, int idx_kind, const void *val, int val_kind,
+                             const int32_t *labels, int64_t ngroups, int64_t *group_cells, int64_t *nexpr, int64_t *total,
+                             int64_t *sumsq);
+int schpf_group_stats(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                      const void *val, int val_kind, const int32_t *labels, int64_t ngroups, int64_t *group_cells,
+                      int64_t *nexpr, int64_t *total, int64_t *sumsq);
+int schpf_debug_group_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                            const void *val, int val_kind, const int32_t *labels, int64_t ngroups, int64_t *group_cells,
+                            int64_t *nexpr, int64_t *total, int64_t *sumsq);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

@@ -14,6 +14,7 @@ from .neighbors import knn, knn_graph, knn_connectivities, louvain, modularity
 from .markers import rank_sums, rank_genes_groups
 from .doublets import simulate_doublets, doublet_scores
 from .qc import qc_metrics, submatrix, filter_counts
+from .aggregate import group_stats, pseudobulk, group_codes
 
 # make the pickle module path of the classes (schpf.scHPF_) resolvable
 import schpf.scHPF_  # noqa: E402,F401
@@ -21,4 +22,4 @@ import schpf.scHPF_  # noqa: E402,F401
 __all__ = ["__version__", "hpf_hip", "loss", "preprocessing", "DeviceCAVI", "HPF_Gamma", "scHPF", "load_model",
            "save_model", "combine_across_cells", "run_trials", "run_trials_pool", "thin_counts", "knn", "knn_graph",
            "knn_connectivities", "louvain", "modularity", "rank_sums", "rank_genes_groups", "simulate_doublets",
-           "doublet_scores", "qc_metrics", "submatrix", "filter_counts"]
+           "doublet_scores", "qc_metrics", "submatrix", "filter_counts", "group_stats", "pseudobulk", "group_codes"]

@@ -106,6 +106,9 @@ SIGNATURES = {
     "schpf_submatrix_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _i64, _vp, _vp, _i64p, _vp, _vp, _vp, _i64],
     "schpf_submatrix": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _i64p, _vp, _vp, _vp, _i64],
     "schpf_debug_submatrix": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _i64, _vp, _vp, _i64p, _vp, _vp, _vp, _i64],
+    "schpf_group_stats_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp],
+    "schpf_group_stats": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp],
+    "schpf_debug_group_stats": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_choose_config": [_int, _int, _int, ctypes.POINTER(_int)],

@@ -142,6 +142,14 @@ def _parser():
                        help="With -i and --clusters: also write the Wilcoxon rank-sum test of every gene, each cluster "
                             "against all the other cells, as marker_scores.txt and marker_pvals_adj.txt (genes x clusters); "
                             "with --genefile also ranked_markers.txt, the gene names by descending score per cluster.")
+    score.add_argument("--pseudobulk", default=False, action="store_true",
+                       help="With -i and --clusters and / or --sample-ids: also write the counts of every gene summed over the "
+                            "cells of each group as pseudobulk_counts.txt (groups x genes, integers), the groups as "
+                            "pseudobulk_groups.txt (one line per group: its keys and its cell count) and the fraction of "
+                            "expressing cells as pseudobulk_pct.txt.")
+    score.add_argument("--sample-ids", default=None, metavar="FILE",
+                       help="With --pseudobulk: a text file with one sample id per cell; the groups are then sample x cluster "
+                            "(or the samples alone without --clusters).")
     score.add_argument("--doublets", default=False, action="store_true",
                        help="With -i: also write Scrublet's doublet score of every cell, from simulated doublets projected "
                             "onto the model together with the cells (doublet_scores.txt: score, standard error and the "
@@ -313,6 +321,11 @@ def _train(args, outprefix):
 
 def _score(args, outprefix):
     from .util import max_pairwise_table, mean_cellscore_fraction_list
+    if args.pseudobulk and not args.clusters and args.sample_ids is None:    # before anything is loaded or written
+        raise ValueError("--pseudobulk needs groups: the clusters (--knn K --knn-graph M --clusters), --sample-ids FILE, or both")
+    if args.sample_ids is not None and not args.pseudobulk:
+        raise ValueError("--sample-ids belongs to --pseudobulk")
+    labels = sample_ids = None
     print("Loading model.....")
     model = joblib.load(args.model)
     cell_score, gene_score = model.cell_score(), model.gene_score()
@@ -341,6 +354,12 @@ def _score(args, outprefix):
         if tuple(data.shape) != (model.theta.dims[0], model.beta.dims[0]):
             raise ValueError("{} is {} x {}, the model was fitted to {} cells x {} genes".format(
                 args.input, data.shape[0], data.shape[1], model.theta.dims[0], model.beta.dims[0]))
+        if args.sample_ids is not None:
+            with open(args.sample_ids) as fh:
+                sample_ids = np.array([line.rstrip("\r\n") for line in fh], dtype=str)
+            if len(sample_ids) != data.shape[0]:
+                raise ValueError("{} holds {} sample ids, the matrix has {} cells".format(args.sample_ids, len(sample_ids),
+                                                                                         data.shape[0]))
         print("Saving per-cell and per-gene loss.....")
         np.savetxt(outprefix + "cell_loss.txt", ls.cellmean_negative_pois_llh(data, theta=model.theta, beta=model.beta))
         np.savetxt(outprefix + "gene_loss.txt", ls.genemean_negative_pois_llh(data, theta=model.theta, beta=model.beta))
@@ -356,6 +375,8 @@ def _score(args, outprefix):
             raise ValueError("--markers needs the count matrix (-i)")
         if args.doublets:
             raise ValueError("--doublets needs the count matrix (-i)")
+        if args.pseudobulk:
+            raise ValueError("--pseudobulk needs the count matrix (-i)")
         del args.input  # the arguments file of a run without the matrix stays what it was
     if not args.ppc:
         del args.ppc     # ... and so does the arguments file of a run without the check
@@ -400,6 +421,17 @@ def _score(args, outprefix):
         del args.clusters, args.resolution   # ... and without its clusters
     if not args.markers:
         del args.markers                     # ... and without their marker genes
+    if args.pseudobulk:
+        from .aggregate import pseudobulk
+        print("Saving pseudobulk.....")
+        found = pseudobulk(data, tuple(key for key in (sample_ids, labels) if key is not None))
+        np.savetxt(outprefix + "pseudobulk_counts.txt", found["counts"], fmt="%d", delimiter="\t")
+        np.savetxt(outprefix + "pseudobulk_pct.txt", found["pct"], delimiter="\t")
+        with open(outprefix + "pseudobulk_groups.txt", "w") as fh:
+            for keys, n in zip(found["groups"], found["n_cells"]):
+                fh.write("\t".join([str(k) for k in keys] + [str(int(n))]) + "\n")
+    else:
+        del args.pseudobulk, args.sample_ids   # ... or a pseudobulk table
     if args.doublets:
         from .doublets import doublet_scores
         print("Saving doublet scores.....")

@@ -1,12 +1,16 @@
-// What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip): the loaders for the
-// index and value kinds of include/schpf_hip.h, the matrix record, the wavefront minimum of the validation kernels, and
-// the device / stream / grid choices of an entry point.
+// What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip, group_stats.hip): the
+// loaders for the index and value kinds of include/schpf_hip.h, the matrix record, the wavefront minimum of the validation
+// kernels, the device / stream / grid choices of an entry point, and -- in csr_checks, for qc.hip and group_stats.hip --
+// the validation of a count CSR: the two kernels, the words of their smallest offenders, and the bisection of a row.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <memory>
 
+#include <rocprim/device/device_scan.hpp>
+
 #include "common.h"
+#include "philox.h"
 
 namespace schpf {
 
@@ -73,5 +77,121 @@ inline hipStream_t pick_stream(void *stream, std::unique_ptr<TempStream> &own)
 }
 
 inline size_t value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
+
+typedef unsigned long long sum_t;   // the int64 outputs as atomicAdd takes them; no sum here is negative
+
+// the first of the n ascending columns at p that is not below `key`
+template <typename I> __device__ __forceinline__ int64_t lower_bound(const I *__restrict__ p, int64_t n, long long key)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((long long)p[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+namespace csr_checks {
+
+constexpr int CSR_THREADS = 256;
+constexpr int CSR_CHECK_BLOCKS = 4096;   // workgroups of csr_entries_kernel at the most: 16 per CU
+constexpr unsigned long long NONE = ~0ull;
+enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_ROW, W_BAD_LABEL, W_VMAX, W_COUNT };
+
+// indptr starts at 0, does not decrease and ends at nnz: the smallest offending row.  Every lane of a wavefront leaves the
+// loop before the reduction: no early return
+static __global__ __launch_bounds__(CSR_THREADS) void csr_indptr_kernel(const void *__restrict__ indptr, int indptr_kind,
+                                                                        int64_t ncells, int64_t nnz,
+                                                                        unsigned long long *__restrict__ words)
+{
+    unsigned long long bad = NONE;
+    for (int64_t r = blockIdx.x * (int64_t)CSR_THREADS + threadIdx.x; r <= ncells; r += (int64_t)gridDim.x * CSR_THREADS) {
+        const long long here = load_index(indptr, indptr_kind, r);
+        const bool wrong = (r == 0 && here != 0) || (r == ncells ? here != nnz : load_index(indptr, indptr_kind, r + 1) < here);
+        if (wrong && (unsigned long long)r < bad) bad = (unsigned long long)r;
+    }
+    bad = wave_min(bad);
+    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_INDPTR, bad);
+}
+
+// A wavefront per row.  counts: the matrix must be canonical and hold counts (the statistics): every column above its left
+// neighbour, every value a count thinning accepts, and the largest value; else only the column range is asked (the submatrix)
+template <bool counts> __global__ __launch_bounds__(CSR_THREADS) void csr_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (CSR_THREADS / 64);
+    unsigned long long bad_index = NONE, bad_order = NONE, bad_value = NONE, vmax = 0;
+    for (int64_t r = blockIdx.x * (int64_t)(CSR_THREADS / 64) + (threadIdx.x >> 6); r < m.ncells; r += waves) {
+        const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
+        for (int64_t e = from + lane; e < to; e += 64) {
+            const long long c = load_index(m.indices, m.idx_kind, e);
+            if ((c < 0 || c >= m.ngenes) && (unsigned long long)e < bad_index) bad_index = (unsigned long long)e;
+            if (!counts) continue;
+            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c && (unsigned long long)r < bad_order)
+                bad_order = (unsigned long long)r;
+            const double v = load_value(m.val, m.val_kind, e);
+            if (thin_value_bad(v)) {
+                if ((unsigned long long)e < bad_value) bad_value = (unsigned long long)e;
+            } else if ((unsigned long long)v > vmax) {
+                vmax = (unsigned long long)v;
+            }
+        }
+    }
+    bad_index = wave_min(bad_index);
+    if (lane == 0 && bad_index != NONE) atomicMin(words + W_BAD_INDEX, bad_index);
+    if (!counts) return;
+    bad_order = wave_min(bad_order);
+    bad_value = wave_min(bad_value);
+    vmax = ~wave_min(~vmax);
+    if (lane == 0) {
+        if (bad_order != NONE) atomicMin(words + W_BAD_ORDER, bad_order);
+        if (bad_value != NONE) atomicMin(words + W_BAD_VALUE, bad_value);
+        // a million wavefronts on one address is what this kernel would wait for: only a value above the one seen goes there
+        if (vmax > __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMax(words + W_VMAX, vmax);
+    }
+}
+
+#define CSR_LAUNCH(kernel, n, per_block, st, ...)                                                                          \
+    do {                                                                                                                   \
+        hipLaunchKernelGGL(kernel, dim3(grid_for(n, per_block)), dim3(schpf::csr_checks::CSR_THREADS), 0, st, __VA_ARGS__); \
+        HIPCHK(hipGetLastError());                                                                                         \
+    } while (0)
+
+struct Words {   // the smallest offenders in device memory, and their copy on the host
+    DevBuf d;
+    unsigned long long h[W_COUNT];
+    unsigned long long *dev() const { return d.as<unsigned long long>(); }
+    void reset(hipStream_t st)
+    {
+        d.alloc(W_COUNT * sizeof(unsigned long long));
+        HIPCHK(hipMemsetAsync(d.p, 0xFF, W_COUNT * sizeof(unsigned long long), st));   // NONE
+        HIPCHK(hipMemsetAsync(dev() + W_VMAX, 0, sizeof(unsigned long long), st));
+    }
+    void fetch(hipStream_t st) { d2h(h, d, sizeof h, st); }
+};
+
+// The two launches; the caller fetches the words and words its own refusals.  The indptr comes first and is fetched before
+// anything follows it into the entries.  A bounded grid for the entries: a wavefront walks many rows and reports once
+inline void launch_indptr_check(hipStream_t st, const Matrix &m, int64_t nnz, Words &w)
+{
+    CSR_LAUNCH(csr_indptr_kernel, m.ncells + 1, CSR_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, w.dev());
+}
+template <bool counts> inline void launch_entries_check(hipStream_t st, const Matrix &m, Words &w)
+{
+    const int per_wave = CSR_THREADS / 64;
+    CSR_LAUNCH(csr_entries_kernel<counts>, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
+}
+
+// out[i] = in[0] + .. + in[i - 1] (rocPRIM); temp is the scan's own scratch
+inline void exclusive_scan(hipStream_t st, DevBuf &temp, const int64_t *in, int64_t *out, size_t n)
+{
+    size_t bytes = 0;
+    HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st));
+    temp.alloc(bytes);
+    HIPCHK(rocprim::exclusive_scan(temp.p, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st));
+}
+
+}  // namespace csr_checks
 
 }  // namespace schpf

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "doublets.h"
+#include "group_stats.h"
 #include "philox.h"
 #include "policy.h"
 #include "qc.h"
@@ -841,6 +842,62 @@ int schpf_debug_submatrix(int64_t ncells, int64_t ngenes, int64_t nnz, const int
                 out_indices[o] = colmap[j];
                 std::memcpy((char *)out_values + (size_t)o * width, (const char *)val + (size_t)e * width, width);   // the bytes as they are
                 ++o;
+            }
+        }
+    });
+}
+
+// group_stats.hip restated: the same refusals in the same order, then one entry after the other, the rows as
+// they are stored
+int schpf_debug_group_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                            const void *val, int val_kind, const int32_t *labels, int64_t ngroups, int64_t *group_cells,
+                            int64_t *nexpr, int64_t *total, int64_t *sumsq)
+{
+    if (const char *why = group_stats_bad_args(ncells, ngenes, nnz, indptr, indices, val, labels, ngroups, group_cells, nexpr, total))
+        return fail("%s", why);
+    return guarded([&] {
+        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        const size_t G = (size_t)ngroups, J = (size_t)ngenes;
+        uint64_t vmax = 0;
+        if (nnz > 0) {
+            for (int64_t r = 0; r <= ncells; ++r)
+                if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
+                    throw std::invalid_argument(group_stats_bad_indptr(r));
+            int64_t bad_index = -1, bad_order = -1, bad_value = -1;
+            for (int64_t r = 0; r < ncells; ++r)
+                for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                    if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
+                    if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
+                    const double v = read_count(val, val_kind, e);
+                    if (schpf::thin_value_bad(v)) {
+                        if (bad_value < 0) bad_value = e;
+                    } else {
+                        vmax = std::max(vmax, (uint64_t)v);
+                    }
+                }
+            if (bad_index >= 0) throw std::invalid_argument(group_stats_bad_index(bad_index));
+            if (bad_order >= 0) throw std::invalid_argument(group_stats_bad_order(bad_order));
+            if (bad_value >= 0) throw std::invalid_argument(group_stats_bad_value(bad_value));
+        }
+        for (int64_t i = 0; i < ncells; ++i)
+            if (labels[i] < -1 || labels[i] >= ngroups) throw std::invalid_argument(group_stats_bad_labels(i));
+        if (sumsq && qc_sumsq_overflows(vmax, ncells)) throw std::invalid_argument(group_stats_bad_sumsq(vmax, ncells));
+        std::fill(group_cells, group_cells + G, (int64_t)0);
+        for (int64_t *p : {nexpr, total, sumsq})
+            if (p && J) std::fill(p, p + G * J, (int64_t)0);
+        for (int64_t i = 0; i < ncells; ++i)
+            if (labels[i] >= 0) ++group_cells[labels[i]];
+        if (nnz == 0) return;
+        for (int64_t r = 0; r < ncells; ++r) {
+            if (labels[r] < 0) continue;
+            const size_t row = (size_t)labels[r] * J;
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                const int64_t v = (int64_t)read_count(val, val_kind, e);
+                if (v == 0) continue;   // a stored zero is no expression
+                const size_t at = row + (size_t)indices[e];
+                ++nexpr[at];
+                total[at] += v;
+                if (sumsq) sumsq[at] += v * v;
             }
         }
     });

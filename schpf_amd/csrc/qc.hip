@@ -3,9 +3,10 @@
 // only; the sums are integer adds, which commute, and every entry of a submatrix is written by exactly one lane: host.cpp's
 // serial restatement gives the same bits, whatever the grid.
 //
-//   qc_indptr_kernel       indptr starts at 0, does not decrease and ends at nnz: the smallest offending row
-//   qc_entries_kernel      a wavefront per row: every column in [0, ngenes); for the statistics also above its left
+//   csr_indptr_kernel      indptr starts at 0, does not decrease and ends at nnz: the smallest offending row
+//   csr_entries_kernel     a wavefront per row: every column in [0, ngenes); for the statistics also above its left
 //                          neighbour, every value a count thinning accepts, and the largest value: the smallest offenders
+//                          (both in csr_device.h, shared with group_stats.hip, as is the bisection of a row)
 //   qc_cell_kernel         a wavefront per row: the entries > 0, their sum, and per gene set the sum of the entries whose
 //                          gene carries the set's bit.  gene_flags is gathered through the cache.  A piece of 64 entries sums
 //                          to at most 2^30, so a set's piece is reduced in 32 bits, and only where a lane carries the bit;
@@ -37,66 +38,13 @@
 namespace schpf {
 namespace {
 
-typedef unsigned long long sum_t;   // the int64 outputs as atomicAdd takes them; no sum here is negative
+using namespace csr_checks;
 
-constexpr int QC_THREADS = 256;
+constexpr int QC_THREADS = CSR_THREADS;
 constexpr int QC_GENE_THREADS = 1024;   // 16 wavefronts share a window's bins
 constexpr int QC_BINS = 3072;           // columns per window: 4 + 8 + 8 bytes each, 60 KiB of LDS, two workgroups per CU
 constexpr int QC_GENE_BLOCKS = 2048;    // workgroups of the gene side, where the matrix has the rows for them
-constexpr int QC_CHECK_BLOCKS = 4096;   // workgroups of qc_entries_kernel at the most: 16 per CU
 constexpr int QC_NARROW_BELOW = 32;     // entries of a row per window below which 16 lanes share a row, not 64
-constexpr unsigned long long NONE = ~0ull;
-enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_ROW, W_VMAX, W_COUNT };
-
-// Every lane of a wavefront leaves the loop before the reduction: no early return
-__global__ __launch_bounds__(QC_THREADS) void qc_indptr_kernel(const void *__restrict__ indptr, int indptr_kind, int64_t ncells,
-                                                               int64_t nnz, unsigned long long *__restrict__ words)
-{
-    unsigned long long bad = NONE;
-    for (int64_t r = blockIdx.x * (int64_t)QC_THREADS + threadIdx.x; r <= ncells; r += (int64_t)gridDim.x * QC_THREADS) {
-        const long long here = load_index(indptr, indptr_kind, r);
-        const bool wrong = (r == 0 && here != 0) || (r == ncells ? here != nnz : load_index(indptr, indptr_kind, r + 1) < here);
-        if (wrong && (unsigned long long)r < bad) bad = (unsigned long long)r;
-    }
-    bad = wave_min(bad);
-    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_INDPTR, bad);
-}
-
-// counts: the matrix must be canonical and hold counts (the statistics); else only the column range is asked (the submatrix)
-template <bool counts> __global__ __launch_bounds__(QC_THREADS) void qc_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (QC_THREADS / 64);
-    unsigned long long bad_index = NONE, bad_order = NONE, bad_value = NONE, vmax = 0;
-    for (int64_t r = blockIdx.x * (int64_t)(QC_THREADS / 64) + (threadIdx.x >> 6); r < m.ncells; r += waves) {
-        const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
-        for (int64_t e = from + lane; e < to; e += 64) {
-            const long long c = load_index(m.indices, m.idx_kind, e);
-            if ((c < 0 || c >= m.ngenes) && (unsigned long long)e < bad_index) bad_index = (unsigned long long)e;
-            if (!counts) continue;
-            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c && (unsigned long long)r < bad_order)
-                bad_order = (unsigned long long)r;
-            const double v = load_value(m.val, m.val_kind, e);
-            if (thin_value_bad(v)) {
-                if ((unsigned long long)e < bad_value) bad_value = (unsigned long long)e;
-            } else if ((unsigned long long)v > vmax) {
-                vmax = (unsigned long long)v;
-            }
-        }
-    }
-    bad_index = wave_min(bad_index);
-    if (lane == 0 && bad_index != NONE) atomicMin(words + W_BAD_INDEX, bad_index);
-    if (!counts) return;
-    bad_order = wave_min(bad_order);
-    bad_value = wave_min(bad_value);
-    vmax = ~wave_min(~vmax);
-    if (lane == 0) {
-        if (bad_order != NONE) atomicMin(words + W_BAD_ORDER, bad_order);
-        if (bad_value != NONE) atomicMin(words + W_BAD_VALUE, bad_value);
-        // a million wavefronts on one address is what this kernel would wait for: only a value above the one seen goes there
-        if (vmax > __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMax(words + W_VMAX, vmax);
-    }
-}
 
 __global__ __launch_bounds__(QC_THREADS) void qc_rows_kernel(const int32_t *__restrict__ rows, int64_t n_rows, int64_t ncells,
                                                              unsigned long long *__restrict__ words)
@@ -155,18 +103,6 @@ __global__ __launch_bounds__(QC_THREADS) void qc_cell_kernel(Matrix m, int n_set
         }
         if (lane < n_sets) cell_set_total[(int64_t)lane * m.ncells + r] = (int64_t)mine;
     }
-}
-
-// the first of the n ascending columns at p that is not below `key`
-template <typename I> __device__ __forceinline__ int64_t lower_bound(const I *__restrict__ p, int64_t n, long long key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((long long)p[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // blockIdx.x: the window of columns, blockIdx.y: the slab of rows_per_slab rows.  G lanes share a row -- 64 for long rows, 16
@@ -287,33 +223,6 @@ __global__ __launch_bounds__(QC_THREADS) void qc_fill_kernel(Matrix m, const int
     }
 }
 
-#define LAUNCH(kernel, n, per_block, st, ...)                                                               \
-    do {                                                                                                    \
-        hipLaunchKernelGGL(kernel, dim3(grid_for(n, per_block)), dim3(QC_THREADS), 0, st, __VA_ARGS__);     \
-        HIPCHK(hipGetLastError());                                                                          \
-    } while (0)
-
-struct Words {   // the smallest offenders in device memory, and their copy on the host
-    DevBuf d;
-    unsigned long long h[W_COUNT];
-    unsigned long long *dev() const { return d.as<unsigned long long>(); }
-    void reset(hipStream_t st)
-    {
-        d.alloc(W_COUNT * sizeof(unsigned long long));
-        HIPCHK(hipMemsetAsync(d.p, 0xFF, W_COUNT * sizeof(unsigned long long), st));   // NONE
-        HIPCHK(hipMemsetAsync(dev() + W_VMAX, 0, sizeof(unsigned long long), st));
-    }
-    void fetch(hipStream_t st) { d2h(h, d, sizeof h, st); }
-};
-
-void exclusive_scan(hipStream_t st, DevBuf &temp, const int64_t *in, int64_t *out, size_t n)
-{
-    size_t bytes = 0;
-    HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st));
-    temp.alloc(bytes);
-    HIPCHK(rocprim::exclusive_scan(temp.p, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st));
-}
-
 // Everything on `st`, which is synchronised when this returns; all pointers are device memory and nnz is at least 1.  The
 // checks come first, indptr before anything that follows it into the entries: a refused call has written nothing
 void stats_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int n_sets, const uint32_t *gene_flags, int64_t *cell_n,
@@ -322,18 +231,17 @@ void stats_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int n_sets, c
     const int per_wave = QC_THREADS / 64;
     Words w;
     w.reset(st);
-    LAUNCH(qc_indptr_kernel, m.ncells + 1, QC_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, w.dev());
+    launch_indptr_check(st, m, nnz, w);
     w.fetch(st);
     if (w.h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(qc_bad_indptr((int64_t)w.h[W_BAD_INDPTR]));
-    // a bounded grid: a wavefront walks many rows and reports once
-    LAUNCH(qc_entries_kernel<true>, std::min<int64_t>(m.ncells, QC_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
+    launch_entries_check<true>(st, m, w);
     w.fetch(st);
     if (w.h[W_BAD_INDEX] != NONE) throw std::invalid_argument(qc_bad_index((int64_t)w.h[W_BAD_INDEX]));
     if (w.h[W_BAD_ORDER] != NONE) throw std::invalid_argument(qc_bad_order((int64_t)w.h[W_BAD_ORDER]));
     if (w.h[W_BAD_VALUE] != NONE) throw std::invalid_argument(qc_bad_value((int64_t)w.h[W_BAD_VALUE]));
     if (qc_sumsq_overflows(w.h[W_VMAX], m.ncells)) throw std::invalid_argument(qc_bad_sumsq(w.h[W_VMAX], m.ncells));
 
-    LAUNCH(qc_cell_kernel, m.ncells, per_wave, st, m, n_sets, gene_flags, cell_n, cell_total, cell_set_total);
+    CSR_LAUNCH(qc_cell_kernel, m.ncells, per_wave, st, m, n_sets, gene_flags, cell_n, cell_total, cell_set_total);
     for (int64_t *p : {gene_n, gene_total, gene_sumsq}) HIPCHK(hipMemsetAsync(p, 0, (size_t)m.ngenes * sizeof(int64_t), st));
     const int64_t windows = (m.ngenes + QC_BINS - 1) / QC_BINS;
     const bool narrow = nnz / m.ncells / windows < QC_NARROW_BELOW;   // the mean share of a window in a row
@@ -360,12 +268,12 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
     Words w;
     w.reset(st);
     if (!empty) {
-        LAUNCH(qc_indptr_kernel, m.ncells + 1, QC_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, w.dev());
+        launch_indptr_check(st, m, nnz, w);
         w.fetch(st);
         if (w.h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(qc_bad_indptr((int64_t)w.h[W_BAD_INDPTR]));
-        LAUNCH(qc_entries_kernel<false>, std::min<int64_t>(m.ncells, QC_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
+        launch_entries_check<false>(st, m, w);
     }
-    if (rows && n_rows > 0) LAUNCH(qc_rows_kernel, n_rows, QC_THREADS, st, rows, n_rows, m.ncells, w.dev());
+    if (rows && n_rows > 0) CSR_LAUNCH(qc_rows_kernel, n_rows, QC_THREADS, st, rows, n_rows, m.ncells, w.dev());
     w.fetch(st);
     if (w.h[W_BAD_INDEX] != NONE) throw std::invalid_argument(qc_bad_index((int64_t)w.h[W_BAD_INDEX]));
     if (w.h[W_BAD_ROW] != NONE) throw std::invalid_argument(qc_bad_rows((int64_t)w.h[W_BAD_ROW]));
@@ -375,7 +283,7 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
     if (gene_keep) {
         kept.alloc((size_t)(m.ngenes + 1) * sizeof(int32_t));
         colmap.alloc((size_t)(m.ngenes + 1) * sizeof(int32_t));
-        LAUNCH(qc_keep_kernel, m.ngenes + 1, QC_THREADS, st, gene_keep, m.ngenes, kept.as<int32_t>());
+        CSR_LAUNCH(qc_keep_kernel, m.ngenes + 1, QC_THREADS, st, gene_keep, m.ngenes, kept.as<int32_t>());
         size_t bytes = 0;
         HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, kept.as<int32_t>(), colmap.as<int32_t>(), (int32_t)0,
                                        (size_t)(m.ngenes + 1), rocprim::plus<int32_t>(), st));
@@ -391,8 +299,8 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
     if (!empty) {   // the lengths and their scan go to scratch: a capacity that is refused leaves out_indptr alone
         len.alloc((size_t)(n_rows + 1) * sizeof(int64_t));
         indptr.alloc((size_t)(n_rows + 1) * sizeof(int64_t));
-        if (map) LAUNCH(qc_length_kernel, n_rows + 1, per_wave, st, m, rows, n_rows, map, len.as<int64_t>());
-        else LAUNCH(qc_span_kernel, n_rows + 1, QC_THREADS, st, m, rows, n_rows, len.as<int64_t>());
+        if (map) CSR_LAUNCH(qc_length_kernel, n_rows + 1, per_wave, st, m, rows, n_rows, map, len.as<int64_t>());
+        else CSR_LAUNCH(qc_span_kernel, n_rows + 1, QC_THREADS, st, m, rows, n_rows, len.as<int64_t>());
         exclusive_scan(st, temp, len.as<int64_t>(), indptr.as<int64_t>(), (size_t)(n_rows + 1));
         HIPCHK(hipMemcpyAsync(&total, indptr.as<int64_t>() + n_rows, sizeof total, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -403,10 +311,10 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
     else HIPCHK(hipMemcpyAsync(out_indptr, indptr.p, (size_t)(n_rows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     if (out_indices && total > 0) {
         if (value_size(m.val_kind) == 4)
-            LAUNCH(qc_fill_kernel<uint32_t>, n_rows, per_wave, st, m, rows, n_rows, map, indptr.as<int64_t>(), out_indices,
+            CSR_LAUNCH(qc_fill_kernel<uint32_t>, n_rows, per_wave, st, m, rows, n_rows, map, indptr.as<int64_t>(), out_indices,
                    static_cast<uint32_t *>(out_values));
         else
-            LAUNCH(qc_fill_kernel<uint64_t>, n_rows, per_wave, st, m, rows, n_rows, map, indptr.as<int64_t>(), out_indices,
+            CSR_LAUNCH(qc_fill_kernel<uint64_t>, n_rows, per_wave, st, m, rows, n_rows, map, indptr.as<int64_t>(), out_indices,
                    static_cast<uint64_t *>(out_values));
     }
     HIPCHK(hipStreamSynchronize(st));   // before the scratch is released

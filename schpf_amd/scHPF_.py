@@ -342,6 +342,19 @@ class scHPF(BaseEstimator):
             labels = self.clusters(k=k, metric=metric, method=method, resolution=resolution, device=kwargs.get("device"))
         return rank_genes_groups(X, labels, **kwargs)
 
+    def pseudobulk(self, X, by=None, min_cells=1, device=None, **clusters_kwargs):
+        """The pseudobulk table of the count matrix X (cells x genes, what `fit` took): per group of cells the exact sums of
+        every gene's counts, the cells, and the fraction, mean and variance per group, on the GPU -- the dict of
+        schpf_amd.pseudobulk (groups, n_cells, counts, pct, mean, var).  by: a label array or a tuple of them (a sample id
+        and a cluster); by=None: the clusters are `clusters(**clusters_kwargs)` (k, metric, method, resolution).  An
+        addition to the reference's surface."""
+        from .aggregate import pseudobulk
+        if by is None:
+            by = self.clusters(device=device, **clusters_kwargs)
+        elif clusters_kwargs:
+            raise TypeError("%s belong to the clusters of by=None" % ", ".join(sorted(clusters_kwargs)))
+        return pseudobulk(X, by, min_cells=min_cells, device=device)
+
     def doublets(self, X, **kwargs):
         """Scrublet's doublet score of every cell of the count matrix X (cells x genes, what `fit` took) under this model:
         simulated doublets -- sums of random pairs of rows of X, made on the GPU -- are projected onto the frozen gene
