@@ -562,7 +562,10 @@ __device__ __forceinline__ double exp1_draw(uint64_t base, unsigned k)
 {
     uint32_t z = (uint32_t)base ^ ((uint32_t)(base >> 32) + k * 0x9E3779B9u);
     z ^= z >> 16; z *= 0x85EBCA6Bu; z ^= z >> 13; z *= 0xC2B2AE35u; z ^= z >> 16;   // murmur3 fmix32
-    const float u = ((float)(z >> 8) + 0.5f) * (1.0f / 16777216.0f);                 // (0,1)
+    // (0, 1]: from 2^23 on, v + 0.5f is a tie that rounds to the even neighbour, and 0xFFFFFF + 0.5f rounds to 2^24.
+    // Then u = 1, the draw is 0 and that factor's phi is exactly 0 (one draw in 2^24); the smallest u is 2^-25, the
+    // largest draw 25 ln 2.  tests/_random_start_reference.py restates these steps bit for bit
+    const float u = ((float)(z >> 8) + 0.5f) * (1.0f / 16777216.0f);
     return (double)(-__logf(u));
 }
 template <typename T, int NV, int LPC>
