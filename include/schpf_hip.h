@@ -691,6 +691,14 @@ int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *mi
                             int32_t *out_minor, float *out_val, int32_t *out_prow, int32_t *out_task,
                             int32_t *out_pfirst, int32_t *out_pcount, int64_t stats[8]);
 
+/* Test hook (host only, no GPU needed): the half (0 / 1) of its step slot in which a window-schedule tile plan, built
+ * as by schpf_debug_tile_expand (160-byte table rows, $SCHPF_BANK_ORDER), stores every nonzero; out_* have nnz
+ * entries, in the kernel's walk order.  The float64 sweep with two lanes per row divides for the first half of a slot
+ * in the even lane and for the second in the odd one. */
+int schpf_debug_tile_halves(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val, int n_major,
+                            int n_minor, int lpc, int waves_per_block, int win_rows, int target_tasks,
+                            int32_t *out_major, int32_t *out_minor, int32_t *out_half);
+
 /* Test hook (host only, no GPU needed, no environment read): the sweep shape an engine of `dtype` with `nfactors`
  * factors runs on -- the library's own choice (policy.cpp choose_config) under plan = 0 (the library picks the plan),
  * 1 (the tile plan forced, SCHPF_PLAN=tile) or 2 (the gather plan forced).  out = {1 tile / 0 gather, LPC (lanes per

@@ -116,6 +116,7 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp, _vp, _vp, _i64p],
     "schpf_debug_tile_expand": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p],
+    "schpf_debug_tile_halves": [_i64, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp, _vp, _vp],
 }
 STRING_FUNCS = ("schpf_last_error", "schpf_version")
 

@@ -244,6 +244,59 @@ int schpf_debug_tile_expand(int64_t nnz, const int32_t *major, const int32_t *mi
     });
 }
 
+// Which half of its step slot every nonzero of a window-schedule tile plan lies in: the plan is built as in
+// schpf_debug_tile_expand and walked as the kernel walks it.  The paired float64 sweep treats the two halves of a slot
+// in different lanes (sweep_impl.h pair_own_sum), and its tests place nonzeros in one half or the other on purpose
+int schpf_debug_tile_halves(int64_t nnz, const int32_t *major, const int32_t *minor, const float *val, int n_major,
+                            int n_minor, int lpc, int waves_per_block, int win_rows, int target_tasks,
+                            int32_t *out_major, int32_t *out_minor, int32_t *out_half)
+{
+    if (!major || !minor || !val || !out_major || !out_minor || !out_half) return fail("NULL argument");
+    return guarded([&] {
+        const schpf::Tuning tn = schpf::tuning_from_env();
+        schpf::TilePlanHost P;
+        schpf::TileShape sh;
+        sh.lpc = lpc; sh.waves_per_block = waves_per_block; sh.win_rows = win_rows; sh.target_tasks = target_tasks;
+        sh.row_slots = tn.debug_row_slots;
+        sh.bank_order = tn.bank_order;
+        schpf::build_tile_plan(nnz, major, minor, val, n_major, n_minor, sh, false, P);
+        const int W = P.n_windows, gpw = P.gpw, wpb = P.wpb, gpb = P.gpb;
+        int64_t n = 0;
+        for (int64_t t = 0; t < P.n_tasks; ++t) {
+            const int b = P.task_block[(size_t)t];
+            for (int v = 0; v < wpb; ++v) {
+                int64_t off = P.task_wave_off[(size_t)t * wpb + v];
+                for (int w = P.task_w0[(size_t)t]; w < P.task_w1[(size_t)t]; ++w) {
+                    const int steps = P.steps[((size_t)b * wpb + v) * W + w];
+                    for (int p = 0; p < steps; ++p)
+                        for (int u = 0; u < 2; ++u)
+                            for (int grp = 0; grp < gpw; ++grp) {
+                                const size_t slot = (size_t)off + (size_t)p * gpw + grp;
+                                uint32_t off16, bits;
+                                if (P.packed) {
+                                    const uint32_t *e = P.entries.data() + slot * 2;
+                                    off16 = (e[0] >> (16 * u)) & 0xFFFFu;
+                                    bits = (e[1] >> (16 * u)) & 0xFFFFu;
+                                } else {
+                                    const uint32_t *e = P.entries.data() + slot * 4 + (size_t)u * 2;
+                                    off16 = e[0];
+                                    bits = e[1] & 0x7FFFFFFFu;   // a float: zero is padding
+                                }
+                                if (bits == 0) continue;
+                                if (n >= nnz) throw std::logic_error("tile plan stores more nonzeros than given");
+                                out_major[n] = P.block_rows[(size_t)b * gpb + v * gpw + grp];
+                                out_minor[n] = w * P.win_rows + (int)(off16 / (uint32_t)P.row_slots);
+                                out_half[n] = u;
+                                ++n;
+                            }
+                    off += schpf::tile_stored_steps(P, steps) * gpw;
+                }
+            }
+        }
+        if (n != nnz) throw std::logic_error("tile plan lost nonzeros");
+    });
+}
+
 // the shape the engine would sweep `nfactors` factors with: choose_config itself, asked with a Tuning that sets the
 // plan and nothing else (no environment is read)
 int schpf_debug_choose_config(int dtype, int nfactors, int plan, int out[5])

@@ -189,6 +189,73 @@ __device__ __forceinline__ T group_dot(const T (&x)[KL], const T (&y)[KL])
     }
     return group_sum<T, LPC>(t);
 }
+// the lane's own share of it: the group of one lane has no cross-lane sum
+template <typename T, int KL>
+__device__ __forceinline__ T lane_dot(const T (&x)[KL], const T (&y)[KL])
+{
+    return group_dot<T, KL, 1>(x, y);
+}
+
+// Paired division (SCHPF_PAIR_DIV; LPC == 2, the paired float64 loop): a step has two nonzeros A and B, and both lanes
+// of a row pair would complete both normalisers and divide twice, on identical inputs.  Instead the even lane sums and
+// divides for A, the odd lane for B, and the quotients are exchanged: one v_rcp_f64, one Newton step, one multiply and
+// one count conversion per lane and step instead of two.  The bits are the ones of the unpaired form: p + partner(p)
+// commutes, and fast_div is the same instruction sequence whichever lane runs it.
+#ifndef SCHPF_PAIR_DIV
+#define SCHPF_PAIR_DIV 1
+#endif
+// The lane's normaliser: s = pA + partner's pA in the even lane, pB + partner's pB in the odd one.
+// s is the sum of two selects whose one side is the partner's value,
+//     m = odd ? pB : partner(pA)        n = odd ? partner(pB) : pA,
+// each half of which is ONE v_cndmask_b32 with a DPP source (quad_perm [1,0,3,2], as dpp_partner<0>).  In assembly,
+// because the compiler turns the selects of the C++ form into branches on the lane mask around v_mov_b32_dpp: four
+// more basic blocks per step, across which it no longer schedules the step (hipcc -S: the row registers spilled).
+// odd / even: the lane masks 0xAAAA... / 0x5555..., in scalar registers for the whole task.  s_nop 1: a DPP source
+// written by the VALU instruction before it needs two wait states, and the compiler does not look into the block.
+__device__ __forceinline__ double pair_own_sum(double pA, double pB, uint64_t odd, uint64_t even)
+{
+    int mlo, mhi, nlo, nhi;
+    asm("s_mov_b64 vcc, %8\n\t"
+        "s_nop 1\n\t"
+        "v_cndmask_b32_dpp %0, %4, %6, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_cndmask_b32_dpp %1, %5, %7, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_mov_b64 vcc, %9\n\t"
+        "v_cndmask_b32_dpp %2, %6, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_cndmask_b32_dpp %3, %7, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(mlo), "=&v"(mhi), "=&v"(nlo), "=&v"(nhi)
+        : "v"(__double2loint(pA)), "v"(__double2hiint(pA)), "v"(__double2loint(pB)), "v"(__double2hiint(pB)),
+          "s"(odd), "s"(even)
+        : "vcc");
+    return __hiloint2double(mhi, mlo) + __hiloint2double(nhi, nlo);
+}
+// The lane's count of a step, from what the decode one step ahead kept of the step's two counts (xc[][0], xc[][1]).
+// 16-bit entries {cnt0 | cnt1 << 16}: the lane's own half as an integer, extracted with a shift of the lane's own (0 or
+// 16, one register for the task: pair_keep_count) and converted here, once and exactly.  16-byte entries: both floats
+// are kept, selected here.
+__device__ __forceinline__ float pair_keep_count(unsigned word, unsigned shift)
+{
+    return __uint_as_float(__builtin_amdgcn_ubfe(word, shift, 16u));
+}
+template <bool PACK> __device__ __forceinline__ double pair_own_count(float c0, float c1, uint64_t odd)
+{
+    if constexpr (PACK) {
+        return (double)__float_as_uint(c0);
+    } else {
+        float x;   // odd ? c1 : c0 (in assembly for the reason given at pair_own_sum)
+        asm("s_mov_b64 vcc, %3\n\tv_cndmask_b32_e32 %0, %1, %2, vcc" : "=v"(x) : "v"(c0), "v"(c1), "s"(odd) : "vcc");
+        return (double)x;
+    }
+}
+// both quotients from the lane's own: A's lives in the even lane of the pair, B's in the odd one.  Every lane has a valid
+// source, as in dpp_partner; no select
+__device__ __forceinline__ void pair_quotients(double q, double &qA, double &qB)
+{
+    const int lo = __double2loint(q), hi = __double2hiint(q);
+    qA = __hiloint2double(__builtin_amdgcn_mov_dpp(hi, 0xA0, 0xF, 0xF, true),    // quad_perm [0,0,2,2]
+                          __builtin_amdgcn_mov_dpp(lo, 0xA0, 0xF, 0xF, true));
+    qB = __hiloint2double(__builtin_amdgcn_mov_dpp(hi, 0xF5, 0xF, 0xF, true),    // quad_perm [1,1,3,3]
+                          __builtin_amdgcn_mov_dpp(lo, 0xF5, 0xF, 0xF, true));
+}
 
 
 // Cold path shared by both sweeps.  When the product-form normaliser of ANY nonzero of a lane
@@ -748,6 +815,18 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
     // registers into the step loop: loss evaluation at the C5 share 1.30 -> 1.64 ms in f64, 0.49 -> 0.55 in f32; round 4)
     constexpr bool PAIR = KL * (int)sizeof(T) <= (MAXT <= 512 ? 192 : 96);
     constexpr bool PIPE = PAIR && MODE != MODE_RANDOM;
+    // paired division (pair_own_sum): float64 only -- the float32 rows of two lanes (K = 33...56) divide with one
+    // v_rcp_f32 and no Newton step; the form has not been built or measured for them, they keep the general one.
+    // And only the kernels it leaves within their registers (hipcc -S against the general form): all of
+    // NV = 4, and NV = 5 with 16-bit entries at 1024 threads (the headline kernel: 122 VGPRs either way).  It costs up
+    // to 7 registers elsewhere: NV = 5 at 512 threads goes from 124 to 129, past the 128 of four waves per SIMD; the
+    // 1024-thread kernels of NV = 5 with 16-byte entries and of NV = 6 sit at 128 already and spill more, the
+    // balanced NV = 6 kernel five accesses per step.  None of those was measured, so they keep the general form too
+    constexpr bool PAIR_DIV = SCHPF_PAIR_DIV && PIPE && LPC == 2 && MODE == MODE_PHI && sizeof(T) == 8 &&
+                              (NV == 4 || (NV == 5 && PACK && MAXT > 512));
+    // the lanes with sub == 1 / sub == 0 (lane parity), as wave masks: constants, held in scalar registers
+    constexpr uint64_t odd_lanes = 0xAAAAAAAAAAAAAAAAull, even_lanes = 0x5555555555555555ull;
+    const unsigned own_shift = PAIR_DIV ? (unsigned)sub * 16u : 0u;   // the lane's own count in a 16-bit entry
     // wide rows: ONE row in registers, refilled vector by vector.  float64 only: the float32 kernel with wide rows
     // (K = 50: 28 floats per lane) is 18 % slower with it (profiles/r03/ab_rolling_wide_rows.txt) and keeps the plain loop
     constexpr bool ROLL = !PAIR && MODE != MODE_RANDOM && sizeof(T) == 8;
@@ -877,8 +956,13 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
             if (nsl > 0) {   // prologue: the first step's rows (the ring was primed before the barrier)
                 const E c = ring[0];
                 unsigned i0 = EF::idx(c, 0), i1 = EF::idx(c, 1);
+                if constexpr (PAIR_DIV && PACK) {
+                    xc[0][0] = pair_keep_count(c.y, own_shift);
+                    asm volatile("" : "+v"(i0), "+v"(i1), "+v"(xc[0][0]));
+                } else {
                 xc[0][0] = EF::val(c, 0); xc[0][1] = EF::val(c, 1);
                 asm volatile("" : "+v"(i0), "+v"(i1), "+v"(xc[0][0]), "+v"(xc[0][1]));
+                }
                 load_lane<T, NV, LPC>(lds_row<T>(lds_raw, i0), sub, bA);
                 load_lane<T, NV, LPC>(lds_row<T>(lds_raw, i1), sub, bB);
             }
@@ -889,8 +973,33 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
                     const E cn = ring[(I + 1) % RING];
                     unsigned n0 = EF::idx(cn, 0), n1 = EF::idx(cn, 1);
                     // counts alternate between two register pairs (RING is even), no copies
+                    if constexpr (PAIR_DIV && PACK) {
+                        xc[(I + 1) & 1][0] = pair_keep_count(cn.y, own_shift);
+                        asm volatile("" : "+v"(n0), "+v"(n1), "+v"(xc[(I + 1) & 1][0]));
+                    } else {
                     xc[(I + 1) & 1][0] = EF::val(cn, 0); xc[(I + 1) & 1][1] = EF::val(cn, 1);
                     asm volatile("" : "+v"(n0), "+v"(n1), "+v"(xc[(I + 1) & 1][0]), "+v"(xc[(I + 1) & 1][1]));
+                    }
+                    if constexpr (PAIR_DIV) {
+                        // as the general form below, with the sum, the conversion of the count and the division done
+                        // once per lane: for A in the even lane, for B in the odd one (pair_own_sum, pair_own_count).  An underflowed
+                        // normaliser of either nonzero still poisons both lanes: its inf / NaN quotient is exchanged
+                        const T pA = lane_dot<T, KL>(tm, bA);
+                        const T pB = lane_dot<T, KL>(tm, bB);
+                        const T s = pair_own_sum(pA, pB, odd_lanes, even_lanes);
+                        const T x = pair_own_count<PACK>(xc[I & 1][0], xc[I & 1][1], odd_lanes);
+                        T q0, q1;
+                        pair_quotients(fast_div(x, s), q0, q1);
+#pragma unroll
+                        for (int k = 0; k < KL; ++k) acc[k] = fma_t(q0, bA[k], acc[k]);
+                        load_lane<T, NV, LPC>(lds_row<T>(lds_raw, n0), sub, bA);
+                        __builtin_amdgcn_sched_barrier(0);   // row A' is requested BEFORE nonzero B is accumulated
+#pragma unroll
+                        for (int k = 0; k < KL; ++k) acc[k] = fma_t(q1, bB[k], acc[k]);
+                        load_lane<T, NV, LPC>(lds_row<T>(lds_raw, n1), sub, bB);
+                        __builtin_amdgcn_sched_barrier(0);
+                        return;
+                    }
                     const T x0 = (T)xc[I & 1][0], x1 = (T)xc[I & 1][1];
                     // both normalisers first: two independent dot / reciprocal chains in flight
                     // (measured -1 % f64, -3 % f32 against finishing nonzero A before starting B:
