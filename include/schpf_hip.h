@@ -464,6 +464,62 @@ int schpf_louvain(int device, int n, const int64_t *indptr, const int32_t *indic
 int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, const double *data, double gamma,
                         int32_t *labels, int64_t stats[4]);
 
+/* Connected components of a graph: which vertices can reach each other, all integers.
+ * Input.  The structure of a CSR matrix n x n: indptr[n + 1] (int64), indices (int32), nnz = indptr[n] < 2^32, 0 <= n < 2^31.
+ *   Values are not read.  within: int32[n] or NULL.
+ * Edges.  Every stored entry (i, j) with j != i is an UNDIRECTED edge {i, j}: the matrix need not be symmetric (the directed
+ *   lists of a k-NN search give the weakly connected components), columns need not ascend and an entry may be stored twice.
+ *   With `within`, an entry is an edge only when within[i] == within[j] >= 0; a vertex with within[i] == -1 has no edges.
+ *   Refused, the outputs untouched, N the smallest offender, in this order:
+ *     "indptr must be 0 at row 0 and must be non-decreasing; offending row N"
+ *     "columns must be in [0, n); offending row N"
+ *     "components: within must be >= -1; offending vertex N"
+ *   and before anything is read: n < 0, nnz >= 2^32, NULL pointers.
+ * Output.  comp[n] (int32): the number of components whose smallest vertex is below the smallest vertex of i's component, i.e.
+ *   labels 0 .. C - 1 in ascending order of first member.  stats[6] (int64): C; the size of the largest component; the
+ *   components of size 1; the entries that were edges; then the hook rounds and the shortcut passes the device ran.  The
+ *   last two depend on how the work was scheduled and are OUTSIDE the bit contract (0 from the host restatement);
+ *   everything else is one well-defined result, equal bit for bit on every schedule.
+ * n = 0 succeeds, writes stats = 0 and does not read the other pointers.  nnz = 0: every vertex is its own component.
+ * Stateless; device memory that cannot be had returns SCHPF_ERR_NO_MEMORY (scratch: about 4 nnz + 24 n bytes).
+ * _device: indptr, indices, within and comp are DEVICE pointers on `device`, stats is a HOST pointer; stream as in
+ *   schpf_knn_device; synchronised before the call returns.
+ * schpf_components: host pointers, staged through the device; the same result.
+ * schpf_debug_components: test hook (host only, no GPU needed): a serial union-find and the numbering, which both must match
+ *   bit for bit on comp and stats[0..3]. */
+int schpf_components_device(int device, void *stream, int n, const int64_t *indptr, const int32_t *indices, const int32_t *within,
+                            int32_t *comp, int64_t stats[6]);
+int schpf_components(int device, int n, const int64_t *indptr, const int32_t *indices, const int32_t *within, int32_t *comp,
+                     int64_t stats[6]);
+int schpf_debug_components(int n, const int64_t *indptr, const int32_t *indices, const int32_t *within, int32_t *comp,
+                           int64_t stats[6]);
+
+/* The graph of the clusters: how many entries, and how much of Louvain's integer weight, join every pair of
+ * groups of vertices -- the integers behind a PAGA plot.  One aggregation step of schpf_louvain with the caller's labels.
+ * Input.  The CSR of schpf_components with data (double; NULL: every entry is 1); labels int32[n] in [-1, G), -1: the vertex
+ *   is in no group; G = ngroups >= 1 with G * G < 2^31.  Columns need not ascend.
+ *   Refused, the outputs untouched, N the smallest offender, in this order: the indptr and columns messages of
+ *   schpf_components, then
+ *     "values must be finite and >= 0; offending row N"
+ *     "cluster_graph: labels must be in [-1, G); offending vertex N"
+ * Output, all int64, row-major, written in full.  group_cells[G]: the vertices of every group.  count[G * G]: count[a * G + b]
+ *   = the stored entries (i, j) with j != i, labels[i] = a and labels[j] = b; stored zeros count.  weight[G * G] (may be NULL):
+ *   the sum over the same entries of q_e = llrint(ldexp(data_e / wmax, 30)), wmax the largest stored entry; with wmax == 0 or
+ *   data == NULL every q_e is 2^30.  *wmax (double, a HOST pointer in all three): the largest stored entry; 1 with data == NULL
+ *   and nnz > 0; 0 with nnz == 0.
+ * n = 0 succeeds and writes zeros.  Integer sums: equal bit for bit on every schedule.  Scratch: about 52 nnz bytes and the
+ *   sort's own.
+ * _device: indptr, indices, data, labels, group_cells, count and weight are DEVICE pointers; stream as in schpf_knn_device;
+ *   synchronised before the call returns.  schpf_cluster_graph: host pointers.  schpf_debug_cluster_graph: the serial
+ *   restatement (host only), which both must match bit for bit. */
+int schpf_cluster_graph_device(int device, void *stream, int n, const int64_t *indptr, const int32_t *indices, const double *data,
+                               const int32_t *labels, int ngroups, int64_t *group_cells, int64_t *count, int64_t *weight,
+                               double *wmax);
+int schpf_cluster_graph(int device, int n, const int64_t *indptr, const int32_t *indices, const double *data, const int32_t *labels,
+                        int ngroups, int64_t *group_cells, int64_t *count, int64_t *weight, double *wmax);
+int schpf_debug_cluster_graph(int n, const int64_t *indptr, const int32_t *indices, const double *data, const int32_t *labels,
+                              int ngroups, int64_t *group_cells, int64_t *count, int64_t *weight, double *wmax);
+
 /* Wilcoxon rank sums of every gene for every group of cells: the exact integers behind "which genes mark
  * each cluster".  With average ranks for ties, twice a rank is an integer; every output below is an integer sum, exact in
  * any order, and is equal bit for bit however the work was scheduled.

@@ -92,6 +92,12 @@ SIGNATURES = {
     "schpf_louvain_device": [_int, _vp, _int, _vp, _vp, _vp, _dbl, _vp, _i64p],
     "schpf_louvain": [_int, _int, _vp, _vp, _vp, _dbl, _vp, _i64p],
     "schpf_debug_louvain": [_int, _vp, _vp, _vp, _dbl, _vp, _i64p],
+    "schpf_components_device": [_int, _vp, _int, _vp, _vp, _vp, _vp, _i64p],
+    "schpf_components": [_int, _int, _vp, _vp, _vp, _vp, _i64p],
+    "schpf_debug_components": [_int, _vp, _vp, _vp, _vp, _i64p],
+    "schpf_cluster_graph_device": [_int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _dblp],
+    "schpf_cluster_graph": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _dblp],
+    "schpf_debug_cluster_graph": [_int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _dblp],
     "schpf_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],

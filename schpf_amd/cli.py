@@ -138,6 +138,16 @@ def _parser():
                             "per cell.")
     score.add_argument("--resolution", type=float, default=None, metavar="R",
                        help="Resolution of --clusters: larger values give more, smaller clusters. [1.0]")
+    score.add_argument("--connected", default=False, action="store_true",
+                       help="With --clusters: split every Louvain cluster into its connected pieces, so that no cluster is "
+                            "two unrelated groups of cells; also write the connected components of the whole graph as "
+                            "components.txt, one label per cell.")
+    score.add_argument("--min-cluster-size", type=int, default=None, metavar="S",
+                       help="With --clusters: merge every cluster of fewer than S cells into the cluster it shares the most "
+                            "graph weight with. [0]")
+    score.add_argument("--paga", default=False, action="store_true",
+                       help="With --clusters: also write the cluster graph (PAGA) of the directed k-NN graph as "
+                            "paga_connectivities.txt and paga_counts.txt (clusters x clusters).")
     score.add_argument("--markers", default=False, action="store_true",
                        help="With -i and --clusters: also write the Wilcoxon rank-sum test of every gene, each cluster "
                             "against all the other cells, as marker_scores.txt and marker_pvals_adj.txt (genes x clusters); "
@@ -325,6 +335,12 @@ def _score(args, outprefix):
         raise ValueError("--pseudobulk needs groups: the clusters (--knn K --knn-graph M --clusters), --sample-ids FILE, or both")
     if args.sample_ids is not None and not args.pseudobulk:
         raise ValueError("--sample-ids belongs to --pseudobulk")
+    if not args.clusters:
+        for name in ("connected", "min_cluster_size", "paga"):
+            if getattr(args, name):
+                raise ValueError("--%s belongs to --clusters" % name.replace("_", "-"))
+    if args.min_cluster_size is not None and args.min_cluster_size < 0:
+        raise ValueError("--min-cluster-size must be >= 0")
     labels = sample_ids = None
     print("Loading model.....")
     model = joblib.load(args.model)
@@ -393,8 +409,22 @@ def _score(args, outprefix):
             if args.clusters:
                 print("Saving clusters.....")
                 args.resolution = 1.0 if args.resolution is None else args.resolution
-                labels = louvain(graph, resolution=args.resolution)
+                labels = louvain(graph, resolution=args.resolution, connected=args.connected)
+                if args.connected:
+                    from .topology import connected_components
+                    np.savetxt(outprefix + "components.txt", connected_components(graph), fmt="%d")
+                if args.min_cluster_size:
+                    from .topology import absorb_small, cluster_graph
+                    table = cluster_graph(graph, labels)
+                    labels = absorb_small(labels, table["weight"], table["n_cells"], args.min_cluster_size)[0]
                 np.savetxt(outprefix + "clusters.txt", labels, fmt="%d")
+                if args.paga:
+                    from .neighbors import knn_graph
+                    from .topology import paga
+                    print("Saving the cluster graph.....")
+                    found = paga(knn_graph(indices, distances, indices.shape[0]), labels)
+                    np.savetxt(outprefix + "paga_connectivities.txt", found["connectivities"], delimiter="\t")
+                    np.savetxt(outprefix + "paga_counts.txt", found["count"], fmt="%d", delimiter="\t")
                 if args.markers:
                     from .markers import rank_genes_groups
                     print("Saving marker genes.....")
@@ -419,6 +449,9 @@ def _score(args, outprefix):
         if args.markers:
             raise ValueError("--markers needs the clusters (--knn K --knn-graph M --clusters)")
         del args.clusters, args.resolution   # ... and without its clusters
+    for name in ("connected", "min_cluster_size", "paga"):
+        if not getattr(args, name):
+            delattr(args, name)              # ... or their connected pieces, merged splinters and cluster graph
     if not args.markers:
         del args.markers                     # ... and without their marker genes
     if args.pseudobulk:

@@ -150,6 +150,45 @@ inline std::string louvain_bad_columns(int64_t row)
 inline std::string louvain_bad_values(int64_t row) { return "values must be finite and >= 0; offending row " + std::to_string(row); }
 constexpr int LOUVAIN_ROUNDS = 32, LOUVAIN_LEVELS = 32;   // the caps of the definition
 
+// What schpf_components, schpf_components_device and schpf_debug_components refuse alike before anything is read
+// (include/schpf_hip.h); n = 0 is asked next by the caller.  nullptr: the arguments are fine
+inline const char *components_bad_args(int n, const void *indptr, const void *comp, const void *stats)
+{
+    if (n < 0) return "n must be in [0, 2^31)";
+    if (!stats) return "stats must not be NULL";
+    if (n == 0) return nullptr;
+    if (!indptr || !comp) return "indptr and comp must not be NULL";
+    return nullptr;
+}
+inline const char *components_bad_nnz(int64_t nnz, const void *indices)
+{
+    if (nnz >= (int64_t)1 << 32) return "nnz must be below 2^32";
+    if (nnz > 0 && !indices) return "indices must not be NULL";
+    return nullptr;
+}
+inline std::string graph_bad_columns(int64_t row) { return "columns must be in [0, n); offending row " + std::to_string(row); }
+inline std::string components_bad_within(int64_t vertex)
+{
+    return "components: within must be >= -1; offending vertex " + std::to_string(vertex);
+}
+
+// What schpf_cluster_graph, schpf_cluster_graph_device and schpf_debug_cluster_graph refuse alike before anything is read
+inline const char *cluster_graph_bad_args(int n, const void *indptr, const void *labels, int ngroups, const void *group_cells,
+                                          const void *count, const void *wmax)
+{
+    if (n < 0) return "n must be in [0, 2^31)";
+    if (ngroups < 1) return "ngroups must be at least 1";
+    if ((int64_t)ngroups * (int64_t)ngroups >= (int64_t)1 << 31) return "ngroups * ngroups must be below 2^31";
+    if (!group_cells || !count || !wmax) return "group_cells, count and wmax must not be NULL";
+    if (n == 0) return nullptr;
+    if (!indptr || !labels) return "indptr and labels must not be NULL";
+    return nullptr;
+}
+inline std::string cluster_graph_bad_labels(int64_t vertex)
+{
+    return "cluster_graph: labels must be in [-1, G); offending vertex " + std::to_string(vertex);
+}
+
 // What schpf_rank_sums, schpf_rank_sums_device and schpf_debug_rank_sums refuse alike (include/schpf_hip.h), before anything
 // is read; ncells = 0 or ngenes = 0 is asked next by the caller.  nullptr: the arguments are fine
 constexpr int RANK_SUMS_MAX_CELLS = 1 << 21;   // the tie term, a sum of cubes, stays under 2^63

@@ -1,6 +1,7 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
 // check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
-// (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the rank sums
+// (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the connected
+// components and the cluster graph (components.hip), of the rank sums
 // (rank_sums.hip), of the simulated doublets (doublets.hip) with the draw of their parents and of the axis statistics and
 // the submatrix (qc.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
 #include <execinfo.h>
@@ -657,6 +658,113 @@ int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, co
         stats[1] = levels;
         stats[2] = rounds;
         stats[3] = w2_first;
+    });
+}
+
+// components.hip restated: a serial union-find that keeps the smaller vertex as the root, then the numbering
+// by first member.  stats[4..5], the rounds of the device, are 0 here
+int schpf_debug_components(int n, const int64_t *indptr, const int32_t *indices, const int32_t *within, int32_t *comp,
+                           int64_t stats[6])
+{
+    if (const char *why = components_bad_args(n, indptr, comp, stats)) return fail("%s", why);
+    return guarded([&] {
+        if (n == 0) {
+            std::fill(stats, stats + 6, (int64_t)0);
+            return;
+        }
+        if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
+        for (int i = 0; i < n; ++i)
+            if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
+        const int64_t nnz = indptr[n];
+        if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= n) throw std::invalid_argument(graph_bad_columns(i));
+        if (within)
+            for (int i = 0; i < n; ++i)
+                if (within[i] < -1) throw std::invalid_argument(components_bad_within(i));
+        std::vector<int32_t> p((size_t)n);
+        for (int i = 0; i < n; ++i) p[(size_t)i] = i;
+        auto find = [&p](int32_t x) {
+            while (p[(size_t)x] != x) {
+                p[(size_t)x] = p[(size_t)p[(size_t)x]];   // path halving
+                x = p[(size_t)x];
+            }
+            return x;
+        };
+        int64_t edges = 0;
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                const int32_t j = indices[e];
+                if (j == i || (within && !(within[i] >= 0 && within[i] == within[j]))) continue;
+                ++edges;
+                const int32_t a = find(i), b = find(j);
+                if (a != b) p[(size_t)std::max(a, b)] = std::min(a, b);
+            }
+        // a root is the smallest vertex of its tree, so the roots are met in the order of the numbering
+        std::vector<int32_t> number((size_t)n), size;
+        for (int i = 0; i < n; ++i) {
+            const int32_t r = find(i);
+            if (r == i) {
+                number[(size_t)i] = (int32_t)size.size();
+                size.push_back(0);
+            }
+            ++size[(size_t)number[(size_t)r]];
+        }
+        int64_t largest = 0, single = 0;
+        for (int32_t s : size) {
+            largest = std::max<int64_t>(largest, s);
+            single += s == 1;
+        }
+        for (int i = 0; i < n; ++i) comp[i] = number[(size_t)find(i)];
+        stats[0] = (int64_t)size.size();
+        stats[1] = largest;
+        stats[2] = single;
+        stats[3] = edges;
+        stats[4] = stats[5] = 0;
+    });
+}
+
+// The cluster graph of components.hip restated: one walk over the entries
+int schpf_debug_cluster_graph(int n, const int64_t *indptr, const int32_t *indices, const double *data, const int32_t *labels,
+                              int ngroups, int64_t *group_cells, int64_t *count, int64_t *weight, double *wmax)
+{
+    if (const char *why = cluster_graph_bad_args(n, indptr, labels, ngroups, group_cells, count, wmax)) return fail("%s", why);
+    return guarded([&] {
+        const int64_t G = ngroups;
+        if (n > 0) {
+            if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
+            for (int i = 0; i < n; ++i)
+                if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
+        }
+        const int64_t nnz = n > 0 ? indptr[n] : 0;
+        if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= n) throw std::invalid_argument(graph_bad_columns(i));
+        double largest = data || nnz == 0 ? 0.0 : 1.0;
+        if (data)
+            for (int i = 0; i < n; ++i)
+                for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                    if (!(data[e] >= 0.0 && std::isfinite(data[e]))) throw std::invalid_argument(louvain_bad_values(i));
+                    largest = data[e] > largest ? data[e] : largest;
+                }
+        for (int i = 0; i < n; ++i)
+            if (labels[i] < -1 || labels[i] >= G) throw std::invalid_argument(cluster_graph_bad_labels(i));
+        std::fill(group_cells, group_cells + G, (int64_t)0);
+        std::fill(count, count + G * G, (int64_t)0);
+        if (weight) std::fill(weight, weight + G * G, (int64_t)0);
+        for (int i = 0; i < n; ++i) {
+            const int64_t a = labels[i];
+            if (a >= 0) ++group_cells[a];
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                const int64_t b = labels[indices[e]];
+                if (indices[e] == i || a < 0 || b < 0) continue;
+                ++count[a * G + b];
+                if (weight) weight[a * G + b] += data && largest > 0.0 ? std::llrint(std::ldexp(data[e] / largest, 30)) : (int64_t)1 << 30;
+            }
+        }
+        *wmax = largest;
     });
 }
 

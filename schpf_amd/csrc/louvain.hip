@@ -3,6 +3,7 @@
 // candidate is a fixed expression of exact integers.  Moves are synchronous.  The definition is in include/schpf_hip.h;
 // host.cpp's serial restatement gives the same bits.
 //
+// (the first four kernels are in graph_device.h, shared with components.hip)
 //   louvain_indptr_kernel   indptr starts at 0 and does not decrease: the smallest offending row of each workgroup
 //   louvain_rows_kernel     the row of every entry, by bisection in indptr (once per level: a row may be of any length,
 //                           no kernel walks one)
@@ -38,12 +39,11 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "common.h"
+#include "graph_device.h"   // what components.hip reads a graph with as well: the indptr, rows, check and quantise kernels
 #include "kernels.h"
 
 namespace schpf {
 namespace {
-
-typedef unsigned long long count_t;   // what rocPRIM writes a number of runs as
 
 struct Cand {
     double s;
@@ -56,10 +56,6 @@ struct Better {
         return (a.s > b.s || (a.s == b.s && a.d <= b.d)) ? a : b;
     }
 };
-struct Larger {
-    __host__ __device__ double operator()(const double &a, const double &b) const { return a > b ? a : b; }
-};
-
 __device__ __forceinline__ bool eligible(int64_t i, int round, int64_t k)
 {
     return ((((uint64_t)i * 2654435761ull) >> 16) & 1) == (uint64_t)(round & 1) && k > 0;
@@ -71,71 +67,6 @@ __device__ __forceinline__ double score(int64_t k, int64_t base, int64_t w2, int
     const double p = (double)k * (double)base;
     const double t = p / (double)w2;
     return fma(-gamma, t, (double)among);
-}
-
-__device__ __forceinline__ void block_min(int bad, int *__restrict__ part)
-{
-    __shared__ int red[256];
-    red[threadIdx.x] = bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-
-#define GRID_STRIDE(v, n) for (int64_t v = blockIdx.x * (int64_t)256 + threadIdx.x; v < (n); v += (int64_t)gridDim.x * 256)
-
-__global__ __launch_bounds__(256) void louvain_indptr_kernel(const int64_t *__restrict__ indptr, int n, int *__restrict__ part)
-{
-    int bad = INT_MAX;
-    GRID_STRIDE(i, n)
-    {
-        if ((i == 0 && indptr[0] != 0) || indptr[i + 1] < indptr[i]) bad = min(bad, (int)i);
-    }
-    block_min(bad, part);
-}
-
-// the largest row i < n with indptr[i] <= e: the row that holds entry e (indptr[0] = 0, indptr does not decrease)
-__global__ __launch_bounds__(256) void louvain_rows_kernel(const int64_t *__restrict__ indptr, int64_t n, int64_t nnz,
-                                                           int32_t *__restrict__ rowof)
-{
-    GRID_STRIDE(e, nnz)
-    {
-        int64_t lo = 0, hi = n;
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (indptr[mid] <= e) lo = mid;
-            else hi = mid;
-        }
-        rowof[e] = (int32_t)lo;
-    }
-}
-
-__global__ __launch_bounds__(256) void louvain_check_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                                            const double *__restrict__ data, const int32_t *__restrict__ rowof,
-                                                            int n, int64_t nnz, int *__restrict__ part_col,
-                                                            int *__restrict__ part_val)
-{
-    int bad_col = INT_MAX, bad_val = INT_MAX;
-    GRID_STRIDE(e, nnz)
-    {
-        const int row = rowof[e], col = indices[e];
-        if (col < 0 || col >= n || (e > indptr[row] && indices[e - 1] >= col)) bad_col = min(bad_col, row);
-        const double v = data[e];
-        if (!(v >= 0.0 && v <= DBL_MAX)) bad_val = min(bad_val, row);
-    }
-    block_min(bad_col, part_col);
-    __syncthreads();   // the LDS of block_min is used again
-    block_min(bad_val, part_val);
-}
-
-__global__ __launch_bounds__(256) void louvain_quantise_kernel(const double *__restrict__ data, const double *__restrict__ wmax,
-                                                               int64_t nnz, int64_t *__restrict__ q)
-{
-    const double m = *wmax;
-    GRID_STRIDE(e, nnz) q[e] = llrint(ldexp(data[e] / m, 30));
 }
 
 __global__ __launch_bounds__(256) void louvain_iota_kernel(int64_t n, int32_t *__restrict__ c)
@@ -268,58 +199,6 @@ __global__ __launch_bounds__(256) void louvain_compose_kernel(const int32_t *__r
     GRID_STRIDE(v, n) labels[v] = (int32_t)renum[c[labels[v]]];
 }
 
-unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 20)); }
-
-int bits_of(uint64_t largest)   // the bits a radix sort has to look at for keys up to `largest`
-{
-    int b = 1;
-    while (b < 64 && (largest >> b)) ++b;
-    return b;
-}
-
-#define LAUNCH(kernel, n, st, ...)                                                          \
-    do {                                                                                    \
-        hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(256), 0, st, __VA_ARGS__);      \
-        HIPCHK(hipGetLastError());                                                          \
-    } while (0)
-
-void use_device(int device)
-{
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
-    HIPCHK(hipSetDevice(device));
-}
-
-// rocPRIM's two-call protocol on one scratch buffer that grows when a call asks for more
-struct Scratch {
-    DevBuf buf;
-    template <typename F> void run(F &&f)
-    {
-        size_t bytes = 0;
-        HIPCHK(f((void *)nullptr, bytes));
-        if (bytes > buf.bytes || !buf.p) buf.alloc(bytes);   // hipFree waits for what still reads the old one
-        HIPCHK(f(buf.p, bytes));
-    }
-};
-
-// indptr[n + 1] in device memory: refused unless it starts at 0 and does not decrease.  Returns nnz = indptr[n]
-int64_t louvain_indptr_on_device(hipStream_t st, int n, const int64_t *indptr)
-{
-    const int64_t blocks = grid_for(n);
-    DevBuf part, bad;
-    part.alloc((size_t)blocks * sizeof(int));
-    bad.alloc(2 * sizeof(int));
-    LAUNCH(louvain_indptr_kernel, n, st, indptr, n, part.as<int>());
-    HIPCHK(launch_knn_bad(part.as<int>(), blocks, nullptr, 0, bad.as<int>(), st));
-    int h_bad[2];
-    int64_t nnz = 0;
-    HIPCHK(hipMemcpyAsync(&nnz, indptr + n, sizeof nnz, hipMemcpyDeviceToHost, st));
-    d2h(h_bad, bad, sizeof h_bad, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument(louvain_bad_indptr(h_bad[0]));
-    return nnz;
-}
-
 // Everything on `st`, which is synchronised when this returns; all pointers but stats are device memory, indptr has been
 // checked.  labels is written once, at the end: a refused call leaves it alone
 void louvain_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr, const int32_t *indices, const double *data,
@@ -354,7 +233,7 @@ void louvain_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr
                   *const d_comms = scalars.as<count_t>() + 5, *const d_next = scalars.as<count_t>() + 6;
 
     LAUNCH(louvain_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
-    LAUNCH(louvain_check_kernel, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, part_col.as<int>(),
+    LAUNCH(louvain_check_kernel<true>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, part_col.as<int>(),
            part_val.as<int>());
     HIPCHK(launch_knn_bad(part_col.as<int>(), blocks, part_val.as<int>(), blocks, bad.as<int>(), st));
     temp.run([&](void *t, size_t &b) { return rocprim::reduce(t, b, data, d_wmax, 0.0, (size_t)nnz, Larger(), st); });
@@ -487,16 +366,6 @@ void louvain_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr
         nnz_l = (int64_t)nnz_next;
     }
     finish(nl, levels, rounds, w2_first);
-}
-
-hipStream_t pick_stream(void *stream, std::unique_ptr<TempStream> &own)
-{
-    // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
-    if (!stream) {
-        own.reset(new TempStream);
-        return own->st;
-    }
-    return stream == SCHPF_STREAM_DEFAULT ? nullptr : (hipStream_t)stream;
 }
 
 }  // namespace

@@ -257,7 +257,23 @@ def _resolution(resolution):
     return gamma
 
 
-def louvain(graph, resolution=1.0, device=None, return_stats=False):
+def _connected(graph, labels, stats, device, return_stats):
+    """louvain(connected=True): the connected pieces of every community, and the community each piece came from."""
+    from .topology import connected_components
+    pieces, found = connected_components(graph, within=labels, device=device, return_stats=True)
+    if not return_stats:
+        return pieces
+    if _is_tensor(pieces):
+        import torch
+        parent = torch.empty(found["components"], dtype=labels.dtype, device=pieces.device)
+        parent[pieces.long()] = labels.to(pieces.device)   # every member of a piece writes the same community
+    else:
+        parent = np.empty(found["components"], np.int32)
+        parent[pieces] = labels
+    return pieces, dict(stats, clusters=found["components"], parent=parent)
+
+
+def louvain(graph, resolution=1.0, device=None, return_stats=False, connected=False):
     """Louvain clusters of a weighted symmetric graph -- `knn_connectivities(...)`, or any n x n CSR matrix with finite
     entries >= 0 that equals its transpose -- as int32 labels 0 .. C - 1, one per row.
 
@@ -270,7 +286,11 @@ def louvain(graph, resolution=1.0, device=None, return_stats=False):
     computed on torch's current stream; nothing but four integers crosses to the host.  return_stats=True: also
     {"communities", "levels", "rounds", "total_weight"} (the levels that moved a vertex, the rounds of all levels, the sum
     of the quantised weights).  A matrix the library refuses -- columns out of range, negative or non-finite values --
-    raises ValueError naming the smallest offending row."""
+    raises ValueError naming the smallest offending row.
+
+    connected=True: Louvain can return a community that is not connected; every community is then split into its connected
+    pieces (schpf_amd.connected_components `within` the labels) and that labelling is returned, numbered in ascending order
+    of first member.  return_stats then also holds "clusters", their number, and "parent", the Louvain label each came from."""
     gamma = _resolution(resolution)
     names = ("communities", "levels", "rounds", "total_weight")
     if _is_tensor(graph) and graph.is_cuda:
@@ -295,6 +315,8 @@ def louvain(graph, resolution=1.0, device=None, return_stats=False):
             ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
             _lib.check(lib.schpf_louvain_device(dev.index, ctypes.c_void_p(stream), n, ptr(indptr), ptr(cols), ptr(data), gamma,
                                                 ptr(labels), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        if connected:
+            return _connected(graph, labels, dict(zip(names, stats.tolist())), device, return_stats)
         return (labels, dict(zip(names, stats.tolist()))) if return_stats else labels
 
     from scipy.sparse import csr_matrix, issparse
@@ -312,6 +334,11 @@ def louvain(graph, resolution=1.0, device=None, return_stats=False):
         G.sum_duplicates()
     labels, stats = _louvain_host(np.ascontiguousarray(G.indptr, dtype=np.int64), np.ascontiguousarray(G.indices, dtype=np.int32),
                                   np.ascontiguousarray(G.data, dtype=np.float64), gamma, device)
+    if connected:
+        pieces = _connected(G, labels, dict(zip(names, np.asarray(stats).tolist())), device, return_stats)
+        if back_to_torch:
+            pieces = (torch.from_numpy(pieces[0]), pieces[1]) if return_stats else torch.from_numpy(pieces)
+        return pieces
     if back_to_torch:
         labels = torch.from_numpy(labels)
     return (labels, dict(zip(names, np.asarray(stats).tolist()))) if return_stats else labels

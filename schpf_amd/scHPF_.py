@@ -323,13 +323,41 @@ class scHPF(BaseEstimator):
         return (knn_graph(indices, distances, indices.shape[0]),
                 knn_connectivities(indices, distances, method=method, device=device))
 
-    def clusters(self, k=15, metric="euclidean", method="jaccard", resolution=1.0, device=None):
+    def clusters(self, k=15, metric="euclidean", method="jaccard", resolution=1.0, device=None, connected=False, min_size=0):
         """The Louvain clusters of this model's cells: int32 labels 0 .. C - 1, one per cell, from the weighted graph of
         `neighbor_graph(k, metric, method)` on the GPU (schpf_amd.louvain; a larger `resolution` gives more clusters).
-        The same model gives the same labels, bit for bit.  An addition to the reference's surface."""
+        The same model gives the same labels, bit for bit.  connected=True: every cluster is split into its connected
+        pieces; min_size > 0: a cluster of fewer cells is merged into the cluster it shares the most graph weight with
+        (schpf_amd.cluster_graph, schpf_amd.absorb_small).  An addition to the reference's surface."""
         from .neighbors import louvain
         graph = self.neighbor_graph(k=k, metric=metric, method=method, device=device)[1]
-        return louvain(graph, resolution=resolution, device=device)
+        labels = louvain(graph, resolution=resolution, device=device, connected=connected)
+        if min_size > 0:
+            from .topology import absorb_small, cluster_graph
+            table = cluster_graph(graph, labels, device=device)
+            labels = absorb_small(labels, table["weight"], table["n_cells"], min_size)[0]
+        return labels
+
+    def components(self, k=15, metric="euclidean", method="jaccard", device=None, return_stats=False):
+        """The connected components of `neighbor_graph(k, metric, method)`: int32 labels 0 .. C - 1, one per cell, in
+        ascending order of first member, on the GPU (schpf_amd.connected_components).  An addition to the reference's
+        surface."""
+        from .topology import connected_components
+        graph = self.neighbor_graph(k=k, metric=metric, method=method, device=device)[1]
+        return connected_components(graph, device=device, return_stats=return_stats)
+
+    def cluster_graph(self, k=15, labels=None, metric="euclidean", device=None, **clusters_kwargs):
+        """The PAGA graph of clusters of this model's cells: the dict of schpf_amd.paga (connectivities, expected, count,
+        n_cells) on the directed k-NN graph of `neighbors(k, metric)`.  labels=None: the clusters are `clusters(k, metric,
+        **clusters_kwargs)`.  An addition to the reference's surface."""
+        from .neighbors import knn_graph
+        from .topology import paga
+        if labels is None:
+            labels = self.clusters(k=k, metric=metric, device=device, **clusters_kwargs)
+        elif clusters_kwargs:
+            raise TypeError("%s belong to the clusters of labels=None" % ", ".join(sorted(clusters_kwargs)))
+        indices, distances = self.neighbors(k=k, metric=metric, device=device)
+        return paga(knn_graph(indices, distances, indices.shape[0]), labels, device=device)
 
     def markers(self, X, labels=None, k=15, metric="euclidean", method="jaccard", resolution=1.0, **kwargs):
         """The marker genes of clusters of this model's cells: the Wilcoxon rank-sum test of every gene of the count matrix
