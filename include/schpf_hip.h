@@ -520,6 +520,45 @@ int schpf_cluster_graph(int device, int n, const int64_t *indptr, const int32_t 
 int schpf_debug_cluster_graph(int n, const int64_t *indptr, const int32_t *indices, const double *data, const int32_t *labels,
                               int ngroups, int64_t *group_cells, int64_t *count, int64_t *weight, double *wmax);
 
+/* Geodesic distances: the exact shortest-path distance of every vertex from sets of root vertices, walking
+ * over the graph -- what a pseudotime, Isomap and Palantir start from.
+ * Definition.  For one root set, d is the GREATEST solution of
+ *     d[v] = 0 for a root v,    d[v] = min over the edges (u, v) of fl(d[u] + w_uv) otherwise,
+ *   fl the IEEE double addition, the minimum of nothing +inf.  Floating-point addition is monotone and no length is negative,
+ *   so this is one well-defined set of doubles: Dijkstra ends on it, and so does relaxation of the edges in any order.
+ * Input.  The CSR of schpf_cluster_graph: int64 indptr[n + 1], int32 indices, double data; data == NULL: every length is 1
+ *   (hop counts).  nnz = indptr[n] < 2^32.  Columns need not ascend, an entry may be stored twice, diagonal entries are
+ *   ignored.  A stored entry (i, j, w) is an edge i -> j of length w; with directed == 0 it is also an edge j -> i (SciPy's
+ *   directed=False): where both directions are stored with different lengths, the smaller applies by itself.  Lengths must
+ *   be finite and >= 0; a stored zero is an edge of length 0.
+ *   Root sets.  roots[set_ptr[r] .. set_ptr[r + 1]) (int32, int64 set_ptr[nsets + 1]) is root set r; all its members start
+ *   at distance 0: one member per set gives one tree per root, one set of many members the distance to the nearest cell of a
+ *   root cluster.  A set may be empty (its row is all +inf); a root may appear in several sets and twice in one.
+ *   Refused, the outputs untouched, N the smallest offender, in this order: the indptr and columns messages of
+ *   schpf_components, the values message of schpf_cluster_graph, then
+ *     "geodesic: set_ptr must be 0 at set 0 and must be non-decreasing; offending set N"
+ *     "geodesic: roots must be in [0, n); offending set N"
+ *   and before anything is read: n < 0, nsets < 0, nnz >= 2^32, NULL pointers, 8 * nsets * n >= 2^63.
+ * Output.  dist[nsets * n] (double), row-major, written in full: dist[r * n + v] is d[v] of root set r, computed with one
+ *   IEEE addition per edge and no other arithmetic; +inf: v cannot be reached.  A sum that overflows is +inf, the same as
+ *   unreachable.  stats[3] (int64): the finite entries of dist; then the rounds and the lowering writes the device made.  The
+ *   last two depend on how the work was scheduled and are OUTSIDE the bit contract (0 from the host restatement);
+ *   everything else is one well-defined result, equal bit for bit on every schedule.
+ * n == 0 or nsets == 0 succeeds, writes stats = 0 and reads nothing else.
+ * Stateless; device memory that cannot be had returns SCHPF_ERR_NO_MEMORY (scratch: 4 nnz + n (8 min(nsets, 8) + 4) bytes,
+ *   4 bytes per root and a few words).
+ * _device: indptr, indices, data, set_ptr, roots and dist are DEVICE pointers on `device`, stats is a HOST pointer; stream as
+ *   in schpf_knn_device; synchronised before the call returns.
+ * schpf_geodesic: host pointers, staged through the device; the same result.
+ * schpf_debug_geodesic: test hook (host only, no GPU needed): a serial binary-heap Dijkstra per root set, which both must
+ *   match bit for bit on dist and stats[0]. */
+int schpf_geodesic_device(int device, void *stream, int n, const int64_t *indptr, const int32_t *indices, const double *data,
+                          int directed, int nsets, const int64_t *set_ptr, const int32_t *roots, double *dist, int64_t stats[3]);
+int schpf_geodesic(int device, int n, const int64_t *indptr, const int32_t *indices, const double *data, int directed, int nsets,
+                   const int64_t *set_ptr, const int32_t *roots, double *dist, int64_t stats[3]);
+int schpf_debug_geodesic(int n, const int64_t *indptr, const int32_t *indices, const double *data, int directed, int nsets,
+                         const int64_t *set_ptr, const int32_t *roots, double *dist, int64_t stats[3]);
+
 /* Wilcoxon rank sums of every gene for every group of cells: the exact integers behind "which genes mark
  * each cluster".  With average ranks for ties, twice a rank is an integer; every output below is an integer sum, exact in
  * any order, and is equal bit for bit however the work was scheduled.

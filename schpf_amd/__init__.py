@@ -12,6 +12,7 @@ from .trials import run_trials, run_trials_pool
 from .thinning import thin_counts
 from .neighbors import knn, knn_graph, knn_connectivities, louvain, modularity
 from .topology import connected_components, cluster_graph, absorb_small, paga
+from .paths import geodesic_distances, pseudotime, farthest_landmarks, landmark_isomap
 from .markers import rank_sums, rank_genes_groups
 from .doublets import simulate_doublets, doublet_scores
 from .qc import qc_metrics, submatrix, filter_counts
@@ -24,4 +25,5 @@ __all__ = ["__version__", "hpf_hip", "loss", "preprocessing", "DeviceCAVI", "HPF
            "save_model", "combine_across_cells", "run_trials", "run_trials_pool", "thin_counts", "knn", "knn_graph",
            "knn_connectivities", "louvain", "modularity", "rank_sums", "rank_genes_groups", "simulate_doublets",
            "doublet_scores", "qc_metrics", "submatrix", "filter_counts", "group_stats", "pseudobulk", "group_codes",
-           "connected_components", "cluster_graph", "absorb_small", "paga"]
+           "connected_components", "cluster_graph", "absorb_small", "paga", "geodesic_distances", "pseudotime",
+           "farthest_landmarks", "landmark_isomap"]

@@ -98,6 +98,9 @@ SIGNATURES = {
     "schpf_cluster_graph_device": [_int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _dblp],
     "schpf_cluster_graph": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _dblp],
     "schpf_debug_cluster_graph": [_int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _dblp],
+    "schpf_geodesic_device": [_int, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64p],
+    "schpf_geodesic": [_int, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64p],
+    "schpf_debug_geodesic": [_int, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64p],
     "schpf_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],

@@ -148,6 +148,12 @@ def _parser():
     score.add_argument("--paga", default=False, action="store_true",
                        help="With --clusters: also write the cluster graph (PAGA) of the directed k-NN graph as "
                             "paga_connectivities.txt and paga_counts.txt (clusters x clusters).")
+    score.add_argument("--pseudotime-root", type=int, nargs="+", default=None, metavar="I",
+                       help="With --knn: also write the pseudotime of every cell from these root cells (one joint root set) "
+                            "as pseudotime.txt: the shortest-path distance over the undirected k-NN distance graph to the "
+                            "nearest root, divided by the largest finite one; inf for a cell no root reaches.")
+    score.add_argument("--pseudotime-root-cluster", type=int, default=None, metavar="C",
+                       help="With --clusters: the cells of cluster C are the root set of pseudotime.txt.")
     score.add_argument("--markers", default=False, action="store_true",
                        help="With -i and --clusters: also write the Wilcoxon rank-sum test of every gene, each cluster "
                             "against all the other cells, as marker_scores.txt and marker_pvals_adj.txt (genes x clusters); "
@@ -341,6 +347,12 @@ def _score(args, outprefix):
                 raise ValueError("--%s belongs to --clusters" % name.replace("_", "-"))
     if args.min_cluster_size is not None and args.min_cluster_size < 0:
         raise ValueError("--min-cluster-size must be >= 0")
+    if args.pseudotime_root is not None and args.knn is None:
+        raise ValueError("--pseudotime-root belongs to --knn")
+    if args.pseudotime_root_cluster is not None and not args.clusters:
+        raise ValueError("--pseudotime-root-cluster belongs to --clusters")
+    if args.pseudotime_root is not None and args.pseudotime_root_cluster is not None:
+        raise ValueError("--pseudotime-root and --pseudotime-root-cluster are two ways to name one root set: give one")
     labels = sample_ids = None
     print("Loading model.....")
     model = joblib.load(args.model)
@@ -435,6 +447,16 @@ def _score(args, outprefix):
                         ranks = np.argsort(found["scores"].T, axis=0)[::-1]
                         ranked = np.stack([genes[ranks[:, c], name_col] for c in range(ranks.shape[1])]).T
                         np.savetxt(outprefix + "ranked_markers.txt", ranked, fmt="%s", delimiter="\t")
+        root = args.pseudotime_root
+        if args.pseudotime_root_cluster is not None and labels is not None:
+            root = np.asarray(labels) == args.pseudotime_root_cluster
+            if not root.any():
+                raise ValueError("--pseudotime-root-cluster {}: no cell is in that cluster".format(args.pseudotime_root_cluster))
+        if root is not None:
+            from .neighbors import knn_graph
+            from .paths import pseudotime
+            print("Saving pseudotime.....")
+            np.savetxt(outprefix + "pseudotime.txt", pseudotime(knn_graph(indices, distances, indices.shape[0]), root))
     else:
         if args.knn_graph is not None:
             raise ValueError("--knn-graph needs the neighbour lists (--knn K)")
@@ -452,6 +474,9 @@ def _score(args, outprefix):
     for name in ("connected", "min_cluster_size", "paga"):
         if not getattr(args, name):
             delattr(args, name)              # ... or their connected pieces, merged splinters and cluster graph
+    for name in ("pseudotime_root", "pseudotime_root_cluster"):
+        if getattr(args, name) is None:
+            delattr(args, name)              # ... or a pseudotime
     if not args.markers:
         del args.markers                     # ... and without their marker genes
     if args.pseudobulk:

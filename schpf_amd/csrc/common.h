@@ -189,6 +189,26 @@ inline std::string cluster_graph_bad_labels(int64_t vertex)
     return "cluster_graph: labels must be in [-1, G); offending vertex " + std::to_string(vertex);
 }
 
+// What schpf_geodesic, schpf_geodesic_device and schpf_debug_geodesic refuse alike before anything is read
+// (include/schpf_hip.h); n = 0 or nsets = 0 is asked next by the caller.  nullptr: the arguments are fine.  The graph's own
+// refusals are those of the components and of the cluster graph (components_bad_nnz, louvain_bad_indptr, graph_bad_columns,
+// louvain_bad_values)
+inline const char *geodesic_bad_args(int n, int nsets, const void *indptr, const void *set_ptr, const void *dist, const void *stats)
+{
+    if (n < 0) return "n must be in [0, 2^31)";
+    if (nsets < 0) return "nsets must be in [0, 2^31)";
+    if (!stats) return "stats must not be NULL";
+    if (n == 0 || nsets == 0) return nullptr;
+    if ((int64_t)nsets * (int64_t)n > INT64_MAX / 8) return "the bytes of dist, 8 * nsets * n, must be below 2^63";
+    if (!indptr || !set_ptr || !dist) return "indptr, set_ptr and dist must not be NULL";
+    return nullptr;
+}
+inline std::string geodesic_bad_set_ptr(int64_t set)
+{
+    return "geodesic: set_ptr must be 0 at set 0 and must be non-decreasing; offending set " + std::to_string(set);
+}
+inline std::string geodesic_bad_roots(int64_t set) { return "geodesic: roots must be in [0, n); offending set " + std::to_string(set); }
+
 // What schpf_rank_sums, schpf_rank_sums_device and schpf_debug_rank_sums refuse alike (include/schpf_hip.h), before anything
 // is read; ncells = 0 or ngenes = 0 is asked next by the caller.  nullptr: the arguments are fine
 constexpr int RANK_SUMS_MAX_CELLS = 1 << 21;   // the tie term, a sum of cubes, stays under 2^63

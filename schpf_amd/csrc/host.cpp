@@ -1,7 +1,7 @@
 // Host-only entry points of the C ABI (include/schpf_hip.h): the marginals of a COO, the two plan expanders the tests
 // check the host builders with, the serial restatements of count thinning (thin.hip), of the nearest-neighbour search
 // (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the connected
-// components and the cluster graph (components.hip), of the rank sums
+// components and the cluster graph (components.hip), of the shortest-path distances (geodesic.hip), of the rank sums
 // (rank_sums.hip), of the simulated doublets (doublets.hip) with the draw of their parents and of the axis statistics and
 // the submatrix (qc.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
 #include <execinfo.h>
@@ -11,6 +11,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
+#include <queue>
 #include <thread>
 
 #include "common.h"
@@ -765,6 +767,97 @@ int schpf_debug_cluster_graph(int n, const int64_t *indptr, const int32_t *indic
             }
         }
         *wmax = largest;
+    });
+}
+
+// geodesic.hip restated: a serial binary-heap Dijkstra per root set over the edges i -> j, and j -> i of an
+// undirected graph, with the one addition d[u] + w per edge.  Floating-point addition is monotone and no length is
+// negative, so a vertex leaves the heap with the greatest fixed point of the definition.  stats[1..2], the rounds and the
+// lowering writes of the device, are 0 here
+int schpf_debug_geodesic(int n, const int64_t *indptr, const int32_t *indices, const double *data, int directed, int nsets,
+                         const int64_t *set_ptr, const int32_t *roots, double *dist, int64_t stats[3])
+{
+    if (const char *why = geodesic_bad_args(n, nsets, indptr, set_ptr, dist, stats)) return fail("%s", why);
+    return guarded([&] {
+        if (n == 0 || nsets == 0) {
+            std::fill(stats, stats + 3, (int64_t)0);
+            return;
+        }
+        if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
+        for (int i = 0; i < n; ++i)
+            if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
+        const int64_t nnz = indptr[n];
+        if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= n) throw std::invalid_argument(graph_bad_columns(i));
+        if (data)
+            for (int i = 0; i < n; ++i)
+                for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+                    if (!(data[e] >= 0.0 && std::isfinite(data[e]))) throw std::invalid_argument(louvain_bad_values(i));
+        if (set_ptr[0] != 0) throw std::invalid_argument(geodesic_bad_set_ptr(0));
+        for (int r = 0; r < nsets; ++r)
+            if (set_ptr[r + 1] < set_ptr[r]) throw std::invalid_argument(geodesic_bad_set_ptr(r));
+        if (set_ptr[nsets] > 0 && !roots) throw std::invalid_argument("roots must not be NULL");
+        for (int r = 0; r < nsets; ++r)
+            for (int64_t e = set_ptr[r]; e < set_ptr[r + 1]; ++e)
+                if (roots[e] < 0 || roots[e] >= n) throw std::invalid_argument(geodesic_bad_roots(r));
+
+        // the edges that leave every vertex: its stored entries, and for an undirected graph the entries stored at others
+        const size_t N = (size_t)n;
+        std::vector<int64_t> start(N + 1, 0);
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                if (indices[e] == i) continue;
+                ++start[(size_t)i + 1];
+                if (!directed) ++start[(size_t)indices[e] + 1];
+            }
+        for (size_t v = 0; v < N; ++v) start[v + 1] += start[v];
+        std::vector<int32_t> head((size_t)start[N]);
+        std::vector<double> length((size_t)start[N]);
+        std::vector<int64_t> fill(start.begin(), start.end() - 1);
+        for (int i = 0; i < n; ++i)
+            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                const int32_t j = indices[e];
+                if (j == i) continue;
+                const double w = data ? data[e] : 1.0;
+                head[(size_t)fill[(size_t)i]] = j;
+                length[(size_t)fill[(size_t)i]++] = w;
+                if (!directed) {
+                    head[(size_t)fill[(size_t)j]] = i;
+                    length[(size_t)fill[(size_t)j]++] = w;
+                }
+            }
+
+        const double inf = std::numeric_limits<double>::infinity();
+        typedef std::pair<double, int32_t> Item;
+        int64_t finite = 0;
+        for (int r = 0; r < nsets; ++r) {
+            double *d = dist + (size_t)r * N;
+            std::fill(d, d + N, inf);
+            std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
+            for (int64_t e = set_ptr[r]; e < set_ptr[r + 1]; ++e)
+                if (d[roots[e]] != 0.0) {
+                    d[roots[e]] = 0.0;
+                    heap.push(Item(0.0, roots[e]));
+                }
+            while (!heap.empty()) {
+                const Item top = heap.top();
+                heap.pop();
+                const int32_t u = top.second;
+                if (top.first > d[u]) continue;   // an entry that a later, lower one has overtaken
+                ++finite;
+                for (int64_t e = start[(size_t)u]; e < start[(size_t)u + 1]; ++e) {
+                    const double cand = top.first + length[(size_t)e];   // the one addition of the definition
+                    if (cand < d[head[(size_t)e]]) {
+                        d[head[(size_t)e]] = cand;
+                        heap.push(Item(cand, head[(size_t)e]));
+                    }
+                }
+            }
+        }
+        stats[0] = finite;
+        stats[1] = stats[2] = 0;
     });
 }
 

@@ -359,6 +359,28 @@ class scHPF(BaseEstimator):
         indices, distances = self.neighbors(k=k, metric=metric, device=device)
         return paga(knn_graph(indices, distances, indices.shape[0]), labels, device=device)
 
+    def pseudotime(self, root, k=15, metric="euclidean", device=None):
+        """The pseudotime of this model's cells from a root: float64, one value per cell in [0, 1], inf for a cell the root
+        cannot reach -- the exact shortest-path distance over the undirected distance graph `knn_graph(*neighbors(k,
+        metric))`, divided by the largest finite one, on the GPU (schpf_amd.pseudotime).  root: a cell index, an index array
+        or a boolean mask over the cells (the distance to the nearest member).  An addition to the reference's surface."""
+        from .neighbors import knn_graph
+        from .paths import pseudotime
+        indices, distances = self.neighbors(k=k, metric=metric, device=device)
+        return pseudotime(knn_graph(indices, distances, indices.shape[0]), root, directed=False, device=device)
+
+    def layout(self, k=15, n_landmarks=64, metric="euclidean", device=None, n_components=2, first=0):
+        """A landmark Isomap of this model's cells: float64 ncells x n_components, from the exact shortest-path distances
+        over the graph of `pseudotime` to min(n_landmarks, ncells) landmarks picked by maxmin sampling from cell `first`
+        (schpf_amd.farthest_landmarks on the GPU, schpf_amd.landmark_isomap in NumPy).  Raises ValueError where the graph
+        is in pieces (see `components`).  An addition to the reference's surface."""
+        from .neighbors import knn_graph
+        from .paths import farthest_landmarks, landmark_isomap
+        indices, distances = self.neighbors(k=k, metric=metric, device=device)
+        graph = knn_graph(indices, distances, indices.shape[0])
+        landmarks, dist = farthest_landmarks(graph, min(int(n_landmarks), indices.shape[0]), first=first, device=device)
+        return landmark_isomap(dist, landmarks, n_components=n_components)
+
     def markers(self, X, labels=None, k=15, metric="euclidean", method="jaccard", resolution=1.0, **kwargs):
         """The marker genes of clusters of this model's cells: the Wilcoxon rank-sum test of every gene of the count matrix
         X (cells x genes, what `fit` took), each cluster against all the other cells, on the GPU -- the dict of
