@@ -72,6 +72,15 @@ const char *schpf_version(void);
 
 /* ---------------------------------------------------------------------------------
  * Stateless operator mirrors: array in, array out, caller's COO order.
+ *
+ * nfactors: every one of the five operators refuses nfactors < 1 ("nfactors must be at
+ * least 1") on the host, before anything is allocated, uploaded or launched.  Only
+ * schpf_rate_update has an upper limit, [1, 256]: its column-sum kernel deals the 256
+ * threads of a block out as 256 / nfactors rows of nfactors factors.  schpf_xphi,
+ * schpf_pois_llh_pointwise, schpf_shape_update and schpf_capacity_rate_update loop over the
+ * factors and take any nfactors >= 1.  The library reads exactly the element counts given
+ * below behind every pointer; it cannot see an array's real length (schpf_amd/hpf_hip.py
+ * checks every array's shape before it takes a pointer).
  * ------------------------------------------------------------------------------- */
 
 /* hpf_numba.psi / hpf_numba.cgammaln (hpf_numba.py:16-22): double -> double. */

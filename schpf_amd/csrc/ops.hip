@@ -67,7 +67,6 @@ void shape_update(int64_t nnz, int K, const void *xphi, const int32_t *keep, int
 template <typename T>
 void rate_update(int n, int m, int K, const void *ps, const void *pr, const void *os, const void *orr, void *out)
 {
-    if (K < 1 || K > 256) throw std::invalid_argument("nfactors must be in [1, 256]");
     TempStream ts;
     DevBuf a, b, c, d, part, S, o;
     h2d<T>(a, ps, (size_t)n, ts.st); h2d<T>(b, pr, (size_t)n, ts.st);
@@ -104,10 +103,15 @@ void special_array(bool gammaln, int64_t n, const double *x, double *out)
     d2h(out, o, (size_t)n * sizeof(double), ts.st);
 }
 
-// f(T()) for the dtype's T, as an entry point: bad dtypes and exceptions become a status
-template <typename F> int by_dtype(int dtype, F &&f)
+// f(T()) for the dtype's T, as an entry point: bad dtypes and exceptions become a status.  The one check of nfactors
+// for all five operators, on the host and ahead of every allocation, upload and launch: at least 1 everywhere (the
+// kernels read factor 0 of a row unasked), at most max_k where an operator has a limit -- ratio_colsum_kernel deals
+// its 256 threads out as 256 / K rows of K factors, so the rate update stops at 256; the other four loop over K
+template <typename F> int by_dtype(int dtype, int K, int max_k, F &&f)
 {
     if (bad_dtype(dtype)) return fail("dtype must be SCHPF_F32 or SCHPF_F64");
+    if (max_k > 0 && (K < 1 || K > max_k)) return fail("nfactors must be in [1, %d]", max_k);
+    if (K < 1) return fail("nfactors must be at least 1");
     return guarded([&] {
         if (dtype == SCHPF_F64) f(double());
         else f(float());
@@ -124,28 +128,28 @@ int schpf_gammaln(int64_t n, const double *x, double *out) { return guarded([&] 
 int schpf_xphi(int dtype, int64_t nnz, int N, int G, int K, const void *x, const int32_t *row, const int32_t *col,
                const void *ths, const void *thr, const void *bes, const void *ber, void *out)
 {
-    return by_dtype(dtype, [&](auto t) { xphi_or_llh<decltype(t)>(false, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out); });
+    return by_dtype(dtype, K, 0, [&](auto t) { xphi_or_llh<decltype(t)>(false, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out); });
 }
 int schpf_pois_llh_pointwise(int dtype, int64_t nnz, int N, int G, int K, const void *x, const int32_t *row,
                              const int32_t *col, const void *ths, const void *thr, const void *bes,
                              const void *ber, void *out)
 {
-    return by_dtype(dtype, [&](auto t) { xphi_or_llh<decltype(t)>(true, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out); });
+    return by_dtype(dtype, K, 0, [&](auto t) { xphi_or_llh<decltype(t)>(true, nnz, N, G, K, x, row, col, ths, thr, bes, ber, out); });
 }
 int schpf_shape_update(int dtype, int64_t nnz, int K, const void *xphi, const int32_t *keep, int nkeep,
                        double prior, void *out)
 {
-    return by_dtype(dtype, [&](auto t) { shape_update<decltype(t)>(nnz, K, xphi, keep, nkeep, prior, out); });
+    return by_dtype(dtype, K, 0, [&](auto t) { shape_update<decltype(t)>(nnz, K, xphi, keep, nkeep, prior, out); });
 }
 int schpf_rate_update(int dtype, int n, int m, int K, const void *ps, const void *pr, const void *os,
                       const void *orr, void *out)
 {
-    return by_dtype(dtype, [&](auto t) { rate_update<decltype(t)>(n, m, K, ps, pr, os, orr, out); });
+    return by_dtype(dtype, K, 256, [&](auto t) { rate_update<decltype(t)>(n, m, K, ps, pr, os, orr, out); });
 }
 int schpf_capacity_rate_update(int dtype, int n, int K, const void *shape, const void *rate, double prior,
                                void *out)
 {
-    return by_dtype(dtype, [&](auto t) { capacity_rate<decltype(t)>(n, K, shape, rate, prior, out); });
+    return by_dtype(dtype, K, 0, [&](auto t) { capacity_rate<decltype(t)>(n, K, shape, rate, prior, out); });
 }
 
 }  // extern "C"

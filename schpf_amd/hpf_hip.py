@@ -55,15 +55,43 @@ def cgammaln(x):
     return _special(_lib.load().schpf_gammaln, x)
 
 
+def _matrix(a, name):
+    """`a` as an array that must be (rows, nfactors >= 1); the sizes sent to the library are read off it."""
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("%s must be a 2-D array (rows, nfactors), got shape %s" % (name, a.shape))
+    if a.shape[1] < 1:
+        raise ValueError("%s: nfactors must be at least 1, got shape %s" % (name, a.shape))
+    return a
+
+
+def _same(a, name, shape, like):
+    """`a` as an array of exactly `shape`: the library reads that many elements behind its pointer and cannot see
+    how many there are."""
+    a = np.asarray(a)
+    if a.shape != tuple(shape):
+        raise ValueError("%s must have shape %s like %s, got %s" % (name, tuple(shape), like, a.shape))
+    return a
+
+
 def _coo_call(fn, out_cols, X_data, X_row, X_col, theta_vi_shape, theta_vi_rate,
               beta_vi_shape, beta_vi_rate):
+    theta_vi_shape = _matrix(theta_vi_shape, "theta_vi_shape")
+    beta_vi_shape = _matrix(beta_vi_shape, "beta_vi_shape")
     dt = theta_vi_shape.dtype
     code = _code(dt)
     ncells, nfactors = theta_vi_shape.shape
     ngenes = beta_vi_shape.shape[0]
     if beta_vi_shape.shape[1] != nfactors:
         raise ValueError("theta and beta must have the same number of factors")
+    theta_vi_rate = _same(theta_vi_rate, "theta_vi_rate", theta_vi_shape.shape, "theta_vi_shape")
+    beta_vi_rate = _same(beta_vi_rate, "beta_vi_rate", beta_vi_shape.shape, "beta_vi_shape")
+    X_data = np.asarray(X_data)
+    if X_data.ndim != 1:
+        raise ValueError("X_data must be a 1-D array, got shape %s" % (X_data.shape,))
     nnz = X_data.shape[0]
+    X_row = _same(X_row, "X_row", (nnz,), "X_data")
+    X_col = _same(X_col, "X_col", (nnz,), "X_data")
     x = _c(X_data, dt)
     row, col = _c(X_row, np.int32), _c(X_col, np.int32)
     ths, thr = _c(theta_vi_shape, dt), _c(theta_vi_rate, dt)
@@ -101,8 +129,12 @@ def compute_Xphi_data_numpy(X, theta, beta, theta_ix=None):
 
 def compute_loading_shape_update(Xphi_data, X_keep, nkeep, shape_prior):
     """Gamma shape update for theta or beta (hpf_numba.py:128-156)."""
+    Xphi_data = _matrix(Xphi_data, "Xphi_data")
     dt = Xphi_data.dtype
     nnz, nfactors = Xphi_data.shape
+    X_keep = _same(X_keep, "X_keep", (nnz,), "the rows of Xphi_data")
+    if int(nkeep) < 0:
+        raise ValueError("nkeep must be at least 0, got %d" % int(nkeep))
     out = np.empty((int(nkeep), nfactors), dtype=dt)
     _lib.check(_lib.load().schpf_shape_update(
         _code(dt), nnz, nfactors, _p(_c(Xphi_data, dt)), _p(_c(X_keep, np.int32)), int(nkeep),
@@ -113,6 +145,13 @@ def compute_loading_shape_update(Xphi_data, X_keep, nkeep, shape_prior):
 def compute_loading_rate_update(prior_vi_shape, prior_vi_rate,
                                 other_loading_vi_shape, other_loading_vi_rate):
     """Gamma rate update for theta or beta (hpf_numba.py:159-177)."""
+    prior_vi_shape = np.asarray(prior_vi_shape)
+    if prior_vi_shape.ndim != 1:
+        raise ValueError("prior_vi_shape must be a 1-D array, got shape %s" % (prior_vi_shape.shape,))
+    other_loading_vi_shape = _matrix(other_loading_vi_shape, "other_loading_vi_shape")
+    prior_vi_rate = _same(prior_vi_rate, "prior_vi_rate", prior_vi_shape.shape, "prior_vi_shape")
+    other_loading_vi_rate = _same(other_loading_vi_rate, "other_loading_vi_rate", other_loading_vi_shape.shape,
+                                  "other_loading_vi_shape")
     dt = prior_vi_shape.dtype
     n = prior_vi_shape.shape[0]
     m, nfactors = other_loading_vi_shape.shape
@@ -125,6 +164,8 @@ def compute_loading_rate_update(prior_vi_shape, prior_vi_rate,
 
 def compute_capacity_rate_update(loading_vi_shape, loading_vi_rate, prior_rate):
     """Gamma rate update for xi or eta (hpf_numba.py:180-188)."""
+    loading_vi_shape = _matrix(loading_vi_shape, "loading_vi_shape")
+    loading_vi_rate = _same(loading_vi_rate, "loading_vi_rate", loading_vi_shape.shape, "loading_vi_shape")
     dt = loading_vi_shape.dtype
     n, nfactors = loading_vi_shape.shape
     out = np.empty((n,), dtype=dt)
