@@ -610,6 +610,45 @@ int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const i
                           const int32_t *labels, int ngroups, int64_t *n, int64_t *zeros, int64_t *ties, int64_t *nexpr,
                           int64_t *rank2);
 
+/* Rank sums between pairs of groups: the exact integers behind "which genes tell cluster a from cluster b" --
+ * the Mann-Whitney test of group a against group b alone, for every requested pair and every gene.  Twice a U is an
+ * integer; every output below is an integer sum, exact in any order, equal bit for bit however the work was scheduled.
+ * Input.  The matrix and the labels as for schpf_rank_sums: indptr[J + 1] (int64), indices (int32 cell ids, strictly
+ *   ascending within a gene), data (float32, finite and >= 0; -0.0 and stored zeros are zeros), nnz = indptr[J] < 2^32;
+ *   labels[N] (int32) in [-1, G).  pairs[P x 2] (int32, row-major): rows (a, b) with a != b, both in [0, G).  A pair may be
+ *   repeated and may appear in both orders; a group may appear in no pair.
+ *   N < 2^21, G >= 1, G * J < 2^31, P >= 0 and P * J < 2^31: refused before anything is read.  The refusals of
+ *   schpf_rank_sums keep their text and their order; after the labels comes
+ *     "pairs must name two different groups in [0, ngroups); offending pair M"  (M the smallest such row)
+ *   A refused call leaves the outputs untouched.
+ * Definition.  Cells outside the pair do not exist for that pair: cells labelled -1 or in a third group are not ranked
+ *   (schpf_rank_sums ranks the -1 cells).  For gene j and group g:  nexpr[g, j] = the cells of g with a positive value,
+ *   z_g = n_g - nexpr[g, j].  For a pair (a, b) and a distinct positive value v of gene j:  c_a(v), c_b(v) = the cells of
+ *   each group with that value (float32 equality);  below_b(v) = z_b + the cells of b with 0 < value < v.
+ * Output, all int64.  n[G]: the cells per group.  nexpr[G x J], row-major by group -- both as schpf_rank_sums gives them.
+ *   u2[P x J] = z_a z_b + the sum over v of c_a(v) (2 below_b(v) + c_b(v)): twice the Mann-Whitney U of a over b (twice the
+ *   rank sum of a within a ∪ b is u2 + n_a (n_a + 1)).  ties[P x J] = (t_0^3 - t_0) + the sum over v of (t_v^3 - t_v), t_0 =
+ *   z_a + z_b, t_v = c_a(v) + c_b(v).  An empty group gives u2 = 0.  u2 of (b, a) is 2 n_a n_b - u2 of (a, b); the ties are
+ *   equal.
+ * N = 0, J = 0 or P = 0 succeeds; N = 0 or J = 0 reads no input, and every output that is not NULL is written as zeros
+ *   where it has a size.  u2 and ties may be NULL when P = 0.  Bad arguments fail with a message.  Stateless; device
+ *   memory that cannot be had returns SCHPF_ERR_NO_MEMORY (scratch: 28 nnz + 4 G J + 16 P bytes and the sort's own, about
+ *   8 nnz -- O(nnz + G J + P J)).
+ * _device: indptr, indices, data, labels, pairs and the four outputs are DEVICE pointers on `device`; stream as in
+ *   schpf_knn_device; synchronised before the call returns.
+ * schpf_pair_rank_sums: host pointers, staged through the device; the same result.
+ * schpf_debug_pair_rank_sums: test hook (host only, no GPU needed): the serial restatement of the definition, one std::sort
+ *   per gene and one merge of two lists per pair, which both must match bit for bit. */
+int schpf_pair_rank_sums_device(int device, void *stream, int ncells, int ngenes, const int64_t *indptr, const int32_t *indices,
+                                const float *data, const int32_t *labels, int ngroups, const int32_t *pairs, int npairs, int64_t *n,
+                                int64_t *nexpr, int64_t *u2, int64_t *ties);
+int schpf_pair_rank_sums(int device, int ncells, int ngenes, const int64_t *indptr, const int32_t *indices, const float *data,
+                         const int32_t *labels, int ngroups, const int32_t *pairs, int npairs, int64_t *n, int64_t *nexpr,
+                         int64_t *u2, int64_t *ties);
+int schpf_debug_pair_rank_sums(int ncells, int ngenes, const int64_t *indptr, const int32_t *indices, const float *data,
+                               const int32_t *labels, int ngroups, const int32_t *pairs, int npairs, int64_t *n, int64_t *nexpr,
+                               int64_t *u2, int64_t *ties);
+
 /* Simulated doublets: rows that are the sum of two observed cells, the first step of Scrublet's doublet
  * score.  Integer work whose result is fully determined: every schedule gives the same bits.
  * Parents.  Simulated row s has the parents (a, b):  w = philox4x32_10(counter (s & 0xffffffff, s >> 32, 0, 1), key (low,

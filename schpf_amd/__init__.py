@@ -13,7 +13,7 @@ from .thinning import thin_counts
 from .neighbors import knn, knn_graph, knn_connectivities, louvain, modularity
 from .topology import connected_components, cluster_graph, absorb_small, paga
 from .paths import geodesic_distances, pseudotime, farthest_landmarks, landmark_isomap
-from .markers import rank_sums, rank_genes_groups
+from .markers import rank_sums, rank_genes_groups, pair_rank_sums, rank_genes_pairs
 from .doublets import simulate_doublets, doublet_scores
 from .qc import qc_metrics, submatrix, filter_counts
 from .aggregate import group_stats, pseudobulk, group_codes
@@ -23,7 +23,7 @@ import schpf.scHPF_  # noqa: E402,F401
 
 __all__ = ["__version__", "hpf_hip", "loss", "preprocessing", "DeviceCAVI", "HPF_Gamma", "scHPF", "load_model",
            "save_model", "combine_across_cells", "run_trials", "run_trials_pool", "thin_counts", "knn", "knn_graph",
-           "knn_connectivities", "louvain", "modularity", "rank_sums", "rank_genes_groups", "simulate_doublets",
+           "knn_connectivities", "louvain", "modularity", "rank_sums", "rank_genes_groups", "pair_rank_sums", "rank_genes_pairs", "simulate_doublets",
            "doublet_scores", "qc_metrics", "submatrix", "filter_counts", "group_stats", "pseudobulk", "group_codes",
            "connected_components", "cluster_graph", "absorb_small", "paga", "geodesic_distances", "pseudotime",
            "farthest_landmarks", "landmark_isomap"]

@@ -104,6 +104,9 @@ SIGNATURES = {
     "schpf_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
     "schpf_debug_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp],
+    "schpf_pair_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp],
+    "schpf_pair_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp],
+    "schpf_debug_pair_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp],
     "schpf_doublet_parents": [_i64, _i64, _i64, ctypes.c_uint64, _vp],
     "schpf_doublet_parents_device": [_int, _vp, _i64, _i64, _i64, ctypes.c_uint64, _vp],
     "schpf_doublet_rows_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],
@@ -256,7 +259,8 @@ def check(status):
     if status != 0:
         msg = load().schpf_last_error().decode("utf-8", "replace")
         if status != ERR_NO_MEMORY and ("must be" in msg or "out of range" in msg or "unknown" in msg
-                                        or "thinning needs" in msg or "neighbour lists must hold" in msg or "may overflow" in msg):
+                                        or "thinning needs" in msg or "neighbour lists must hold" in msg or "may overflow" in msg
+                                        or "pairs must name" in msg):
             raise ValueError(msg)
         raise SchpfHipError(msg, status)
 

@@ -158,6 +158,11 @@ def _parser():
                        help="With -i and --clusters: also write the Wilcoxon rank-sum test of every gene, each cluster "
                             "against all the other cells, as marker_scores.txt and marker_pvals_adj.txt (genes x clusters); "
                             "with --genefile also ranked_markers.txt, the gene names by descending score per cluster.")
+    score.add_argument("--marker-pairs", default=None, choices=["all", "neighbors"], metavar="WHICH",
+                       help="With --markers: also write the rank-sum test of every gene between pairs of clusters, each pair "
+                            "ranked alone -- all: every pair a < b; neighbors: the pairs with an edge of the k-NN graph between "
+                            "them -- as pair_marker_pairs.txt (pairs x 2), pair_marker_scores.txt and "
+                            "pair_marker_pvals_adj.txt (genes x pairs); with --genefile also ranked_pair_markers.txt.")
     score.add_argument("--pseudobulk", default=False, action="store_true",
                        help="With -i and --clusters and / or --sample-ids: also write the counts of every gene summed over the "
                             "cells of each group as pseudobulk_counts.txt (groups x genes, integers), the groups as "
@@ -447,6 +452,22 @@ def _score(args, outprefix):
                         ranks = np.argsort(found["scores"].T, axis=0)[::-1]
                         ranked = np.stack([genes[ranks[:, c], name_col] for c in range(ranks.shape[1])]).T
                         np.savetxt(outprefix + "ranked_markers.txt", ranked, fmt="%s", delimiter="\t")
+                    if args.marker_pairs is not None:
+                        from .markers import rank_genes_pairs
+                        print("Saving pairwise marker genes.....")
+                        pairs = args.marker_pairs
+                        if pairs == "neighbors":
+                            from .neighbors import knn_graph
+                            from .topology import paga
+                            count = np.asarray(paga(knn_graph(indices, distances, indices.shape[0]), labels)["count"])
+                            pairs = np.stack(np.nonzero(np.triu((count + count.T) > 0, 1)), axis=1).astype(np.int32)
+                        found = rank_genes_pairs(data, labels, pairs=pairs)
+                        np.savetxt(outprefix + "pair_marker_pairs.txt", found["pairs"].reshape(-1, 2), fmt="%d", delimiter="\t")
+                        np.savetxt(outprefix + "pair_marker_scores.txt", found["scores"].T, delimiter="\t")
+                        np.savetxt(outprefix + "pair_marker_pvals_adj.txt", found["pvals_adj"].T, delimiter="\t")
+                        if args.genefile is not None:
+                            ranked = genes[:, name_col][np.argsort(found["scores"].T, axis=0)[::-1]]   # genes x pairs
+                            np.savetxt(outprefix + "ranked_pair_markers.txt", ranked, fmt="%s", delimiter="\t")
         root = args.pseudotime_root
         if args.pseudotime_root_cluster is not None and labels is not None:
             root = np.asarray(labels) == args.pseudotime_root_cluster
@@ -477,8 +498,12 @@ def _score(args, outprefix):
     for name in ("pseudotime_root", "pseudotime_root_cluster"):
         if getattr(args, name) is None:
             delattr(args, name)              # ... or a pseudotime
+    if args.marker_pairs is not None and not args.markers:
+        raise ValueError("--marker-pairs needs the marker genes (-i X --knn K --knn-graph M --clusters --markers)")
     if not args.markers:
         del args.markers                     # ... and without their marker genes
+    if args.marker_pairs is None:
+        del args.marker_pairs                # ... or the genes between pairs of clusters
     if args.pseudobulk:
         from .aggregate import pseudobulk
         print("Saving pseudobulk.....")

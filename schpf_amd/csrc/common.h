@@ -241,6 +241,29 @@ inline std::string rank_sums_bad_cells(int64_t gene)
 inline std::string rank_sums_bad_values(int64_t gene) { return "values must be finite and >= 0; offending gene " + std::to_string(gene); }
 inline std::string rank_sums_bad_labels(int64_t cell) { return "labels must be in [-1, ngroups); offending cell " + std::to_string(cell); }
 
+// What schpf_pair_rank_sums, schpf_pair_rank_sums_device and schpf_debug_pair_rank_sums refuse alike before anything is
+// read: the refusals of the rank sums in their order, with those of the pairs where the sizes and the pointers are asked
+inline const char *pair_rank_sums_bad_args(int ncells, int ngenes, int ngroups, const void *indptr, const void *labels,
+                                           const void *pairs, int npairs, const void *n, const void *nexpr, const void *u2,
+                                           const void *ties)
+{
+    if (ncells < 0 || ncells >= RANK_SUMS_MAX_CELLS) return "ncells must be in [0, 2^21)";
+    if (ngenes < 0) return "ngenes must be >= 0";
+    if (ngroups < 1) return "ngroups must be at least 1";
+    if ((int64_t)ngroups * (int64_t)ngenes >= (int64_t)1 << 31) return "ngroups * ngenes must be below 2^31";
+    if (npairs < 0) return "npairs must be >= 0";
+    if ((int64_t)npairs * (int64_t)ngenes >= (int64_t)1 << 31) return "npairs * ngenes must be below 2^31";
+    if (ncells == 0 || ngenes == 0) return nullptr;
+    if (!indptr || !labels) return "indptr and labels must not be NULL";
+    if (npairs > 0 && !pairs) return "pairs must not be NULL";
+    if (!n || !nexpr || (npairs > 0 && (!u2 || !ties))) return "n, nexpr, u2 and ties must not be NULL";
+    return nullptr;
+}
+inline std::string pair_rank_sums_bad_pairs(int64_t pair)
+{
+    return "pairs must name two different groups in [0, ngroups); offending pair " + std::to_string(pair);
+}
+
 // RAII device buffer
 struct DevBuf {
     void *p = nullptr;

@@ -928,6 +928,88 @@ int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const i
     });
 }
 
+// pair_rank_sums.hip restated: the definition of include/schpf_hip.h gene by gene -- the positive entries of
+// the cells that are in a group sorted by (value, group) with one std::sort, cut into every group's list of distinct values
+// with their counts, then for every pair one merge of its two lists
+int schpf_debug_pair_rank_sums(int ncells, int ngenes, const int64_t *indptr, const int32_t *indices, const float *data,
+                               const int32_t *labels, int ngroups, const int32_t *pairs, int npairs, int64_t *n, int64_t *nexpr,
+                               int64_t *u2, int64_t *ties)
+{
+    if (const char *why = pair_rank_sums_bad_args(ncells, ngenes, ngroups, indptr, labels, pairs, npairs, n, nexpr, u2, ties))
+        return fail("%s", why);
+    return guarded([&] {
+        const int64_t N = ncells, J = ngenes, G = ngroups, P = npairs;
+        if (N == 0 || J == 0) {
+            if (n) std::fill(n, n + G, (int64_t)0);
+            if (nexpr) std::fill(nexpr, nexpr + G * J, (int64_t)0);
+            if (u2) std::fill(u2, u2 + P * J, (int64_t)0);
+            if (ties) std::fill(ties, ties + P * J, (int64_t)0);
+            return;
+        }
+        if (indptr[0] != 0) throw std::invalid_argument(rank_sums_bad_indptr(0));
+        for (int64_t j = 0; j < J; ++j)
+            if (indptr[j + 1] < indptr[j]) throw std::invalid_argument(rank_sums_bad_indptr(j));
+        const int64_t nnz = indptr[J];
+        if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
+        for (int64_t j = 0; j < J; ++j)
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= N || (e > indptr[j] && indices[e - 1] >= indices[e]))
+                    throw std::invalid_argument(rank_sums_bad_cells(j));
+        for (int64_t j = 0; j < J; ++j)
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (!(data[e] >= 0.0f && std::isfinite(data[e]))) throw std::invalid_argument(rank_sums_bad_values(j));
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] < -1 || labels[i] >= G) throw std::invalid_argument(rank_sums_bad_labels(i));
+        for (int64_t p = 0; p < P; ++p) {
+            const int64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+            if (a < 0 || a >= G || b < 0 || b >= G || a == b) throw std::invalid_argument(pair_rank_sums_bad_pairs(p));
+        }
+
+        std::vector<int64_t> cnt((size_t)G, 0), expr((size_t)(G * J), 0), u((size_t)(P * J), 0), tie((size_t)(P * J), 0);
+        for (int64_t i = 0; i < N; ++i)
+            if (labels[i] >= 0) ++cnt[(size_t)labels[i]];
+        std::vector<std::pair<float, int32_t>> pos;                          // (value, group) of a gene's positive entries
+        std::vector<std::vector<std::pair<float, int64_t>>> list((size_t)G);   // per group: (distinct value, cells), ascending
+        for (int64_t j = 0; j < J; ++j) {
+            pos.clear();
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (data[e] > 0.0f && labels[indices[e]] >= 0) pos.emplace_back(data[e], labels[indices[e]]);
+            std::sort(pos.begin(), pos.end());
+            for (size_t x = 0; x < pos.size();) {
+                size_t y = x;
+                while (y < pos.size() && pos[y] == pos[x]) ++y;
+                list[(size_t)pos[x].second].emplace_back(pos[x].first, (int64_t)(y - x));
+                expr[(size_t)(pos[x].second * J + j)] += (int64_t)(y - x);
+                x = y;
+            }
+            for (int64_t p = 0; p < P; ++p) {
+                const int64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+                const auto &la = list[(size_t)a], &lb = list[(size_t)b];
+                const int64_t za = cnt[(size_t)a] - expr[(size_t)(a * J + j)], zb = cnt[(size_t)b] - expr[(size_t)(b * J + j)];
+                const int64_t t0 = za + zb;
+                int64_t below_b = zb, sum = za * zb, cubes = t0 * t0 * t0 - t0;
+                for (size_t x = 0, y = 0; x < la.size() || y < lb.size();) {   // the distinct values of a and b, ascending
+                    const bool in_a = x < la.size() && (y == lb.size() || la[x].first <= lb[y].first);
+                    const bool in_b = y < lb.size() && (x == la.size() || lb[y].first <= la[x].first);
+                    const int64_t ca = in_a ? la[x].second : 0, cb = in_b ? lb[y].second : 0, t = ca + cb;
+                    sum += ca * (2 * below_b + cb);
+                    cubes += t * t * t - t;
+                    below_b += cb;
+                    x += in_a;
+                    y += in_b;
+                }
+                u[(size_t)(p * J + j)] = sum;
+                tie[(size_t)(p * J + j)] = cubes;
+            }
+            for (const auto &e : pos) list[(size_t)e.second].clear();
+        }
+        std::copy(cnt.begin(), cnt.end(), n);
+        std::copy(expr.begin(), expr.end(), nexpr);
+        if (P) std::copy(u.begin(), u.end(), u2);
+        if (P) std::copy(tie.begin(), tie.end(), ties);
+    });
+}
+
 // the draw of doublets.h, one simulated row after the other: row first + t for t < n_sim
 int schpf_doublet_parents(int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed, int32_t *parents)
 {

@@ -392,6 +392,23 @@ class scHPF(BaseEstimator):
             labels = self.clusters(k=k, metric=metric, method=method, resolution=resolution, device=kwargs.get("device"))
         return rank_genes_groups(X, labels, **kwargs)
 
+    def pair_markers(self, X, labels=None, pairs="neighbors", k=15, metric="euclidean", method="jaccard", resolution=1.0, **kwargs):
+        """The genes that tell two clusters of this model's cells apart: the Wilcoxon rank-sum test of every gene of the
+        count matrix X (cells x genes, what `fit` took) between pairs of clusters, each pair ranked alone, on the GPU -- the
+        dict of schpf_amd.rank_genes_pairs (scores, pvals, pvals_adj, logfoldchanges, ..., pairs; kwargs go there:
+        tie_correct, target_sum, device).  pairs="neighbors": the pairs a < b of clusters with at least one edge of the
+        k-NN graph between them (`cluster_graph(k, labels)["count"]`, either direction); "all" or rows (a, b) are passed
+        through.  labels=None: the clusters are `clusters(k, metric, method, resolution)`.  An addition to the reference's
+        surface."""
+        from .markers import rank_genes_pairs
+        if labels is None:
+            labels = self.clusters(k=k, metric=metric, method=method, resolution=resolution, device=kwargs.get("device"))
+        if isinstance(pairs, str) and pairs == "neighbors":
+            count = np.asarray(self.cluster_graph(k=k, labels=labels, metric=metric, device=kwargs.get("device"))["count"])
+            a, b = np.nonzero(np.triu((count + count.T) > 0, 1))
+            pairs = np.stack([a, b], axis=1).astype(np.int32)
+        return rank_genes_pairs(X, labels, pairs=pairs, **kwargs)
+
     def pseudobulk(self, X, by=None, min_cells=1, device=None, **clusters_kwargs):
         """The pseudobulk table of the count matrix X (cells x genes, what `fit` took): per group of cells the exact sums of
         every gene's counts, the cells, and the fraction, mean and variance per group, on the GPU -- the dict of
