@@ -4,7 +4,9 @@
 // entry, so a row may be of any length and no thread walks one.
 //
 // components: min-label hooking with pointer doubling on p[n], p[i] = i at the start
-//   components_within_kernel    within[i] >= -1: the smallest offending vertex of each workgroup
+//   (graph_device.h: the columns, and for the cluster graph the values and the labels; every check leaves its smallest
+//   offender in a word of the call's one record, device_call.h, which is fetched once)
+//   components_within_kernel    within[i] >= -1: the smallest offending vertex
 //   components_edges_kernel     the number of entries that are edges (one integer add per wavefront)
 //   per hook round:
 //   components_hook_kernel      per edge (i, j) with p[i] != p[j]: atomicMin(p[max], min) and flags[0] = 1
@@ -18,7 +20,8 @@
 //   sizes by integer atomicAdd (count_keys: runs in registers, LDS bins, and memory for the many small ones)
 //   components_stats_kernel     C, the largest size, the components of size 1
 // cluster graph: one aggregation step of louvain.hip with the caller's labels
-//   cluster_labels_kernel       labels[i] in [-1, G): the smallest offending vertex; cluster_cells_kernel: group_cells
+//   labels_check_kernel         (graph_device.h) labels[i] in [-1, G): the smallest offending vertex
+//   cluster_cells_kernel        group_cells
 //   cluster_records_kernel      per entry the key a * G + b (G * G: does not count) and the value (1, q)
 //   (rocPRIM radix sort over the occupied bits, reduce-by-key with the integer sum of both members)
 //   cluster_scatter_kernel      the reduced records into the zeroed tables
@@ -47,6 +50,8 @@ struct TallyPlus {
 };
 
 enum { W_EDGES = 0, W_LARGEST, W_SINGLE, W_COUNT_C, W_WORDS };
+// the smallest offenders of a call, in the order they are asked; BAD_ITEMS: `within` (components), `labels` (cluster graph)
+enum { BAD_COLUMNS = 0, BAD_VALUES, BAD_ITEMS, BAD_COUNT };
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 {
@@ -102,14 +107,15 @@ __device__ __forceinline__ bool is_edge(int i, int j, const int32_t *__restrict_
     return wi >= 0 && wi == within[j];
 }
 
-__global__ __launch_bounds__(256) void components_within_kernel(const int32_t *__restrict__ within, int64_t n, int *__restrict__ part)
+__global__ __launch_bounds__(256) void components_within_kernel(const int32_t *__restrict__ within, int64_t n,
+                                                                unsigned long long *__restrict__ word)
 {
-    int bad = INT_MAX;
+    unsigned long long bad = NONE;
     GRID_STRIDE(i, n)
     {
-        if (within[i] < -1) bad = min(bad, (int)i);
+        if (within[i] < -1) offends(bad, i);
     }
-    block_min(bad, part);
+    report_min(word, bad);
 }
 
 __global__ __launch_bounds__(256) void components_init_kernel(int64_t n, int32_t *__restrict__ p)
@@ -202,16 +208,6 @@ __global__ __launch_bounds__(256) void components_stats_kernel(int64_t n, const 
     if (blockIdx.x == 0 && threadIdx.x == 0) words[W_COUNT_C] = (unsigned long long)(renum[n - 1] + root[n - 1]);
 }
 
-__global__ __launch_bounds__(256) void cluster_labels_kernel(const int32_t *__restrict__ labels, int64_t n, int G, int *__restrict__ part)
-{
-    int bad = INT_MAX;
-    GRID_STRIDE(i, n)
-    {
-        if (labels[i] < -1 || labels[i] >= G) bad = min(bad, (int)i);
-    }
-    block_min(bad, part);
-}
-
 __global__ __launch_bounds__(256) void cluster_cells_kernel(const int32_t *__restrict__ labels, int64_t n, sum_t *__restrict__ cells)
 {
     count_keys(n, cells, [&](int64_t i) { return (int)labels[i]; });
@@ -247,13 +243,6 @@ __global__ __launch_bounds__(256) void cluster_scatter_kernel(const uint64_t *__
     }
 }
 
-// a grid of at most COUNT_BLOCKS workgroups for the kernels that end in one atomic per wavefront or workgroup
-#define LAUNCH_FEW(kernel, n, st, ...)                                                                                      \
-    do {                                                                                                                    \
-        hipLaunchKernelGGL(kernel, dim3(std::min<unsigned>(grid_for(n), COUNT_BLOCKS)), dim3(256), 0, st, __VA_ARGS__);    \
-        HIPCHK(hipGetLastError());                                                                                          \
-    } while (0)
-
 int doubling_passes(int n)   // ceil(log2 n) passes bring a tree of depth n - 1 to depth 1, and one more sees no change
 {
     int l = 0;
@@ -267,29 +256,19 @@ void components_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *ind
                           int32_t *comp, int64_t *stats)
 {
     const size_t N = (size_t)n;
-    const int64_t blocks_n = grid_for(n), blocks_e = grid_for(nnz);
-    DevBuf rowof, part_col, part_val, part_within, bad, bad_within;
-    bad.alloc(2 * sizeof(int));
-    bad_within.alloc(2 * sizeof(int));
+    DevBuf rowof;
+    Offenders<BAD_COUNT> w;   // no values here: BAD_VALUES stays NONE
+    w.reset(st);
     if (nnz > 0) {
         rowof.alloc((size_t)nnz * sizeof(int32_t));
-        part_col.alloc((size_t)blocks_e * sizeof(int));
-        part_val.alloc((size_t)blocks_e * sizeof(int));
-        LAUNCH(louvain_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
-        LAUNCH(louvain_check_kernel<false>, nnz, st, indptr, indices, (const double *)nullptr, rowof.as<int32_t>(), n, nnz,
-               part_col.as<int>(), part_val.as<int>());
+        LAUNCH(entry_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
+        LAUNCH(graph_entries_check_kernel<false>, nnz, st, indptr, indices, (const double *)nullptr, rowof.as<int32_t>(), n, nnz,
+               w.dev() + BAD_COLUMNS, w.dev() + BAD_VALUES);
     }
-    if (within) {
-        part_within.alloc((size_t)blocks_n * sizeof(int));
-        LAUNCH(components_within_kernel, n, st, within, (int64_t)n, part_within.as<int>());
-    }
-    HIPCHK(launch_knn_bad(part_col.as<int>(), nnz > 0 ? blocks_e : 0, nullptr, 0, bad.as<int>(), st));
-    HIPCHK(launch_knn_bad(part_within.as<int>(), within ? blocks_n : 0, nullptr, 0, bad_within.as<int>(), st));
-    int h_bad[2], h_bad_within[2];
-    HIPCHK(hipMemcpyAsync(h_bad, bad.p, sizeof h_bad, hipMemcpyDeviceToHost, st));
-    d2h(h_bad_within, bad_within, sizeof h_bad_within, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument(graph_bad_columns(h_bad[0]));
-    if (h_bad_within[0] != INT_MAX) throw std::invalid_argument(components_bad_within(h_bad_within[0]));
+    if (within) LAUNCH(components_within_kernel, n, st, within, (int64_t)n, w.dev() + BAD_ITEMS);
+    w.fetch(st);
+    w.refuse(BAD_COLUMNS, graph_bad_columns);
+    w.refuse(BAD_ITEMS, components_bad_within);
 
     DevBuf p, flags, words, root, renum, size;
     Scratch temp;
@@ -304,7 +283,7 @@ void components_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *ind
 
     int64_t rounds = 0, passes = 0;
     if (nnz > 0) {
-        LAUNCH_FEW(components_edges_kernel, nnz, st, rowof.as<int32_t>(), indices, within, nnz, words.as<unsigned long long>());
+        LAUNCH_BOUNDED(components_edges_kernel, nnz, COUNT_BLOCKS, st, rowof.as<int32_t>(), indices, within, nnz, words.as<unsigned long long>());
         std::vector<int> h_flags((size_t)L + 1);
         for (bool again = true, hook = true; again;) {
             HIPCHK(hipMemsetAsync(flags.p, 0, h_flags.size() * sizeof(int), st));
@@ -325,8 +304,8 @@ void components_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *ind
     temp.run([&](void *t, size_t &b) {
         return rocprim::exclusive_scan(t, b, root.as<int64_t>(), renum.as<int64_t>(), (int64_t)0, N, rocprim::plus<int64_t>(), st);
     });
-    LAUNCH_FEW(components_label_kernel, n, st, (int64_t)n, p.as<int32_t>(), renum.as<int64_t>(), comp, size.as<int>());
-    LAUNCH_FEW(components_stats_kernel, n, st, (int64_t)n, size.as<int>(), root.as<int64_t>(), renum.as<int64_t>(),
+    LAUNCH_BOUNDED(components_label_kernel, n, COUNT_BLOCKS, st, (int64_t)n, p.as<int32_t>(), renum.as<int64_t>(), comp, size.as<int>());
+    LAUNCH_BOUNDED(components_stats_kernel, n, COUNT_BLOCKS, st, (int64_t)n, size.as<int>(), root.as<int64_t>(), renum.as<int64_t>(),
            words.as<unsigned long long>());
     unsigned long long h_words[W_WORDS];
     d2h(h_words, words, sizeof h_words, st);
@@ -343,40 +322,32 @@ void cluster_graph_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *
                              const int32_t *labels, int G, int64_t *group_cells, int64_t *count, int64_t *weight, double *wmax)
 {
     const size_t GG = (size_t)G * (size_t)G;
-    const int64_t blocks_n = grid_for(n), blocks_e = grid_for(nnz);
-    DevBuf rowof, part_col, part_val, part_lab, bad, bad_lab, d_wmax;
+    DevBuf rowof, d_wmax;
     Scratch temp;
-    bad.alloc(2 * sizeof(int));
-    bad_lab.alloc(2 * sizeof(int));
+    Offenders<BAD_COUNT> w;
+    w.reset(st);
     d_wmax.alloc(sizeof(double), true, st);
     if (nnz > 0) {
         rowof.alloc((size_t)nnz * sizeof(int32_t));
-        part_col.alloc((size_t)blocks_e * sizeof(int));
-        part_val.alloc((size_t)blocks_e * sizeof(int));
-        LAUNCH(louvain_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
-        LAUNCH(louvain_check_kernel<false>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, part_col.as<int>(),
-               part_val.as<int>());
+        LAUNCH(entry_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
+        LAUNCH(graph_entries_check_kernel<false>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, w.dev() + BAD_COLUMNS,
+               w.dev() + BAD_VALUES);
         if (data)
             temp.run([&](void *t, size_t &b) { return rocprim::reduce(t, b, data, d_wmax.as<double>(), 0.0, (size_t)nnz, Larger(), st); });
     }
-    part_lab.alloc((size_t)blocks_n * sizeof(int));
-    LAUNCH(cluster_labels_kernel, n, st, labels, (int64_t)n, G, part_lab.as<int>());
-    HIPCHK(launch_knn_bad(part_col.as<int>(), nnz > 0 ? blocks_e : 0, part_val.as<int>(), nnz > 0 ? blocks_e : 0, bad.as<int>(), st));
-    HIPCHK(launch_knn_bad(part_lab.as<int>(), blocks_n, nullptr, 0, bad_lab.as<int>(), st));
-    int h_bad[2], h_bad_lab[2];
+    LAUNCH(labels_check_kernel, n, st, labels, (int64_t)n, G, w.dev() + BAD_ITEMS);
     double h_wmax = 0.0;
-    HIPCHK(hipMemcpyAsync(h_bad, bad.p, sizeof h_bad, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&h_wmax, d_wmax.p, sizeof h_wmax, hipMemcpyDeviceToHost, st));
-    d2h(h_bad_lab, bad_lab, sizeof h_bad_lab, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument(graph_bad_columns(h_bad[0]));
-    if (h_bad[1] != INT_MAX) throw std::invalid_argument(louvain_bad_values(h_bad[1]));
-    if (h_bad_lab[0] != INT_MAX) throw std::invalid_argument(cluster_graph_bad_labels(h_bad_lab[0]));
+    w.fetch(st);
+    w.refuse(BAD_COLUMNS, graph_bad_columns);
+    w.refuse(BAD_VALUES, louvain_bad_values);
+    w.refuse(BAD_ITEMS, cluster_graph_bad_labels);
     if (!data && nnz > 0) h_wmax = 1.0;   // all ones
 
     HIPCHK(hipMemsetAsync(group_cells, 0, (size_t)G * sizeof(int64_t), st));
     HIPCHK(hipMemsetAsync(count, 0, GG * sizeof(int64_t), st));
     if (weight) HIPCHK(hipMemsetAsync(weight, 0, GG * sizeof(int64_t), st));
-    LAUNCH_FEW(cluster_cells_kernel, n, st, labels, (int64_t)n, reinterpret_cast<sum_t *>(group_cells));
+    LAUNCH_BOUNDED(cluster_cells_kernel, n, COUNT_BLOCKS, st, labels, (int64_t)n, reinterpret_cast<sum_t *>(group_cells));
     if (nnz > 0) {
         DevBuf key_a, key_b, val_a, val_b, runs;
         key_a.alloc((size_t)nnz * sizeof(uint64_t));
@@ -422,7 +393,7 @@ int schpf_components_device(int device, void *stream, int n, const int64_t *indp
         use_device(device);
         std::unique_ptr<TempStream> own;
         hipStream_t st = pick_stream(stream, own);
-        const int64_t nnz = louvain_indptr_on_device(st, n, indptr);
+        const int64_t nnz = indptr_on_device(st, n, indptr, louvain_bad_indptr);
         if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
         int64_t result[6];
         components_on_device(st, n, nnz, indptr, indices, within, comp, result);
@@ -443,7 +414,7 @@ int schpf_components(int device, int n, const int64_t *indptr, const int32_t *in
         TempStream ts;
         DevBuf d_indptr, d_indices, d_within, d_comp;
         h2d<int64_t>(d_indptr, indptr, (size_t)n + 1, ts.st);
-        const int64_t nnz = louvain_indptr_on_device(ts.st, n, d_indptr.as<int64_t>());   // the host's indptr[n] if it passes
+        const int64_t nnz = indptr_on_device(ts.st, n, d_indptr.as<int64_t>(), louvain_bad_indptr);   // the host's indptr[n] if it passes
         if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
         h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);
         if (within) h2d<int32_t>(d_within, within, (size_t)n, ts.st);
@@ -465,7 +436,7 @@ int schpf_cluster_graph_device(int device, void *stream, int n, const int64_t *i
         use_device(device);
         std::unique_ptr<TempStream> own;
         hipStream_t st = pick_stream(stream, own);
-        const int64_t nnz = n ? louvain_indptr_on_device(st, n, indptr) : 0;
+        const int64_t nnz = n ? indptr_on_device(st, n, indptr, louvain_bad_indptr) : 0;
         if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
         double result = 0.0;
         cluster_graph_on_device(st, n, nnz, indptr, indices, data, labels, ngroups, group_cells, count, weight, &result);
@@ -485,7 +456,7 @@ int schpf_cluster_graph(int device, int n, const int64_t *indptr, const int32_t 
         int64_t nnz = 0;
         if (n) {
             h2d<int64_t>(d_indptr, indptr, (size_t)n + 1, ts.st);
-            nnz = louvain_indptr_on_device(ts.st, n, d_indptr.as<int64_t>());
+            nnz = indptr_on_device(ts.st, n, d_indptr.as<int64_t>(), louvain_bad_indptr);
         }
         if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
         h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);

@@ -1,15 +1,11 @@
-// What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip, group_stats.hip): the
-// loaders for the index and value kinds of include/schpf_hip.h, the matrix record, the wavefront minimum of the validation
-// kernels, the device / stream / grid choices of an entry point, and -- in csr_checks, for qc.hip and group_stats.hip --
-// the validation of a count CSR: the two kernels, the words of their smallest offenders, and the bisection of a row.
+// What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip, group_stats.hip) on
+// top of the scaffold of device_call.h: the loaders for the index and value kinds of include/schpf_hip.h, the matrix record,
+// the bisection of a row, and -- in csr_checks, for qc.hip and group_stats.hip -- the validation of a count CSR: the two
+// kernels and the words of their smallest offenders.
 #pragma once
-#include <algorithm>
-#include <cstdint>
-#include <memory>
-
 #include <rocprim/device/device_scan.hpp>
 
-#include "common.h"
+#include "device_call.h"
 #include "philox.h"
 
 namespace schpf {
@@ -29,15 +25,6 @@ __device__ __forceinline__ double load_value(const void *p, int kind, int64_t j)
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 struct Matrix {   // a CSR in device memory whose indptr has been checked: every row lies in [0, nnz)
     int64_t ncells, ngenes;
     const void *indptr, *indices, *val;
@@ -53,32 +40,7 @@ __device__ __forceinline__ Row row_of(const Matrix &m, int64_t r)
     return Row{from, load_index(m.indptr, m.indptr_kind, r + 1) - from};
 }
 
-inline unsigned grid_for(int64_t n, int per_block)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 1 << 20));
-}
-
-inline void use_device(int device)
-{
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
-    HIPCHK(hipSetDevice(device));
-}
-
-inline hipStream_t pick_stream(void *stream, std::unique_ptr<TempStream> &own)
-{
-    // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
-    if (!stream) {
-        own.reset(new TempStream);
-        return own->st;
-    }
-    return stream == SCHPF_STREAM_DEFAULT ? nullptr : (hipStream_t)stream;
-}
-
 inline size_t value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
-
-typedef unsigned long long sum_t;   // the int64 outputs as atomicAdd takes them; no sum here is negative
 
 // the first of the n ascending columns at p that is not below `key`
 template <typename I> __device__ __forceinline__ int64_t lower_bound(const I *__restrict__ p, int64_t n, long long key)
@@ -96,7 +58,6 @@ namespace csr_checks {
 
 constexpr int CSR_THREADS = 256;
 constexpr int CSR_CHECK_BLOCKS = 4096;   // workgroups of csr_entries_kernel at the most: 16 per CU
-constexpr unsigned long long NONE = ~0ull;
 enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_ROW, W_BAD_LABEL, W_VMAX, W_COUNT };
 
 // indptr starts at 0, does not decrease and ends at nnz: the smallest offending row.  Every lane of a wavefront leaves the
@@ -109,10 +70,9 @@ static __global__ __launch_bounds__(CSR_THREADS) void csr_indptr_kernel(const vo
     for (int64_t r = blockIdx.x * (int64_t)CSR_THREADS + threadIdx.x; r <= ncells; r += (int64_t)gridDim.x * CSR_THREADS) {
         const long long here = load_index(indptr, indptr_kind, r);
         const bool wrong = (r == 0 && here != 0) || (r == ncells ? here != nnz : load_index(indptr, indptr_kind, r + 1) < here);
-        if (wrong && (unsigned long long)r < bad) bad = (unsigned long long)r;
+        if (wrong) offends(bad, r);
     }
-    bad = wave_min(bad);
-    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_INDPTR, bad);
+    report_min(words + W_BAD_INDPTR, bad);
 }
 
 // A wavefront per row.  counts: the matrix must be canonical and hold counts (the statistics): every column above its left
@@ -138,18 +98,13 @@ template <bool counts> __global__ __launch_bounds__(CSR_THREADS) void csr_entrie
             }
         }
     }
-    bad_index = wave_min(bad_index);
-    if (lane == 0 && bad_index != NONE) atomicMin(words + W_BAD_INDEX, bad_index);
+    report_min(words + W_BAD_INDEX, bad_index);
     if (!counts) return;
-    bad_order = wave_min(bad_order);
-    bad_value = wave_min(bad_value);
+    report_min(words + W_BAD_ORDER, bad_order);
+    report_min(words + W_BAD_VALUE, bad_value);
     vmax = ~wave_min(~vmax);
-    if (lane == 0) {
-        if (bad_order != NONE) atomicMin(words + W_BAD_ORDER, bad_order);
-        if (bad_value != NONE) atomicMin(words + W_BAD_VALUE, bad_value);
-        // a million wavefronts on one address is what this kernel would wait for: only a value above the one seen goes there
-        if (vmax > __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMax(words + W_VMAX, vmax);
-    }
+    // a million wavefronts on one address is what this kernel would wait for: only a value above the one seen goes there
+    if (lane == 0 && vmax > __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMax(words + W_VMAX, vmax);
 }
 
 #define CSR_LAUNCH(kernel, n, per_block, st, ...)                                                                          \
@@ -158,17 +113,12 @@ template <bool counts> __global__ __launch_bounds__(CSR_THREADS) void csr_entrie
         HIPCHK(hipGetLastError());                                                                                         \
     } while (0)
 
-struct Words {   // the smallest offenders in device memory, and their copy on the host
-    DevBuf d;
-    unsigned long long h[W_COUNT];
-    unsigned long long *dev() const { return d.as<unsigned long long>(); }
+struct Words : Offenders<W_COUNT> {   // the smallest offenders, and the running maximum, which starts at 0
     void reset(hipStream_t st)
     {
-        d.alloc(W_COUNT * sizeof(unsigned long long));
-        HIPCHK(hipMemsetAsync(d.p, 0xFF, W_COUNT * sizeof(unsigned long long), st));   // NONE
+        Offenders<W_COUNT>::reset(st);
         HIPCHK(hipMemsetAsync(dev() + W_VMAX, 0, sizeof(unsigned long long), st));
     }
-    void fetch(hipStream_t st) { d2h(h, d, sizeof h, st); }
 };
 
 // The two launches; the caller fetches the words and words its own refusals.  The indptr comes first and is fetched before
@@ -183,13 +133,10 @@ template <bool counts> inline void launch_entries_check(hipStream_t st, const Ma
     CSR_LAUNCH(csr_entries_kernel<counts>, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
 }
 
-// out[i] = in[0] + .. + in[i - 1] (rocPRIM); temp is the scan's own scratch
-inline void exclusive_scan(hipStream_t st, DevBuf &temp, const int64_t *in, int64_t *out, size_t n)
+// out[i] = in[0] + .. + in[i - 1] (rocPRIM)
+inline void exclusive_scan(hipStream_t st, Scratch &temp, const int64_t *in, int64_t *out, size_t n)
 {
-    size_t bytes = 0;
-    HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st));
-    temp.alloc(bytes);
-    HIPCHK(rocprim::exclusive_scan(temp.p, bytes, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st));
+    temp.run([&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), st); });
 }
 
 }  // namespace csr_checks

@@ -33,7 +33,6 @@ namespace {
 
 constexpr int DB_THREADS = 256;
 constexpr int DOUBLET_PIECE = 64;   // entries of a parent per pass of a wavefront: one per lane
-constexpr unsigned long long NONE = ~0ull;
 // the smallest offenders, in device memory, in the order they are reported
 enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_PARENT, W_COUNT };
 
@@ -56,10 +55,9 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_indptr_kernel(const void *
     for (int64_t r = blockIdx.x * (int64_t)DB_THREADS + threadIdx.x; r <= ncells; r += (int64_t)gridDim.x * DB_THREADS) {
         const long long here = load_index(indptr, indptr_kind, r);
         const bool wrong = (r == 0 && here != 0) || (r == ncells ? here != nnz : load_index(indptr, indptr_kind, r + 1) < here);
-        if (wrong && (unsigned long long)r < bad) bad = (unsigned long long)r;
+        if (wrong) offends(bad, r);
     }
-    bad = wave_min(bad);
-    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_INDPTR, bad);
+    report_min(words + W_BAD_INDPTR, bad);
 }
 
 __global__ __launch_bounds__(DB_THREADS) void doublet_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
@@ -71,20 +69,14 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_entries_kernel(Matrix m, u
         const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
         for (int64_t e = from + lane; e < to; e += 64) {
             const long long c = load_index(m.indices, m.idx_kind, e);
-            if ((c < 0 || c >= m.ngenes) && (unsigned long long)e < bad_index) bad_index = (unsigned long long)e;
-            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c && (unsigned long long)r < bad_order)
-                bad_order = (unsigned long long)r;
-            if (thin_value_bad(load_value(m.val, m.val_kind, e)) && (unsigned long long)e < bad_value) bad_value = (unsigned long long)e;
+            if (c < 0 || c >= m.ngenes) offends(bad_index, e);
+            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c) offends(bad_order, r);
+            if (thin_value_bad(load_value(m.val, m.val_kind, e))) offends(bad_value, e);
         }
     }
-    bad_index = wave_min(bad_index);
-    bad_order = wave_min(bad_order);
-    bad_value = wave_min(bad_value);
-    if (lane == 0) {
-        if (bad_index != NONE) atomicMin(words + W_BAD_INDEX, bad_index);
-        if (bad_order != NONE) atomicMin(words + W_BAD_ORDER, bad_order);
-        if (bad_value != NONE) atomicMin(words + W_BAD_VALUE, bad_value);
-    }
+    report_min(words + W_BAD_INDEX, bad_index);
+    report_min(words + W_BAD_ORDER, bad_order);
+    report_min(words + W_BAD_VALUE, bad_value);
 }
 
 __global__ __launch_bounds__(DB_THREADS) void doublet_pairs_kernel(const int32_t *__restrict__ parents, int64_t n_pairs, int64_t ncells,
@@ -93,10 +85,9 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_pairs_kernel(const int32_t
     unsigned long long bad = NONE;
     for (int64_t s = blockIdx.x * (int64_t)DB_THREADS + threadIdx.x; s < n_pairs; s += (int64_t)gridDim.x * DB_THREADS) {
         const int64_t a = parents[2 * s], b = parents[2 * s + 1];
-        if ((a < 0 || a >= ncells || b < 0 || b >= ncells) && (unsigned long long)s < bad) bad = (unsigned long long)s;
+        if (a < 0 || a >= ncells || b < 0 || b >= ncells) offends(bad, s);
     }
-    bad = wave_min(bad);
-    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_PARENT, bad);
+    report_min(words + W_BAD_PARENT, bad);
 }
 
 // how many of the n ascending columns at p are below `key`
@@ -191,15 +182,9 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_fill_kernel(Matrix m, cons
     }
 }
 
-#define LAUNCH(kernel, n, per_block, st, ...)                                                               \
-    do {                                                                                                    \
-        hipLaunchKernelGGL(kernel, dim3(grid_for(n, per_block)), dim3(DB_THREADS), 0, st, __VA_ARGS__);     \
-        HIPCHK(hipGetLastError());                                                                          \
-    } while (0)
-
 void parents_on_device(hipStream_t st, int64_t first, int64_t n_sim, int64_t ncells, uint64_t seed, int32_t *parents)
 {
-    LAUNCH(doublet_parents_kernel, n_sim, DB_THREADS, st, (uint64_t)first, n_sim, (uint32_t)ncells, (uint32_t)seed,
+    CSR_LAUNCH(doublet_parents_kernel, n_sim, DB_THREADS, st, (uint64_t)first, n_sim, (uint32_t)ncells, (uint32_t)seed,
            (uint32_t)(seed >> 32), parents);
     HIPCHK(hipStreamSynchronize(st));
 }
@@ -211,40 +196,34 @@ int64_t rows_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_t n_p
                        int32_t *out_indices, int32_t *out_values, int64_t capacity)
 {
     const int per_wave = DB_THREADS / 64;
-    DevBuf d_words, len, temp;
-    d_words.alloc(W_COUNT * sizeof(unsigned long long));
-    unsigned long long *const words = d_words.as<unsigned long long>();
-    unsigned long long h[W_COUNT];
-    HIPCHK(hipMemsetAsync(words, 0xFF, W_COUNT * sizeof(unsigned long long), st));   // NONE
-    LAUNCH(doublet_indptr_kernel, m.ncells + 1, DB_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, words);
-    d2h(h, d_words, sizeof h, st);
-    if (h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(doublet_bad_indptr((int64_t)h[W_BAD_INDPTR]));
-    LAUNCH(doublet_entries_kernel, m.ncells, per_wave, st, m, words);
-    LAUNCH(doublet_pairs_kernel, n_pairs, DB_THREADS, st, parents, n_pairs, m.ncells, words);
-    d2h(h, d_words, sizeof h, st);
-    if (h[W_BAD_INDEX] != NONE) throw std::invalid_argument(doublet_bad_index((int64_t)h[W_BAD_INDEX]));
-    if (h[W_BAD_ORDER] != NONE) throw std::invalid_argument(doublet_bad_order((int64_t)h[W_BAD_ORDER]));
-    if (h[W_BAD_VALUE] != NONE) throw std::invalid_argument(doublet_bad_value((int64_t)h[W_BAD_VALUE]));
-    if (h[W_BAD_PARENT] != NONE) throw std::invalid_argument(doublet_bad_parent((int64_t)h[W_BAD_PARENT]));
+    DevBuf len;
+    Scratch temp;
+    Offenders<W_COUNT> w;
+    w.reset(st);
+    CSR_LAUNCH(doublet_indptr_kernel, m.ncells + 1, DB_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, w.dev());
+    w.fetch(st);
+    w.refuse(W_BAD_INDPTR, doublet_bad_indptr);
+    CSR_LAUNCH(doublet_entries_kernel, m.ncells, per_wave, st, m, w.dev());
+    CSR_LAUNCH(doublet_pairs_kernel, n_pairs, DB_THREADS, st, parents, n_pairs, m.ncells, w.dev());
+    w.fetch(st);
+    w.refuse(W_BAD_INDEX, doublet_bad_index);
+    w.refuse(W_BAD_ORDER, doublet_bad_order);
+    w.refuse(W_BAD_VALUE, doublet_bad_value);
+    w.refuse(W_BAD_PARENT, doublet_bad_parent);
 
     const bool wide = m.idx_kind == SCHPF_IDX_I64;
     len.alloc((size_t)(n_pairs + 1) * sizeof(int64_t));
-    if (wide) LAUNCH(doublet_length_kernel<long long>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
-    else LAUNCH(doublet_length_kernel<int>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
-    size_t bytes = 0;
-    HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, len.as<int64_t>(), out_indptr, (int64_t)0, (size_t)(n_pairs + 1),
-                                   rocprim::plus<int64_t>(), st));
-    temp.alloc(bytes);
-    HIPCHK(rocprim::exclusive_scan(temp.p, bytes, len.as<int64_t>(), out_indptr, (int64_t)0, (size_t)(n_pairs + 1),
-                                   rocprim::plus<int64_t>(), st));
+    if (wide) CSR_LAUNCH(doublet_length_kernel<long long>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
+    else CSR_LAUNCH(doublet_length_kernel<int>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
+    csr_checks::exclusive_scan(st, temp, len.as<int64_t>(), out_indptr, (size_t)(n_pairs + 1));
     int64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, out_indptr + n_pairs, sizeof total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (!out_indices) return total;
     if (capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
     if (total > 0) {
-        if (wide) LAUNCH(doublet_fill_kernel<long long>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
-        else LAUNCH(doublet_fill_kernel<int>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
+        if (wide) CSR_LAUNCH(doublet_fill_kernel<long long>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
+        else CSR_LAUNCH(doublet_fill_kernel<int>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
     }
     HIPCHK(hipStreamSynchronize(st));   // before the scratch is released
     return total;

@@ -6,7 +6,9 @@
 // Root sets are processed in tiles of ROOT_TILE.  Inside a tile the working distances are vertex-major, work[v * TW + t], as
 // the uint64 bit patterns of the doubles: doubles >= +0 order the way their bit patterns do and +inf is the largest.  TW is
 // the tile's width, the smallest of 1, 2, 4, ROOT_TILE that holds the sets left; a column without a set stays at +inf.
-//   geodesic_roots_check_kernel  roots[e] in [0, n): the smallest offending set of each workgroup
+//   (graph_device.h: the columns, the values and set_ptr; every check leaves its smallest offender in a word of the call's
+//   one record, device_call.h: one fetch for the graph and set_ptr, one for the roots)
+//   geodesic_roots_check_kernel  roots[e] in [0, n): the smallest offending set
 //   geodesic_init_kernel         work = +inf, stamp = 0;  geodesic_roots_kernel: work[root * TW + t] = +0
 //   geodesic_relax_kernel        round r, one thread per stored entry (i, j, w), j != i: both endpoints' lines are read past
 //                                the L1; for each column t, cand = d[i] + w (one double add) goes to atomicMin(work[j]) only
@@ -38,6 +40,9 @@ constexpr int RELAX_BLOCKS = 2048;   // workgroups of a round at the most: 8 wav
 constexpr int COUNT_BLOCKS = 1024;
 constexpr unsigned long long INF_BITS = 0x7ff0000000000000ull;
 
+// the smallest offenders of a call, in the order they are asked
+enum { BAD_COLUMNS = 0, BAD_VALUES, BAD_SET_PTR, BAD_ROOTS, BAD_COUNT };
+
 typedef unsigned long long bits_t;
 
 __device__ __forceinline__ bits_t wave_sum(bits_t v)
@@ -49,14 +54,14 @@ __device__ __forceinline__ bits_t wave_sum(bits_t v)
 __device__ __forceinline__ bits_t load_past_l1(const bits_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(256) void geodesic_roots_check_kernel(const int32_t *__restrict__ roots, const int32_t *__restrict__ setof,
-                                                                   int n, int64_t nroots, int *__restrict__ part)
+                                                                   int n, int64_t nroots, unsigned long long *__restrict__ word)
 {
-    int bad = INT_MAX;
+    unsigned long long bad = NONE;
     GRID_STRIDE(e, nroots)
     {
-        if (roots[e] < 0 || roots[e] >= n) bad = min(bad, (int)setof[e]);
+        if (roots[e] < 0 || roots[e] >= n) offends(bad, setof[e]);
     }
-    block_min(bad, part);
+    report_min(word, bad);
 }
 
 __global__ __launch_bounds__(256) void geodesic_init_kernel(int64_t n, int64_t cells, bits_t *__restrict__ work, int *__restrict__ stamp)
@@ -164,12 +169,6 @@ __global__ __launch_bounds__(256) void geodesic_writes_kernel(const bits_t *__re
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(words + 1, mine);
 }
 
-#define LAUNCH_BOUNDED(kernel, n, blocks, st, ...)                                                                       \
-    do {                                                                                                                 \
-        hipLaunchKernelGGL(kernel, dim3(std::min<unsigned>(grid_for(n), blocks)), dim3(256), 0, st, __VA_ARGS__);       \
-        HIPCHK(hipGetLastError());                                                                                       \
-    } while (0)
-
 template <int TW>
 void launch_round(hipStream_t st, bool directed, const int32_t *rowof, const int32_t *indices, const double *data, int64_t nnz,
                   bits_t *work, int *stamp, int round, bool filtered, const int *before, int *flag, bits_t *writes)
@@ -194,46 +193,33 @@ int tile_width(int sets)   // the smallest of 1, 2, 4, ROOT_TILE that holds them
 void geodesic_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr, const int32_t *indices, const double *data,
                         bool directed, int nsets, const int64_t *set_ptr, const int32_t *roots, double *dist, int64_t *stats)
 {
-    const int64_t blocks_e = grid_for(nnz), blocks_s = grid_for(nsets);
-    DevBuf rowof, part_col, part_val, part_set, bad, bad_set, bad_root;
-    bad.alloc(2 * sizeof(int));
-    bad_set.alloc(2 * sizeof(int));
-    bad_root.alloc(2 * sizeof(int));
+    DevBuf rowof;
+    Offenders<BAD_COUNT> w;
+    w.reset(st);
     if (nnz > 0) {
         rowof.alloc((size_t)nnz * sizeof(int32_t));
-        part_col.alloc((size_t)blocks_e * sizeof(int));
-        part_val.alloc((size_t)blocks_e * sizeof(int));
-        LAUNCH(louvain_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
-        LAUNCH(louvain_check_kernel<false>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, part_col.as<int>(),
-               part_val.as<int>());
+        LAUNCH(entry_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
+        LAUNCH(graph_entries_check_kernel<false>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, w.dev() + BAD_COLUMNS,
+               w.dev() + BAD_VALUES);
     }
-    // set_ptr is an indptr over the sets: the same kernel, other words
-    part_set.alloc((size_t)blocks_s * sizeof(int));
-    LAUNCH(louvain_indptr_kernel, nsets, st, set_ptr, nsets, part_set.as<int>());
-    HIPCHK(launch_knn_bad(part_col.as<int>(), nnz > 0 ? blocks_e : 0, part_val.as<int>(), nnz > 0 ? blocks_e : 0, bad.as<int>(), st));
-    HIPCHK(launch_knn_bad(part_set.as<int>(), blocks_s, nullptr, 0, bad_set.as<int>(), st));
-    int h_bad[2], h_bad_set[2];
+    // set_ptr is an indptr over the sets: the same kernel, other words.  Not through indptr_on_device: its verdict is asked
+    // behind the graph's, and all of it comes to the host with the one fetch, not its last entry alone
+    LAUNCH(indptr_check_kernel, nsets, st, set_ptr, nsets, w.dev() + BAD_SET_PTR);
     std::vector<int64_t> h_set_ptr((size_t)nsets + 1);
-    HIPCHK(hipMemcpyAsync(h_bad, bad.p, sizeof h_bad, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_set_ptr.data(), set_ptr, h_set_ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    d2h(h_bad_set, bad_set, sizeof h_bad_set, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument(graph_bad_columns(h_bad[0]));
-    if (h_bad[1] != INT_MAX) throw std::invalid_argument(louvain_bad_values(h_bad[1]));
-    if (h_bad_set[0] != INT_MAX) throw std::invalid_argument(geodesic_bad_set_ptr(h_bad_set[0]));
+    w.fetch(st);
+    w.refuse(BAD_COLUMNS, graph_bad_columns);
+    w.refuse(BAD_VALUES, louvain_bad_values);
+    w.refuse(BAD_SET_PTR, geodesic_bad_set_ptr);
     const int64_t nroots = h_set_ptr[(size_t)nsets];
     if (nroots > 0 && !roots) throw std::invalid_argument("roots must not be NULL");
     DevBuf setof;
     if (nroots > 0) {
-        const int64_t blocks_r = grid_for(nroots);
-        DevBuf part_root;
         setof.alloc((size_t)nroots * sizeof(int32_t));
-        part_root.alloc((size_t)blocks_r * sizeof(int));
-        LAUNCH(louvain_rows_kernel, nroots, st, set_ptr, (int64_t)nsets, nroots, setof.as<int32_t>());
-        LAUNCH(geodesic_roots_check_kernel, nroots, st, roots, setof.as<int32_t>(), n, nroots, part_root.as<int>());
-        HIPCHK(launch_knn_bad(part_root.as<int>(), blocks_r, nullptr, 0, bad_root.as<int>(), st));
-        int h_bad_root[2];
-        d2h(h_bad_root, bad_root, sizeof h_bad_root, st);
-        if (h_bad_root[0] != INT_MAX) throw std::invalid_argument(geodesic_bad_roots(h_bad_root[0]));
+        LAUNCH(entry_rows_kernel, nroots, st, set_ptr, (int64_t)nsets, nroots, setof.as<int32_t>());
+        LAUNCH(geodesic_roots_check_kernel, nroots, st, roots, setof.as<int32_t>(), n, nroots, w.dev() + BAD_ROOTS);
+        w.fetch(st);
+        w.refuse(BAD_ROOTS, geodesic_bad_roots);
     }
 
     const int widest = tile_width(nsets);
@@ -311,7 +297,7 @@ int schpf_geodesic_device(int device, void *stream, int n, const int64_t *indptr
         use_device(device);
         std::unique_ptr<TempStream> own;
         hipStream_t st = pick_stream(stream, own);
-        const int64_t nnz = louvain_indptr_on_device(st, n, indptr);
+        const int64_t nnz = indptr_on_device(st, n, indptr, louvain_bad_indptr);
         if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
         int64_t result[3];
         geodesic_on_device(st, n, nnz, indptr, indices, data, directed != 0, nsets, set_ptr, roots, dist, result);
@@ -332,7 +318,7 @@ int schpf_geodesic(int device, int n, const int64_t *indptr, const int32_t *indi
         TempStream ts;
         DevBuf d_indptr, d_indices, d_data, d_set_ptr, d_roots, d_dist;
         h2d<int64_t>(d_indptr, indptr, (size_t)n + 1, ts.st);
-        const int64_t nnz = louvain_indptr_on_device(ts.st, n, d_indptr.as<int64_t>());   // the host's indptr[n] if it passes
+        const int64_t nnz = indptr_on_device(ts.st, n, d_indptr.as<int64_t>(), louvain_bad_indptr);   // the host's indptr[n] if it passes
         if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
         h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);
         if (data) h2d<double>(d_data, data, (size_t)nnz, ts.st);

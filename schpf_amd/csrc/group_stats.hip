@@ -56,12 +56,11 @@ __global__ __launch_bounds__(GS_THREADS) void gs_keys_kernel(const int32_t *__re
     unsigned long long bad = NONE;
     for (int64_t i = blockIdx.x * (int64_t)GS_THREADS + threadIdx.x; i < ncells; i += (int64_t)gridDim.x * GS_THREADS) {
         const int64_t g = labels[i];
-        if ((g < -1 || g >= ngroups) && (unsigned long long)i < bad) bad = (unsigned long long)i;
+        if (g < -1 || g >= ngroups) offends(bad, i);
         key[i] = g >= 0 && g < ngroups ? (int32_t)g : (int32_t)ngroups;
         cell[i] = (int32_t)i;
     }
-    bad = wave_min(bad);
-    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_LABEL, bad);
+    report_min(words + W_BAD_LABEL, bad);
 }
 
 // key: the ncells sorted keys.  Thread g <= ngroups; group ngroups is the cells in no group and gets no slab
@@ -148,13 +147,6 @@ __global__ __launch_bounds__(GS_SUM_THREADS) void gs_sum_kernel(Matrix m, const 
     }
 }
 
-int bits_of(uint64_t largest)   // the bits a radix sort has to look at for keys up to `largest`
-{
-    int b = 1;
-    while (b < 64 && (largest >> b)) ++b;
-    return b;
-}
-
 template <typename I, int G> void launch_sum(hipStream_t st, dim3 grid, const Matrix &m, const int32_t *order, const Slab *slabs,
                                              int64_t n_slabs, int64_t *nexpr, int64_t *total, int64_t *sumsq)
 {
@@ -172,31 +164,28 @@ void group_stats_on_device(hipStream_t st, const Matrix &m, int64_t nnz, const i
     const int64_t N = m.ncells;
     Words w;
     w.reset(st);
-    DevBuf key_a, key_b, cell_a, cell_b, starts, slabs_of, first_slab, slabs, temp;
+    DevBuf key_a, key_b, cell_a, cell_b, starts, slabs_of, first_slab, slabs;
+    Scratch temp;
     for (DevBuf *b : {&key_a, &key_b, &cell_a, &cell_b}) b->alloc((size_t)N * sizeof(int32_t));
     if (nnz > 0) {
         launch_indptr_check(st, m, nnz, w);
         w.fetch(st);
-        if (w.h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(group_stats_bad_indptr((int64_t)w.h[W_BAD_INDPTR]));
+        w.refuse(W_BAD_INDPTR, group_stats_bad_indptr);
         launch_entries_check<true>(st, m, w);
     }
     if (N > 0) CSR_LAUNCH(gs_keys_kernel, N, GS_THREADS, st, labels, N, ngroups, key_a.as<int32_t>(), cell_a.as<int32_t>(), w.dev());
     w.fetch(st);
-    if (w.h[W_BAD_INDEX] != NONE) throw std::invalid_argument(group_stats_bad_index((int64_t)w.h[W_BAD_INDEX]));
-    if (w.h[W_BAD_ORDER] != NONE) throw std::invalid_argument(group_stats_bad_order((int64_t)w.h[W_BAD_ORDER]));
-    if (w.h[W_BAD_VALUE] != NONE) throw std::invalid_argument(group_stats_bad_value((int64_t)w.h[W_BAD_VALUE]));
-    if (w.h[W_BAD_LABEL] != NONE) throw std::invalid_argument(group_stats_bad_labels((int64_t)w.h[W_BAD_LABEL]));
+    w.refuse(W_BAD_INDEX, group_stats_bad_index);
+    w.refuse(W_BAD_ORDER, group_stats_bad_order);
+    w.refuse(W_BAD_VALUE, group_stats_bad_value);
+    w.refuse(W_BAD_LABEL, group_stats_bad_labels);
     if (sumsq && qc_sumsq_overflows(w.h[W_VMAX], N)) throw std::invalid_argument(group_stats_bad_sumsq(w.h[W_VMAX], N));
 
-    if (N > 0) {
-        size_t bytes = 0;
-        const int bits = bits_of((uint64_t)ngroups);
-        HIPCHK(rocprim::radix_sort_pairs((void *)nullptr, bytes, key_a.as<uint32_t>(), key_b.as<uint32_t>(), cell_a.as<int32_t>(),
-                                         cell_b.as<int32_t>(), (size_t)N, 0, bits, st));
-        temp.alloc(bytes);
-        HIPCHK(rocprim::radix_sort_pairs(temp.p, bytes, key_a.as<uint32_t>(), key_b.as<uint32_t>(), cell_a.as<int32_t>(),
-                                         cell_b.as<int32_t>(), (size_t)N, 0, bits, st));
-    }
+    if (N > 0)
+        temp.run([&](void *t, size_t &b) {
+            return rocprim::radix_sort_pairs(t, b, key_a.as<uint32_t>(), key_b.as<uint32_t>(), cell_a.as<int32_t>(),
+                                             cell_b.as<int32_t>(), (size_t)N, 0, bits_of((uint64_t)ngroups), st);
+        });
     for (DevBuf *b : {&starts, &slabs_of, &first_slab}) b->alloc((size_t)(ngroups + 1) * sizeof(int64_t));
     CSR_LAUNCH(gs_starts_kernel, ngroups + 1, GS_THREADS, st, key_b.as<int32_t>(), N, ngroups, starts.as<int64_t>(), slabs_of.as<int64_t>(),
                group_cells);

@@ -209,9 +209,8 @@ hipError_t launch_predictive_e(const T *shape, const T *rate, int n, int K, doub
 hipError_t launch_predictive_rows(const double *e_major, const double *e_minor, int n_major, int n_minor, int K, int strip,
                                   double *out, hipStream_t st);
 // k nearest neighbours between two sets of rows (knn.hip).  launch_knn_table: one side's rows as doubles,
-// tab[knn_pad(n) * K] in the blocked layout [row / 64][k][row % 64], padding rows 0; bad_part[knn_table_blocks(n, K)]
-// takes per block the smallest row that holds a non-finite value (INT_MAX: none).  launch_knn_bad: the minima of both
-// sides' bad_part, bad[0] query, bad[1] ref (n_*_blocks = 0: that side was not looked at).  launch_knn_select: a
+// tab[knn_pad(n) * K] in the blocked layout [row / 64][k][row % 64], padding rows 0; *bad_row, a word of the call's record
+// of offenders (device_call.h: preset to "none"), takes the smallest row that holds a non-finite value.  launch_knn_select: a
 // workgroup per (strip of 64 query rows, segment of seg_tiles tiles of 64 reference rows) leaves the segment's sorted
 // best min(k, admissible) keys (d2, r) of every row at [(q * n_seg + s) * k ...) of idx / d2 and their number in
 // cnt[q * n_seg + s] (nullptr with n_seg = 1: the final lists).  launch_knn_merge: the n_seg lists of a row -> its k best
@@ -232,18 +231,16 @@ inline int knn_segments(int n_query, int n_ref, int cu_count)
 inline size_t knn_lds_bytes(int k, int kc) { return 8 * ((size_t)128 * kc + 64 * 64 + 64 * (size_t)k + 64) + 4 * (64 * (size_t)k + 192); }
 inline int knn_stage_factors(int k) { return knn_lds_bytes(k, 32) <= 160 * 1024 ? 32 : 16; }
 template <typename T>
-hipError_t launch_knn_table(const T *x, int n, int K, double *tab, int *bad_part, hipStream_t st);
-hipError_t launch_knn_bad(const int *part_query, int64_t n_query_blocks, const int *part_ref, int64_t n_ref_blocks, int *bad,
-                          hipStream_t st);
+hipError_t launch_knn_table(const T *x, int n, int K, double *tab, unsigned long long *bad_row, hipStream_t st);
 hipError_t launch_knn_select(const double *qtab, const double *rtab, int n_query, int n_ref, int K, int k,
                              int64_t self_first, int seg_tiles, int n_seg, int32_t *idx, double *d2, int *cnt,
                              hipStream_t st);
 hipError_t launch_knn_merge(const int32_t *part_idx, const double *part_d2, const int *part_cnt, int n_query, int n_seg,
                             int k, int32_t *idx, double *d2, hipStream_t st);
 // Weighted neighbour graphs from k-NN lists (knn_graph.hip).  launch_graph_rows: one thread per row, 64 rows
-// per workgroup: bad_idx / bad_dist[graph_row_blocks(n)] take per workgroup the smallest row whose list (an index out of
-// range, the row itself, an index twice) or whose distances (negative, not finite) are refused, INT_MAX: none -- reduced by
-// launch_knn_bad; dist != nullptr (umap): rho[n], sigma[n] and the directed weights w[n * k]; sorted != nullptr: the rows'
+// per workgroup: *bad_idx / *bad_dist, two words of the call's record of offenders (device_call.h: preset to "none"), take
+// the smallest row whose list (an index out of range, the row itself, an index twice) or whose distances (negative, not
+// finite) are refused; dist != nullptr (umap): rho[n], sigma[n] and the directed weights w[n * k]; sorted != nullptr: the rows'
 // indices ascending.  launch_graph_keys: the 2 n k records of the directed edges, key = ((row * n + col) << 1) | direction,
 // val (may be nullptr) the edge's weight.  launch_graph_heads: head[p] = 1 where the SORTED key p starts a new (row, col).
 // launch_graph_fill: pos = the exclusive scan of head; writes indptr[n + 1], indices and data; val (the sorted weights:
@@ -251,7 +248,8 @@ hipError_t launch_knn_merge(const int32_t *part_idx, const double *part_d2, cons
 inline int64_t graph_row_blocks(int n) { return ((int64_t)n + 63) / 64; }
 inline size_t graph_row_lds_bytes(int k) { return (size_t)64 * (size_t)k * sizeof(double); }
 hipError_t launch_graph_rows(const int32_t *idx, const double *dist, int n, int k, double target, double *w, double *rho,
-                             double *sigma, int32_t *sorted, int *bad_idx, int *bad_dist, hipStream_t st);
+                             double *sigma, int32_t *sorted, unsigned long long *bad_idx, unsigned long long *bad_dist,
+                             hipStream_t st);
 hipError_t launch_graph_keys(const int32_t *idx, const double *w, int n, int k, uint64_t *key, double *val, hipStream_t st);
 hipError_t launch_graph_heads(const uint64_t *key, int64_t n_keys, int64_t *head, hipStream_t st);
 hipError_t launch_graph_fill(const uint64_t *key, const double *val, const int64_t *pos, const int32_t *sorted, int64_t n_keys,

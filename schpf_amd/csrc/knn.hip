@@ -3,12 +3,12 @@
 // with one subtraction and one fused multiply-add per factor, in factor order -- host.cpp's serial restatement gives the
 // same bits.  The key is a total order, so the result does not depend on how the pairs were walked or merged.
 //
-//   knn_table_kernel<T>  one side as doubles in the layout the tiles are staged from; flags non-finite values
-//   knn_bad_kernel       the smallest offending row of each side
+//   knn_table_kernel<T>  one side as doubles in the layout the tiles are staged from; the smallest row that holds a
+//                        non-finite value goes to the side's word of the call's record (device_call.h)
 //   knn_select_kernel    a workgroup owns a strip of 64 query rows and walks (a segment of) the reference rows in tiles of
 //                        64; every thread owns 4 x 4 pairs; the k best keys of every row of the strip stay in the LDS
 //   knn_merge_kernel     reference axis cut into segments (kernels.h knn_segments): the segments' lists of a row -> one
-// No atomics anywhere: who writes what is fixed by the indices.
+// No atomics but the check's integer minimum: who writes what is fixed by the indices.
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -17,7 +17,7 @@
 #include <memory>
 #include <string>
 
-#include "common.h"
+#include "device_call.h"
 #include "kernels.h"
 
 namespace schpf {
@@ -34,14 +34,14 @@ __device__ __forceinline__ size_t tab_index(int row, int k, int K)
 // the order of section 16: the smaller d2 first, equal d2 by the smaller row
 __device__ __forceinline__ bool key_less(double ad, int ai, double bd, int bi) { return ad < bd || (ad == bd && ai < bi); }
 
-// One thread per element of the padded table; per block the smallest row with a NaN or an infinity
+// One thread per element of the padded table; *bad_row takes the smallest row with a NaN or an infinity.  No early return:
+// every lane reaches report_min
 template <typename T>
 __global__ __launch_bounds__(256) void knn_table_kernel(const T *__restrict__ x, int n, int n_pad, int K,
-                                                        double *__restrict__ tab, int *__restrict__ bad_part)
+                                                        double *__restrict__ tab, unsigned long long *__restrict__ bad_row)
 {
-    __shared__ int red[256];
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    int bad = INT_MAX;
+    unsigned long long bad = NONE;
     if (i < (size_t)n_pad * (size_t)K) {
         const size_t q = i >> 6;
         const int k = (int)(q % (size_t)K);
@@ -49,36 +49,11 @@ __global__ __launch_bounds__(256) void knn_table_kernel(const T *__restrict__ x,
         double v = 0.0;
         if (row < n) {
             v = (double)x[(size_t)row * K + k];
-            if (!(fabs(v) <= DBL_MAX)) bad = row;
+            if (!(fabs(v) <= DBL_MAX)) offends(bad, row);
         }
         tab[i] = v;
     }
-    red[threadIdx.x] = bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bad_part[blockIdx.x] = red[0];
-}
-
-// block 0: the query side's minimum, block 1: the reference side's
-__global__ __launch_bounds__(256) void knn_bad_kernel(const int *__restrict__ part_query, int64_t n_query_blocks,
-                                                      const int *__restrict__ part_ref, int64_t n_ref_blocks,
-                                                      int *__restrict__ out)
-{
-    __shared__ int red[256];
-    const int *part = blockIdx.x ? part_ref : part_query;
-    const int64_t n = blockIdx.x ? n_ref_blocks : n_query_blocks;
-    int bad = INT_MAX;
-    for (int64_t i = threadIdx.x; i < n; i += 256) bad = min(bad, part[i]);
-    red[threadIdx.x] = bad;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    report_min(bad_row, bad);
 }
 
 // One wavefront merges up to 64 candidates (one per lane, `valid`) into a row's sorted list ld2 / lidx[0 .. cnt) of
@@ -279,17 +254,10 @@ __global__ __launch_bounds__(64) void knn_merge_kernel(const int32_t *__restrict
 }  // namespace
 
 template <typename T>
-hipError_t launch_knn_table(const T *x, int n, int K, double *tab, int *bad_part, hipStream_t st)
+hipError_t launch_knn_table(const T *x, int n, int K, double *tab, unsigned long long *bad_row, hipStream_t st)
 {
     hipLaunchKernelGGL((knn_table_kernel<T>), dim3((unsigned)knn_table_blocks(n, K)), dim3(256), 0, st, x, n, knn_pad(n), K,
-                       tab, bad_part);
-    return hipGetLastError();
-}
-
-hipError_t launch_knn_bad(const int *part_query, int64_t n_query_blocks, const int *part_ref, int64_t n_ref_blocks, int *bad,
-                          hipStream_t st)
-{
-    hipLaunchKernelGGL(knn_bad_kernel, dim3(2), dim3(256), 0, st, part_query, n_query_blocks, part_ref, n_ref_blocks, bad);
+                       tab, bad_row);
     return hipGetLastError();
 }
 
@@ -318,18 +286,10 @@ hipError_t launch_knn_merge(const int32_t *part_idx, const double *part_d2, cons
     return hipGetLastError();
 }
 
-template hipError_t launch_knn_table<float>(const float *, int, int, double *, int *, hipStream_t);
-template hipError_t launch_knn_table<double>(const double *, int, int, double *, int *, hipStream_t);
+template hipError_t launch_knn_table<float>(const float *, int, int, double *, unsigned long long *, hipStream_t);
+template hipError_t launch_knn_table<double>(const double *, int, int, double *, unsigned long long *, hipStream_t);
 
 namespace {
-
-void use_device(int device)
-{
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
-    HIPCHK(hipSetDevice(device));
-}
 
 // $SCHPF_KNN_SPLIT, read once per call: unset = the rule of knn_segments; 0 or 1 = one segment; n >= 2 = n segments
 int segments_wanted(int n_query, int n_ref, int device)
@@ -347,22 +307,20 @@ void knn_on_device(int device, hipStream_t st, int dtype, int n_query, int n_ref
                    int k, int64_t self_first, int32_t *idx, double *d2)
 {
     const bool shared = query == ref && n_query == n_ref;
-    DevBuf qtab, rtab, qbad, rbad, bad;
-    auto table = [&](const void *x, int n, DevBuf &tab, DevBuf &part) {
+    DevBuf qtab, rtab;
+    enum { BAD_QUERY = 0, BAD_REF, BAD_COUNT };
+    Offenders<BAD_COUNT> w;
+    w.reset(st);
+    auto table = [&](const void *x, int n, DevBuf &tab, int side) {
         tab.alloc((size_t)knn_pad(n) * K * sizeof(double));
-        part.alloc((size_t)knn_table_blocks(n, K) * sizeof(int));
-        if (dtype == SCHPF_F32) HIPCHK(launch_knn_table<float>((const float *)x, n, K, tab.as<double>(), part.as<int>(), st));
-        else HIPCHK(launch_knn_table<double>((const double *)x, n, K, tab.as<double>(), part.as<int>(), st));
+        if (dtype == SCHPF_F32) HIPCHK(launch_knn_table<float>((const float *)x, n, K, tab.as<double>(), w.dev() + side, st));
+        else HIPCHK(launch_knn_table<double>((const double *)x, n, K, tab.as<double>(), w.dev() + side, st));
     };
-    table(query, n_query, qtab, qbad);
-    if (!shared) table(ref, n_ref, rtab, rbad);
-    bad.alloc(2 * sizeof(int));
-    HIPCHK(launch_knn_bad(qbad.as<int>(), knn_table_blocks(n_query, K), rbad.as<int>(), shared ? 0 : knn_table_blocks(n_ref, K),
-                          bad.as<int>(), st));
-    int h_bad[2];
-    d2h(h_bad, bad, sizeof h_bad, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument("scores must be finite; offending row " + std::to_string(h_bad[0]) + " of query");
-    if (h_bad[1] != INT_MAX) throw std::invalid_argument("scores must be finite; offending row " + std::to_string(h_bad[1]) + " of ref");
+    table(query, n_query, qtab, BAD_QUERY);
+    if (!shared) table(ref, n_ref, rtab, BAD_REF);
+    w.fetch(st);
+    w.refuse(BAD_QUERY, [](int64_t row) { return "scores must be finite; offending row " + std::to_string(row) + " of query"; });
+    w.refuse(BAD_REF, [](int64_t row) { return "scores must be finite; offending row " + std::to_string(row) + " of ref"; });
     const double *rt = shared ? qtab.as<double>() : rtab.as<double>();
     const int n_tiles = (n_ref + RT - 1) / RT;
     const int wanted = std::min(segments_wanted(n_query, n_ref, device), n_tiles);
@@ -398,11 +356,8 @@ int schpf_knn_device(int device, void *stream, int dtype, int n_query, int n_ref
     if (n_query == 0) return 0;
     return guarded([&] {
         use_device(device);
-        // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
         std::unique_ptr<TempStream> own;
-        hipStream_t st = nullptr;
-        if (!stream) { own.reset(new TempStream); st = own->st; }
-        else if (stream != SCHPF_STREAM_DEFAULT) st = (hipStream_t)stream;
+        hipStream_t st = pick_stream(stream, own);
         knn_on_device(device, st, dtype, n_query, n_ref, nfactors, query, ref, k, self_first, idx, d2);
     });
 }

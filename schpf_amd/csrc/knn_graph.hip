@@ -12,7 +12,7 @@
 //   graph_heads_kernel  1 where a key starts a new (row, col); rocPRIM's exclusive scan of that is the place in the CSR
 //   graph_fill_kernel   one thread per sorted key: a head writes its column, its value -- the union of the one or two
 //                       weights, or the Jaccard ratio from the two sorted lists -- and, where a row starts, indptr
-// No atomics anywhere: who writes what is fixed by the sorted order.
+// No atomics but the checks' integer minima (device_call.h): who writes what is fixed by the sorted order.
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -22,7 +22,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "common.h"
+#include "device_call.h"
 #include "kernels.h"
 #include "special.h"
 
@@ -39,14 +39,8 @@ struct GraphRowArgs {
     double *w;            // [n][k] directed weights, in the caller's column order (umap)
     double *rho, *sigma;  // [n] (umap)
     int32_t *sorted;      // [n][k] the row's indices ascending (jaccard; nullptr: not kept)
-    int *bad_idx, *bad_dist;   // [workgroups]: the smallest offending row of each, INT_MAX: none
+    unsigned long long *bad_idx, *bad_dist;   // two words of the call's record: the smallest offending row of each check
 };
-
-__device__ __forceinline__ int wave_min(int v)
-{
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
 
 // W(e, s) of the definition
 __device__ __forceinline__ double graph_weight(double e, double s)
@@ -73,7 +67,7 @@ __global__ __launch_bounds__(ROWS) void graph_row_kernel(GraphRowArgs a)
         li[j * ROWS + r] = a.idx[base + t];
     }
     __syncthreads();
-    int bad = INT_MAX;
+    unsigned long long bad = NONE;
     if (lane < rows) {
         bool wrong = false;
         for (int j = 0; j < k; ++j) {
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(ROWS) void graph_row_kernel(GraphRowArgs a)
             li[(b + 1) * ROWS + lane] = v;
         }
         for (int j = 1; j < k; ++j) wrong |= li[j * ROWS + lane] == li[(j - 1) * ROWS + lane];
-        if (wrong) bad = row;
+        if (wrong) offends(bad, row);
     }
     __syncthreads();
     if (a.sorted)
@@ -98,19 +92,15 @@ __global__ __launch_bounds__(ROWS) void graph_row_kernel(GraphRowArgs a)
             const int r = t / k, j = t - r * k;
             a.sorted[base + t] = li[j * ROWS + r];
         }
-    bad = wave_min(bad);
-    if (lane == 0) a.bad_idx[blockIdx.x] = bad;
-    if (!a.dist) {
-        if (lane == 0) a.bad_dist[blockIdx.x] = INT_MAX;
-        return;
-    }
+    report_min(a.bad_idx, bad);   // the one wavefront of the workgroup is here: nothing returns before it
+    if (!a.dist) return;
     __syncthreads();   // the indices have been read
     for (int t = lane; t < total; t += ROWS) {
         const int r = t / k, j = t - r * k;
         ld[j * ROWS + r] = a.dist[base + t];
     }
     __syncthreads();
-    bad = INT_MAX;
+    bad = NONE;
     if (lane < rows) {
         double rho = HUGE_VAL, sum = 0.0;
         bool wrong = false;
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(ROWS) void graph_row_kernel(GraphRowArgs a)
             rho = d > 0.0 && d < rho ? d : rho;
             sum += d;
         }
-        if (wrong) bad = row;
+        if (wrong) offends(bad, row);
         rho = rho == HUGE_VAL ? 0.0 : rho;
         double lo = 0.0, hi = HUGE_VAL, mid = 1.0;
         for (int round = 0; round < 64; ++round) {
@@ -156,8 +146,7 @@ __global__ __launch_bounds__(ROWS) void graph_row_kernel(GraphRowArgs a)
         const int r = t / k, j = t - r * k;
         a.w[base + t] = ld[j * ROWS + r];
     }
-    bad = wave_min(bad);
-    if (lane == 0) a.bad_dist[blockIdx.x] = bad;
+    report_min(a.bad_dist, bad);
 }
 
 // edge e = i * k + j' of the validated lists -> the records 2 e (entry (i, j), bit 0) and 2 e + 1 (entry (j, i), bit 1)
@@ -237,12 +226,11 @@ __global__ __launch_bounds__(256) void graph_fill_kernel(const uint64_t *__restr
     }
 }
 
-unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 1 << 20); }
-
 }  // namespace
 
 hipError_t launch_graph_rows(const int32_t *idx, const double *dist, int n, int k, double target, double *w, double *rho,
-                             double *sigma, int32_t *sorted, int *bad_idx, int *bad_dist, hipStream_t st)
+                             double *sigma, int32_t *sorted, unsigned long long *bad_idx, unsigned long long *bad_dist,
+                             hipStream_t st)
 {
     if (n < 1 || k < 1 || k > 128) return hipErrorInvalidValue;
     const GraphRowArgs a{idx, dist, n, k, target, w, rho, sigma, sorted, bad_idx, bad_dist};
@@ -274,14 +262,6 @@ hipError_t launch_graph_fill(const uint64_t *key, const double *val, const int64
 
 namespace {
 
-void use_device(int device)
-{
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
-    HIPCHK(hipSetDevice(device));
-}
-
 // Everything on `st`, which is synchronised when this returns; all pointers are device memory.  Nothing is written to the
 // outputs when the lists are refused: the row pass writes scratch only
 void graph_on_device(hipStream_t st, int method, int n, int k, const int32_t *idx, const double *dist, int64_t *indptr,
@@ -289,8 +269,10 @@ void graph_on_device(hipStream_t st, int method, int n, int k, const int32_t *id
 {
     const bool umap = method == SCHPF_GRAPH_UMAP;
     const size_t n_edges = (size_t)n * (size_t)k, n_keys = 2 * n_edges;
-    const int64_t blocks = graph_row_blocks(n);
-    DevBuf w, d_rho, d_sigma, sorted, part_idx, part_dist, bad;
+    DevBuf w, d_rho, d_sigma, sorted;
+    enum { BAD_LISTS = 0, BAD_DISTANCES, BAD_COUNT };
+    Offenders<BAD_COUNT> bad;
+    bad.reset(st);
     if (umap) {
         w.alloc(n_edges * sizeof(double));
         d_rho.alloc((size_t)n * sizeof(double));
@@ -298,17 +280,12 @@ void graph_on_device(hipStream_t st, int method, int n, int k, const int32_t *id
     } else {
         sorted.alloc(n_edges * sizeof(int32_t));
     }
-    part_idx.alloc((size_t)blocks * sizeof(int));
-    part_dist.alloc((size_t)blocks * sizeof(int));
-    bad.alloc(2 * sizeof(int));
     HIPCHK(launch_graph_rows(idx, umap ? dist : nullptr, n, k, std::log2((double)(k + 1)), w.as<double>(), d_rho.as<double>(),
-                             d_sigma.as<double>(), umap ? nullptr : sorted.as<int32_t>(), part_idx.as<int>(),
-                             part_dist.as<int>(), st));
-    HIPCHK(launch_knn_bad(part_idx.as<int>(), blocks, part_dist.as<int>(), blocks, bad.as<int>(), st));
-    int h_bad[2];
-    d2h(h_bad, bad, sizeof h_bad, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument(graph_bad_lists(h_bad[0]));
-    if (h_bad[1] != INT_MAX) throw std::invalid_argument(graph_bad_distances(h_bad[1]));
+                             d_sigma.as<double>(), umap ? nullptr : sorted.as<int32_t>(), bad.dev() + BAD_LISTS,
+                             bad.dev() + BAD_DISTANCES, st));
+    bad.fetch(st);
+    bad.refuse(BAD_LISTS, graph_bad_lists);
+    bad.refuse(BAD_DISTANCES, graph_bad_distances);
 
     // the alternate buffers of the sort are free once it is done: the head flags and their scan go there
     DevBuf k_in, k_out, v_in, v_out, temp;
@@ -357,11 +334,8 @@ int schpf_knn_graph_device(int device, void *stream, int method, int n, int k, c
     if (n == 0) return 0;
     return guarded([&] {
         use_device(device);
-        // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
         std::unique_ptr<TempStream> own;
-        hipStream_t st = nullptr;
-        if (!stream) { own.reset(new TempStream); st = own->st; }
-        else if (stream != SCHPF_STREAM_DEFAULT) st = (hipStream_t)stream;
+        hipStream_t st = pick_stream(stream, own);
         graph_on_device(st, method, n, k, idx, dist, indptr, indices, data, rho, sigma);
     });
 }

@@ -3,11 +3,12 @@
 // candidate is a fixed expression of exact integers.  Moves are synchronous.  The definition is in include/schpf_hip.h;
 // host.cpp's serial restatement gives the same bits.
 //
-// (the first four kernels are in graph_device.h, shared with components.hip)
-//   louvain_indptr_kernel   indptr starts at 0 and does not decrease: the smallest offending row of each workgroup
-//   louvain_rows_kernel     the row of every entry, by bisection in indptr (once per level: a row may be of any length,
+// (the first four kernels are in graph_device.h, shared with components.hip, geodesic.hip and the rank sums)
+//   indptr_check_kernel     indptr starts at 0 and does not decrease: the smallest offending row
+//   entry_rows_kernel       the row of every entry, by bisection in indptr (once per level: a row may be of any length,
 //                           no kernel walks one)
-//   louvain_check_kernel    one thread per entry: column in range and above its left neighbour, value finite and >= 0
+//   graph_entries_check_kernel  one thread per entry: column in range and above its left neighbour, value finite and >= 0;
+//                           the smallest offending row of each into the call's record of two words (device_call.h)
 //   (rocPRIM reduce: wmax)
 //   louvain_quantise_kernel q = llrint(ldexp(data / wmax, 30))
 //   per level: (rocPRIM reduce-by-key over the rows: k_i; reduce: W2)
@@ -26,7 +27,8 @@
 //   louvain_rekey_kernel    per entry the key c'(i) * n' + c'(j); sort and reduce-by-key give the next level's entries
 //   louvain_fill_kernel     columns and, by bisection in the sorted keys, indptr (a row may be empty)
 //   louvain_compose_kernel  labels through the renumbering
-// No atomics in any kernel here: who writes what is fixed by the sorted order.
+// No atomics in any kernel here: who writes what is fixed by the sorted order.  (The checks' one atomicMin per wavefront that
+// found an offender is an integer minimum.)
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -219,12 +221,11 @@ void louvain_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr
     if (nnz == 0) return finish(n, 0, 0, 0);
 
     Scratch temp;
-    DevBuf rowof, part_col, part_val, bad, scalars;
+    DevBuf rowof, scalars;
+    enum { BAD_COLUMNS = 0, BAD_VALUES, BAD_COUNT };
+    Offenders<BAD_COUNT> w;
+    w.reset(st);
     rowof.alloc((size_t)nnz * sizeof(int32_t));
-    const int64_t blocks = grid_for(nnz);
-    part_col.alloc((size_t)blocks * sizeof(int));
-    part_val.alloc((size_t)blocks * sizeof(int));
-    bad.alloc(2 * sizeof(int));
     // device scalars: [0] wmax (double), [1] W2, [2] the moves of a round, then the run counts of the reductions
     scalars.alloc(8 * sizeof(int64_t));
     double *const d_wmax = scalars.as<double>();
@@ -232,17 +233,15 @@ void louvain_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr
     count_t *const d_runs = scalars.as<count_t>() + 3, *const d_vertices = scalars.as<count_t>() + 4,
                   *const d_comms = scalars.as<count_t>() + 5, *const d_next = scalars.as<count_t>() + 6;
 
-    LAUNCH(louvain_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
-    LAUNCH(louvain_check_kernel<true>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, part_col.as<int>(),
-           part_val.as<int>());
-    HIPCHK(launch_knn_bad(part_col.as<int>(), blocks, part_val.as<int>(), blocks, bad.as<int>(), st));
+    LAUNCH(entry_rows_kernel, nnz, st, indptr, (int64_t)n, nnz, rowof.as<int32_t>());
+    LAUNCH(graph_entries_check_kernel<true>, nnz, st, indptr, indices, data, rowof.as<int32_t>(), n, nnz, w.dev() + BAD_COLUMNS,
+           w.dev() + BAD_VALUES);
     temp.run([&](void *t, size_t &b) { return rocprim::reduce(t, b, data, d_wmax, 0.0, (size_t)nnz, Larger(), st); });
-    int h_bad[2];
     double wmax = 0.0;
     HIPCHK(hipMemcpyAsync(&wmax, d_wmax, sizeof wmax, hipMemcpyDeviceToHost, st));
-    d2h(h_bad, bad, sizeof h_bad, st);
-    if (h_bad[0] != INT_MAX) throw std::invalid_argument(louvain_bad_columns(h_bad[0]));
-    if (h_bad[1] != INT_MAX) throw std::invalid_argument(louvain_bad_values(h_bad[1]));
+    w.fetch(st);
+    w.refuse(BAD_COLUMNS, louvain_bad_columns);
+    w.refuse(BAD_VALUES, louvain_bad_values);
     if (!(wmax > 0.0)) return finish(n, 0, 0, 0);
 
     // the level's graph: level 0 reads the caller's indptr and indices, the later ones two sets of buffers in turn
@@ -279,7 +278,7 @@ void louvain_on_device(hipStream_t st, int n, int64_t nnz, const int64_t *indptr
 
     int64_t levels = 0, rounds = 0, w2_first = 0;
     for (int level = 0; level < LOUVAIN_LEVELS; ++level) {
-        if (level > 0) LAUNCH(louvain_rows_kernel, nnz_l, st, ip, nl, nnz_l, rowof.as<int32_t>());
+        if (level > 0) LAUNCH(entry_rows_kernel, nnz_l, st, ip, nl, nnz_l, rowof.as<int32_t>());
         // k_i: the rows are runs of rowof already; rows without entries keep 0
         HIPCHK(hipMemsetAsync(k.p, 0, (size_t)nl * sizeof(int64_t), st));
         LAUNCH(louvain_rowkeys_kernel, nnz_l, st, rowof.as<int32_t>(), nnz_l, kb);
@@ -387,7 +386,7 @@ int schpf_louvain_device(int device, void *stream, int n, const int64_t *indptr,
         use_device(device);
         std::unique_ptr<TempStream> own;
         hipStream_t st = pick_stream(stream, own);
-        const int64_t nnz = louvain_indptr_on_device(st, n, indptr);
+        const int64_t nnz = indptr_on_device(st, n, indptr, louvain_bad_indptr);
         if (const char *why = louvain_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
         int64_t result[4];
         louvain_on_device(st, n, nnz, indptr, indices, data, gamma, labels, result);
@@ -408,7 +407,7 @@ int schpf_louvain(int device, int n, const int64_t *indptr, const int32_t *indic
         TempStream ts;
         DevBuf d_indptr, d_indices, d_data, d_labels;
         h2d<int64_t>(d_indptr, indptr, (size_t)n + 1, ts.st);
-        const int64_t nnz = louvain_indptr_on_device(ts.st, n, d_indptr.as<int64_t>());   // the host's indptr[n] if it passes
+        const int64_t nnz = indptr_on_device(ts.st, n, d_indptr.as<int64_t>(), louvain_bad_indptr);   // the host's indptr[n] if it passes
         if (const char *why = louvain_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
         h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);
         h2d<double>(d_data, data, (size_t)nnz, ts.st);

@@ -3,8 +3,10 @@
 // an integer sum -- exact in any order.  The definition is in include/schpf_hip.h; host.cpp's serial restatement gives the
 // same bits.  One sort serves all pairs; no thread and no workgroup walks a gene.
 //
-//   (rank_sums_device.h: the checks of indptr, the cell ids, the values and the labels, the gene of every entry, n[g])
-//   pair_check_kernel       one thread per pair: two different groups in [0, G); the smallest offending row of a workgroup
+//   (graph_device.h, rank_sums_device.h: the checks of indptr, the cell ids, the values and the labels, the gene of every
+//   entry, n[g])
+//   pair_check_kernel       one thread per pair: two different groups in [0, G); the smallest offending row into the last
+//                           word of the call's record
 //   pair_degree_kernel      deg[g] = the pair rows that name g; (rocPRIM exclusive scan: side_ptr[G + 1], T = 2 P sides)
 //   pair_sides_kernel       the sides of group g at side_ptr[g] ..: the pair row and (other group) * 2 + (g is the row's first)
 //   pair_keys_kernel        per entry the key ((gene * G + group) << 32) | float bits; an entry that is a stored zero or whose
@@ -36,15 +38,16 @@ namespace {
 constexpr int CHUNK = 512;    // sub-runs per pass of a workgroup: 2 per thread
 constexpr int BINS = 2048;    // (gene, side) bins of a chunk in LDS, u2 and ties: 32 KiB
 
-__global__ __launch_bounds__(256) void pair_check_kernel(const int32_t *__restrict__ pairs, int npairs, int ngroups, int *__restrict__ part)
+__global__ __launch_bounds__(256) void pair_check_kernel(const int32_t *__restrict__ pairs, int npairs, int ngroups,
+                                                         unsigned long long *__restrict__ word)
 {
-    int bad = INT_MAX;
+    unsigned long long bad = NONE;
     GRID_STRIDE(p, npairs)
     {
         const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        if (a < 0 || a >= ngroups || b < 0 || b >= ngroups || a == b) bad = min(bad, (int)p);
+        if (a < 0 || a >= ngroups || b < 0 || b >= ngroups || a == b) offends(bad, p);
     }
-    block_min(bad, part);
+    report_min(word, bad);
 }
 
 // deg is 0 on entry
@@ -219,17 +222,12 @@ void pair_rank_sums_on_device(hipStream_t st, int ncells, int ngenes, int64_t nn
 {
     const int64_t N = ncells, J = ngenes, G = ngroups, P = npairs, T = 2 * P, lists = G * J;
     DevBuf geneof;
-    entries_and_labels_on_device(st, ncells, ngenes, nnz, indptr, indices, data, labels, ngroups, geneof);
-    if (P > 0) {
-        const int64_t blocks = grid_for(P);
-        DevBuf part, bad;
-        part.alloc((size_t)blocks * sizeof(int));
-        bad.alloc(2 * sizeof(int));
-        LAUNCH(pair_check_kernel, P, st, pairs, npairs, ngroups, part.as<int>());
-        HIPCHK(launch_knn_bad(part.as<int>(), blocks, nullptr, 0, bad.as<int>(), st));
-        int h_bad[2];
-        d2h(h_bad, bad, sizeof h_bad, st);
-        if (h_bad[0] != INT_MAX) throw std::invalid_argument(pair_rank_sums_bad_pairs(h_bad[0]));
+    RankWords w;
+    entries_and_labels_on_device(st, ncells, ngenes, nnz, indptr, indices, data, labels, ngroups, geneof, w);
+    if (P > 0) {   // after the labels, as the refusals are ordered: the word is still NONE
+        LAUNCH(pair_check_kernel, P, st, pairs, npairs, ngroups, w.dev() + R_BAD_PAIRS);
+        w.fetch(st);
+        w.refuse(R_BAD_PAIRS, pair_rank_sums_bad_pairs);
     }
 
     HIPCHK(hipMemsetAsync(n, 0, (size_t)G * sizeof(int64_t), st));
@@ -325,7 +323,7 @@ int schpf_pair_rank_sums_device(int device, void *stream, int ncells, int ngenes
             zero_outputs(st, ngenes, ngroups, npairs, n, nexpr, u2, ties);
             return;
         }
-        const int64_t nnz = indptr_on_device(st, ngenes, indptr);
+        const int64_t nnz = indptr_on_device(st, ngenes, indptr, rank_sums_bad_indptr);
         if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
         pair_rank_sums_on_device(st, ncells, ngenes, nnz, indptr, indices, data, labels, ngroups, pairs, npairs, n, nexpr, u2, ties);
     });
@@ -350,7 +348,7 @@ int schpf_pair_rank_sums(int device, int ncells, int ngenes, const int64_t *indp
         TempStream ts;
         DevBuf d_indptr, d_indices, d_data, d_labels, d_pairs, d_n, d_nexpr, d_u2, d_ties;
         h2d<int64_t>(d_indptr, indptr, J + 1, ts.st);
-        const int64_t nnz = indptr_on_device(ts.st, ngenes, d_indptr.as<int64_t>());   // the host's indptr[J] if it passes
+        const int64_t nnz = indptr_on_device(ts.st, ngenes, d_indptr.as<int64_t>(), rank_sums_bad_indptr);   // the host's indptr[J] if it passes
         if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
         h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);
         h2d<float>(d_data, data, (size_t)nnz, ts.st);

@@ -52,10 +52,9 @@ __global__ __launch_bounds__(QC_THREADS) void qc_rows_kernel(const int32_t *__re
     unsigned long long bad = NONE;
     for (int64_t s = blockIdx.x * (int64_t)QC_THREADS + threadIdx.x; s < n_rows; s += (int64_t)gridDim.x * QC_THREADS) {
         const int64_t r = rows[s];
-        if ((r < 0 || r >= ncells) && (unsigned long long)s < bad) bad = (unsigned long long)s;
+        if (r < 0 || r >= ncells) offends(bad, s);
     }
-    bad = wave_min(bad);
-    if ((threadIdx.x & 63) == 0 && bad != NONE) atomicMin(words + W_BAD_ROW, bad);
+    report_min(words + W_BAD_ROW, bad);
 }
 
 __device__ __forceinline__ unsigned int wave_sum32(unsigned int v)
@@ -233,12 +232,12 @@ void stats_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int n_sets, c
     w.reset(st);
     launch_indptr_check(st, m, nnz, w);
     w.fetch(st);
-    if (w.h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(qc_bad_indptr((int64_t)w.h[W_BAD_INDPTR]));
+    w.refuse(W_BAD_INDPTR, qc_bad_indptr);
     launch_entries_check<true>(st, m, w);
     w.fetch(st);
-    if (w.h[W_BAD_INDEX] != NONE) throw std::invalid_argument(qc_bad_index((int64_t)w.h[W_BAD_INDEX]));
-    if (w.h[W_BAD_ORDER] != NONE) throw std::invalid_argument(qc_bad_order((int64_t)w.h[W_BAD_ORDER]));
-    if (w.h[W_BAD_VALUE] != NONE) throw std::invalid_argument(qc_bad_value((int64_t)w.h[W_BAD_VALUE]));
+    w.refuse(W_BAD_INDEX, qc_bad_index);
+    w.refuse(W_BAD_ORDER, qc_bad_order);
+    w.refuse(W_BAD_VALUE, qc_bad_value);
     if (qc_sumsq_overflows(w.h[W_VMAX], m.ncells)) throw std::invalid_argument(qc_bad_sumsq(w.h[W_VMAX], m.ncells));
 
     CSR_LAUNCH(qc_cell_kernel, m.ncells, per_wave, st, m, n_sets, gene_flags, cell_n, cell_total, cell_set_total);
@@ -270,26 +269,25 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
     if (!empty) {
         launch_indptr_check(st, m, nnz, w);
         w.fetch(st);
-        if (w.h[W_BAD_INDPTR] != NONE) throw std::invalid_argument(qc_bad_indptr((int64_t)w.h[W_BAD_INDPTR]));
+        w.refuse(W_BAD_INDPTR, qc_bad_indptr);
         launch_entries_check<false>(st, m, w);
     }
     if (rows && n_rows > 0) CSR_LAUNCH(qc_rows_kernel, n_rows, QC_THREADS, st, rows, n_rows, m.ncells, w.dev());
     w.fetch(st);
-    if (w.h[W_BAD_INDEX] != NONE) throw std::invalid_argument(qc_bad_index((int64_t)w.h[W_BAD_INDEX]));
-    if (w.h[W_BAD_ROW] != NONE) throw std::invalid_argument(qc_bad_rows((int64_t)w.h[W_BAD_ROW]));
+    w.refuse(W_BAD_INDEX, qc_bad_index);
+    w.refuse(W_BAD_ROW, qc_bad_rows);
 
-    DevBuf kept, colmap, len, indptr, temp;
+    DevBuf kept, colmap, len, indptr;
+    Scratch temp;
     int64_t ngenes_kept = m.ngenes, total = 0;
     if (gene_keep) {
         kept.alloc((size_t)(m.ngenes + 1) * sizeof(int32_t));
         colmap.alloc((size_t)(m.ngenes + 1) * sizeof(int32_t));
         CSR_LAUNCH(qc_keep_kernel, m.ngenes + 1, QC_THREADS, st, gene_keep, m.ngenes, kept.as<int32_t>());
-        size_t bytes = 0;
-        HIPCHK(rocprim::exclusive_scan((void *)nullptr, bytes, kept.as<int32_t>(), colmap.as<int32_t>(), (int32_t)0,
-                                       (size_t)(m.ngenes + 1), rocprim::plus<int32_t>(), st));
-        temp.alloc(bytes);
-        HIPCHK(rocprim::exclusive_scan(temp.p, bytes, kept.as<int32_t>(), colmap.as<int32_t>(), (int32_t)0, (size_t)(m.ngenes + 1),
-                                       rocprim::plus<int32_t>(), st));
+        temp.run([&](void *t, size_t &b) {
+            return rocprim::exclusive_scan(t, b, kept.as<int32_t>(), colmap.as<int32_t>(), (int32_t)0, (size_t)(m.ngenes + 1),
+                                           rocprim::plus<int32_t>(), st);
+        });
         int32_t last = 0;
         HIPCHK(hipMemcpyAsync(&last, colmap.as<int32_t>() + m.ngenes, sizeof last, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));

@@ -2,7 +2,8 @@
 // average ranks, twice a rank is an integer, so every output is an integer sum -- exact in any order.  The definition is in
 // include/schpf_hip.h; host.cpp's serial restatement gives the same bits.
 //
-//   (rank_sums_device.h: the checks of indptr, the cell ids, the values and the labels, the gene of every entry, n[g])
+//   (graph_device.h, rank_sums_device.h: the checks of indptr, the cell ids, the values and the labels, each leaving its
+//   smallest offender in a word of the call's record; the gene of every entry; n[g])
 //   rank_sums_keys_kernel        per entry the key (gene << 32) | float bits -- non-negative floats order as their bits; a
 //                                stored zero, -0.0 included, gets the bits 0 -- and the label of its cell as the payload
 //   (rocPRIM radix sort over the occupied bits: a gene's entries stay in indptr[j] .. indptr[j + 1], ascending in value)
@@ -149,7 +150,8 @@ void rank_sums_on_device(hipStream_t st, int ncells, int ngenes, int64_t nnz, co
 {
     const int64_t N = ncells, J = ngenes, G = ngroups;
     DevBuf geneof;
-    entries_and_labels_on_device(st, ncells, ngenes, nnz, indptr, indices, data, labels, ngroups, geneof);
+    RankWords w;
+    entries_and_labels_on_device(st, ncells, ngenes, nnz, indptr, indices, data, labels, ngroups, geneof, w);
 
     HIPCHK(hipMemsetAsync(n, 0, (size_t)G * sizeof(int64_t), st));
     LAUNCH(rank_sums_count_kernel, N, st, labels, ncells, ngroups, (sum_t *)n);
@@ -218,7 +220,7 @@ int schpf_rank_sums_device(int device, void *stream, int ncells, int ngenes, con
             HIPCHK(hipStreamSynchronize(st));
             return;
         }
-        const int64_t nnz = indptr_on_device(st, ngenes, indptr);
+        const int64_t nnz = indptr_on_device(st, ngenes, indptr, rank_sums_bad_indptr);
         if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
         rank_sums_on_device(st, ncells, ngenes, nnz, indptr, indices, data, labels, ngroups, n, zeros, ties, nexpr, rank2);
     });
@@ -244,7 +246,7 @@ int schpf_rank_sums(int device, int ncells, int ngenes, const int64_t *indptr, c
         TempStream ts;
         DevBuf d_indptr, d_indices, d_data, d_labels, d_n, d_zeros, d_ties, d_nexpr, d_rank2;
         h2d<int64_t>(d_indptr, indptr, J + 1, ts.st);
-        const int64_t nnz = indptr_on_device(ts.st, ngenes, d_indptr.as<int64_t>());   // the host's indptr[J] if it passes
+        const int64_t nnz = indptr_on_device(ts.st, ngenes, d_indptr.as<int64_t>(), rank_sums_bad_indptr);   // the host's indptr[J] if it passes
         if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
         h2d<int32_t>(d_indices, indices, (size_t)nnz, ts.st);
         h2d<float>(d_data, data, (size_t)nnz, ts.st);

@@ -9,14 +9,14 @@
 #include <cstdlib>
 #include <memory>
 
-#include "common.h"
+#include "device_call.h"
 #include "philox.h"
 
 namespace schpf {
 namespace {
 
 constexpr int TH_THREADS = 256;
-constexpr unsigned long long NONE = ~0ull;
+constexpr unsigned TH_BLOCKS = 4096;   // workgroups of a pass at the most: every wavefront ends in atomics
 // the words both passes share in device memory: the four statistics of the C ABI, the length of the heavy list, and
 // the smallest offending entries
 enum { W_TRAIN_NNZ = 0, W_TEST_NNZ, W_TRAIN_SUM, W_TEST_SUM, W_HEAVY, W_BAD_INDEX, W_BAD_VALUE, W_COUNT };
@@ -50,14 +50,6 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 // the pair of one entry and its share of the statistics
 struct Tally {
@@ -82,11 +74,11 @@ __global__ __launch_bounds__(TH_THREADS) void thin_light_kernel(ThinArgs a, unsi
         const long long r = load_index(a.row, a.idx_kind, e), c = load_index(a.col, a.idx_kind, e);
         const double d = load_value(a.val, a.val_kind, e);
         if (thin_index_bad(r) || thin_index_bad(c)) {
-            if ((unsigned long long)e < bad_index) bad_index = (unsigned long long)e;
+            offends(bad_index, e);
             continue;
         }
         if (thin_value_bad(d)) {
-            if ((unsigned long long)e < bad_value) bad_value = (unsigned long long)e;
+            offends(bad_value, e);
             continue;
         }
         const uint32_t x = (uint32_t)d;
@@ -104,15 +96,13 @@ __global__ __launch_bounds__(TH_THREADS) void thin_light_kernel(ThinArgs a, unsi
     tally.test_nnz = wave_sum(tally.test_nnz);
     tally.train_sum = wave_sum(tally.train_sum);
     tally.test_sum = wave_sum(tally.test_sum);
-    bad_index = wave_min(bad_index);
-    bad_value = wave_min(bad_value);
+    report_min(words + W_BAD_INDEX, bad_index);
+    report_min(words + W_BAD_VALUE, bad_value);
     if ((threadIdx.x & 63) == 0) {
         if (tally.train_nnz) atomicAdd(words + W_TRAIN_NNZ, tally.train_nnz);
         if (tally.test_nnz) atomicAdd(words + W_TEST_NNZ, tally.test_nnz);
         if (tally.train_sum) atomicAdd(words + W_TRAIN_SUM, tally.train_sum);
         if (tally.test_sum) atomicAdd(words + W_TEST_SUM, tally.test_sum);
-        if (bad_index != NONE) atomicMin(words + W_BAD_INDEX, bad_index);
-        if (bad_value != NONE) atomicMin(words + W_BAD_VALUE, bad_value);
     }
 }
 
@@ -160,11 +150,6 @@ struct ThinScratch {
     }
 };
 
-unsigned grid_for(int64_t n, int per_block)
-{
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 4096));
-}
-
 // Both passes over nnz > 0 entries in device memory, on `st`; synchronises it.  The outputs of a call that reports an
 // offender are incomplete.
 ThinOutcome thin_on_device(hipStream_t st, ThinScratch &scratch, int64_t nnz, const void *row, const void *col, int idx_kind,
@@ -175,7 +160,7 @@ ThinOutcome thin_on_device(hipStream_t st, ThinScratch &scratch, int64_t nnz, co
     HIPCHK(hipMemsetAsync(words + W_BAD_INDEX, 0xFF, 2 * sizeof(unsigned long long), st));   // NONE
     const ThinArgs a{nnz, row, col, val, idx_kind, val_kind, (uint32_t)seed, (uint32_t)(seed >> 32), T, train, test,
                      scratch.heavy.as<int32_t>()};
-    hipLaunchKernelGGL(thin_light_kernel, dim3(grid_for(nnz, TH_THREADS)), dim3(TH_THREADS), 0, st, a, words);
+    hipLaunchKernelGGL(thin_light_kernel, dim3(std::min(grid_for(nnz, TH_THREADS), TH_BLOCKS)), dim3(TH_THREADS), 0, st, a, words);
     HIPCHK(hipGetLastError());
     unsigned long long h[W_COUNT];
     d2h(h, scratch.words, sizeof h, st);   // the one small copy between the passes
@@ -185,7 +170,7 @@ ThinOutcome thin_on_device(hipStream_t st, ThinScratch &scratch, int64_t nnz, co
     const int64_t n_heavy = (int64_t)h[W_HEAVY];
     if (n_heavy > nnz) throw std::logic_error("thinning: the heavy list is longer than the matrix");
     if (n_heavy > 0 && out.first_bad_index < 0 && out.first_bad_value < 0) {
-        hipLaunchKernelGGL(thin_heavy_kernel, dim3(grid_for(n_heavy, TH_THREADS / 64)), dim3(TH_THREADS), 0, st, a, n_heavy,
+        hipLaunchKernelGGL(thin_heavy_kernel, dim3(std::min(grid_for(n_heavy, TH_THREADS / 64), TH_BLOCKS)), dim3(TH_THREADS), 0, st, a, n_heavy,
                            words);
         HIPCHK(hipGetLastError());
         d2h(h, scratch.words, W_BAD_INDEX * sizeof(unsigned long long), st);
@@ -205,14 +190,6 @@ uint32_t threshold_or_throw(double frac)
     uint32_t T = 0;
     if (!thin_threshold(frac, &T)) throw std::invalid_argument("frac must be in (0, 1) and at least 2^-32");
     return T;
-}
-
-void use_device(int device)
-{
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device");
-    HIPCHK(hipSetDevice(device));
 }
 
 // an index error before a value error, the rule of schpf_upload_coo_device
@@ -248,11 +225,8 @@ int schpf_thin_counts_device(int device, void *stream, int64_t nnz, const void *
         use_device(device);
         for (int k = 0; k < 4; ++k) stats[k] = 0;
         if (nnz == 0) return;
-        // NULL: a stream of the call's own; SCHPF_STREAM_DEFAULT: the device's null stream; else the given handle
         std::unique_ptr<TempStream> own;
-        hipStream_t st = nullptr;
-        if (!stream) { own.reset(new TempStream); st = own->st; }
-        else if (stream != SCHPF_STREAM_DEFAULT) st = (hipStream_t)stream;
+        hipStream_t st = pick_stream(stream, own);
         ThinScratch scratch;
         scratch.alloc(nnz);
         const ThinOutcome out = thin_on_device(st, scratch, nnz, row, col, idx_kind, val, val_kind, T, seed, train, test);
