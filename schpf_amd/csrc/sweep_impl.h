@@ -119,6 +119,10 @@ template <typename T, int LPC> __device__ __forceinline__ T group_max(T v)
 //        (1e-12) and of random sign, so it averages out in the sums over a row's nonzeros;
 //   f32: v_rcp_f32 is good to 1 ulp: x * rcp(s) is within 2 ulp.
 // fast_div_exact keeps the residual correction (<= 1 ulp) for the paths that are not VALU-bound.
+// Nothing checks "normal" in the tile loops: the reciprocal does.  v_rcp_f64 overflows below 2^-1024, before a denormal
+// s has lost three bits; v_rcp_f32 was measured on an MI355X to return inf for every denormal s (nothing relies on it:
+// were it to keep them, it overflows below 2^-128); inf, or a sum of huge weights that overflows, sends the group to
+// the cold path (tests/_fallback_reference.py derives the bound for either behaviour, tests/test_fallback_gpu.py holds it).
 __device__ __forceinline__ double fast_div(double x, double s)
 {
     double r = __builtin_amdgcn_rcp(s);
@@ -1297,7 +1301,9 @@ __device__ __forceinline__ void tile_sweep_task_window(const TileArgs<T> &a, con
         T probe = T(0);
 #pragma unroll
         for (int k = 0; k < KL; ++k) probe = fma_t(acc[k], T(0), probe);   // 0, or NaN
-        any_bad = !(probe == T(0));
+        // An inf reciprocal poisons every lane of the group, but a sum of finite weights x / s (s a small normal number)
+        // overflows only in the lanes whose factors carry weight: the group must agree before slow_nonzero's DPP exchanges
+        any_bad = !(group_sum<T, LPC>(probe) == T(0));
     }
     if (MODE == MODE_PHI && __builtin_expect(any_bad && live, 0)) {   // group-uniform; rare: see slow_nonzero
         slow_task_row<T, NV, LPC, PACK>(a.entries, (size_t)a.task_wave_off[(size_t)task * a.wpb + wv] + grp, st, w0, w1,
