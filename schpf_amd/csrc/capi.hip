@@ -438,6 +438,13 @@ template <typename T> struct Engine final : Uploader {
         const bool sharded = flags_ & SCHPF_SHARDED;
         const bool only_gene = flags_ & SCHPF_LOCAL_GENE, only_cell = flags_ & SCHPF_LOCAL_CELL;
         const bool do_cell = !only_gene || only_cell, do_gene = !only_cell || only_gene;
+        if (sharded && sums_stale) {
+            // after a fused iteration the exchange buffer's tail still mirrors an older sum of E[theta], and step_finish
+            // would bring it up to date behind the all-reduce, with this rank's sum alone: do it before the packing
+            reduce_colsums(0, s_theta);
+            reduce_colsums(1, s_beta);
+            sums_stale = false;
+        }
         if (pending_init == 0 && mx.dual_slots > 0 && do_gene && do_cell && !freeze) {   // dual_slots: tile plans only
             // both sweeps read the same old tables: one launch (timed as kind 0, see schpf_profile_read)
             ScopedTimer tm(prof, stream, 0);
