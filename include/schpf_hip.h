@@ -649,6 +649,58 @@ int schpf_debug_pair_rank_sums(int ncells, int ngenes, const int64_t *indptr, co
                                const int32_t *labels, int ngroups, const int32_t *pairs, int npairs, int64_t *n, int64_t *nexpr,
                                int64_t *u2, int64_t *ties);
 
+/* Pearson residual variance per gene: the two sums behind "which genes vary more than a negative-binomial
+ * null explains" (Lause et al. 2021; scanpy's highly_variable_genes(flavor="pearson_residuals")), over ALL N J pairs, zeros
+ * included, from the raw counts.
+ * Input.  The count matrix gene-major as for schpf_rank_sums, ncells = N cells, ngenes = J genes: indptr[J + 1] (int64),
+ *   indices (int32 cell ids, strictly ascending within a gene), data (float32: integer counts in [0, 2^24]; -0.0 is 0; stored
+ *   zeros are zeros like the implicit ones), nnz = indptr[J].  inv_theta = 1 / theta >= 0, the inverse of the null's
+ *   overdispersion (0: the Poisson null).  clip in (0, inf]: the bound of a residual's size.
+ *   Refused before anything is read, in this order:
+ *     "hvg: ncells, ngenes and nnz must be in [0, 2^31)"
+ *     "hvg: inv_theta must be finite and >= 0"
+ *     "hvg: clip must be > 0"  (a NaN is refused)
+ *     "hvg: sum and sumsq must not be NULL"  (J > 0)
+ *     "hvg: indptr must not be NULL"  (J > 0)
+ *     "hvg: indices and data must not be NULL"  (nnz > 0)
+ *   then, M the smallest offending gene, structure before values, indptr before the cell ids:
+ *     "hvg: indptr must be 0 at gene 0, must be non-decreasing and must end at nnz; offending gene M"  (indptr[0] != 0: gene 0;
+ *       indptr[M + 1] < indptr[M]: gene M; indptr[J] != nnz: gene J - 1; J = 0 with nnz != 0: gene 0)
+ *     "hvg: cell ids must be in [0, ncells) and strictly ascending within a gene; offending gene M"
+ *     "hvg: values must be integer counts in [0, 2^24]; offending gene M"  (a fraction, a negative, a denormal, inf, nan)
+ *   A refused call leaves the outputs untouched.  No input aborts.
+ * Definition, all arithmetic in double.  n_c = the total of cell c, s_g = the total of gene g, T = the total of all, exact
+ *   in int64.  q_g = (double)s_g / (double)T,  mu_cg = (double)n_c * q_g,
+ *     r_cg = min(clip, max(-clip, (x_cg - mu_cg) / sqrt(mu_cg (1 + mu_cg inv_theta)))),   r_cg = 0 where mu_cg = 0
+ *   (a gene or a cell without counts, T = 0).  S1_g = the sum of r_cg over all N cells, S2_g = the sum of r_cg^2.  The
+ *   variance of the residuals of gene g (ddof = 0) is S2_g / N - (S1_g / N)^2.
+ * Output.  sum[J] = S1, sumsq[J] = S2 (double).  Optional, skipped when NULL: cell_total[N] = n_c, gene_total[J] = s_g (int64).
+ * How it is summed.  A zero entry's residual z(mu) = -min(clip, sqrt(mu / (1 + mu inv_theta))) depends on the cell only through
+ *   n_c:  S1_g = the sum over the distinct cell totals u, m_u cells each, of m_u z(u q_g)  +  the sum over the stored
+ *   entries with x > 0 of r_cg - z(mu_cg);  S2_g likewise with squares.  There are no floating-point atomics and the order of
+ *   every sum is fixed by the input alone: two calls, two streams, host or device pointers give the same bits.  The first
+ *   part sees only the multiset of the cell totals and does not change by a bit when the cells are renumbered.  The second
+ *   part adds a gene's entries in an order fixed by their position in the gene's segment: it is NOT invariant under a
+ *   renumbering of the cells, which moves the sums by rounding only.  Against the definition summed in double, |S1 - exact|
+ *   <= 4 N 2^-53 * the sum of |r_cg| and |S2 - exact| <= 4 N 2^-53 S2 (tests/test_residual_var_gpu.py).
+ * N = 0 or J = 0 or nnz = 0 succeeds: every output that is not NULL is written as zeros.  Stateless; device memory that
+ *   cannot be had returns SCHPF_ERR_NO_MEMORY (scratch: 4 nnz bytes during the checks, then 44 N + 8 J and the sort's own).
+ * _device: indptr, indices, data and the outputs are DEVICE pointers on `device`; stream as in schpf_thin_counts_device;
+ *   synchronised before the call returns.
+ * schpf_residual_var: host pointers, staged through the device; the same bits.
+ * schpf_debug_residual_var: test hook (host only, no GPU needed): the definition walked serially over all N cells of every
+ *   gene, with the same refusals.  It knows nothing of the split and is not bit-equal to the device: both are held to the
+ *   bound above. */
+int schpf_residual_var_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr,
+                              const int32_t *indices, const float *data, double inv_theta, double clip, double *sum, double *sumsq,
+                              int64_t *cell_total, int64_t *gene_total);
+int schpf_residual_var(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                       const float *data, double inv_theta, double clip, double *sum, double *sumsq, int64_t *cell_total,
+                       int64_t *gene_total);
+int schpf_debug_residual_var(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                             const float *data, double inv_theta, double clip, double *sum, double *sumsq, int64_t *cell_total,
+                             int64_t *gene_total);
+
 /* Simulated doublets: rows that are the sum of two observed cells, the first step of Scrublet's doublet
  * score.  Integer work whose result is fully determined: every schedule gives the same bits.
  * Parents.  Simulated row s has the parents (a, b):  w = philox4x32_10(counter (s & 0xffffffff, s >> 32, 0, 1), key (low,

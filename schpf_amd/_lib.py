@@ -107,6 +107,9 @@ SIGNATURES = {
     "schpf_pair_rank_sums_device": [_int, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp],
     "schpf_pair_rank_sums": [_int, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp],
     "schpf_debug_pair_rank_sums": [_int, _int, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp],
+    "schpf_residual_var_device": [_int, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "schpf_residual_var": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp],
+    "schpf_debug_residual_var": [_i64, _i64, _i64, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp],
     "schpf_doublet_parents": [_i64, _i64, _i64, ctypes.c_uint64, _vp],
     "schpf_doublet_parents_device": [_int, _vp, _i64, _i64, _i64, ctypes.c_uint64, _vp],
     "schpf_doublet_rows_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _i64, _vp, _vp, _vp, _vp, _i64],

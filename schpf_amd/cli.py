@@ -214,6 +214,12 @@ def _parser():
     qc.add_argument("--write-filtered", default=False, action="store_true",
                     help="Also write the filtered matrix (filtered.mtx) and the 0-based indices of the cells and genes it "
                          "keeps (kept_cells.txt, kept_genes.txt).")
+    qc.add_argument("--n-top-genes", type=int, default=None, metavar="N",
+                    help="Also select the N most variable genes by the variance of their Pearson residuals among the cells "
+                         "and genes that pass the thresholds (gene_hvg.txt: residual variance, rank, 0/1 per gene; a gene "
+                         "that fails --min-cells has nan, -1, 0).  With --write-filtered only the selected genes are kept.")
+    qc.add_argument("--hvg-theta", type=float, default=None, metavar="T",
+                    help="Overdispersion of the negative-binomial null of --n-top-genes; inf is the Poisson null. [100]")
     return parser
 
 
@@ -576,6 +582,25 @@ def _qc(args, outprefix):
                                                      float(found["gene_mean"][j]), float(found["gene_var"][j])))
     print(".....{} of {} cells and {} of {} genes pass".format(int(cell_keep.sum()), len(cell_keep), int(gene_keep.sum()),
                                                                 len(gene_keep)))
+    if args.n_top_genes is not None:
+        from .qc import submatrix
+        from .variable_genes import highly_variable_genes
+        print("Selecting variable genes.....")
+        args.hvg_theta = 100.0 if args.hvg_theta is None else args.hvg_theta
+        hvg = highly_variable_genes(filtered, n_top_genes=args.n_top_genes, theta=args.hvg_theta)
+        kept = np.flatnonzero(gene_keep)       # the genes that fail --min-cells are out before the ranking
+        var, rank, chosen = np.full(len(gene_keep), np.nan), np.full(len(gene_keep), -1, np.int64), np.zeros(len(gene_keep), bool)
+        var[kept], rank[kept], chosen[kept] = hvg["residual_var"], hvg["rank"], hvg["highly_variable"]
+        with open(outprefix + "gene_hvg.txt", "w") as fh:
+            fh.write("residual_var\trank\thighly_variable\n")
+            for j in range(len(gene_keep)):
+                fh.write("{!r}\t{}\t{}\n".format(float(var[j]), rank[j], int(chosen[j])))
+        print(".....{} of {} genes selected".format(int(chosen.sum()), len(chosen)))
+        filtered, gene_keep = submatrix(filtered, genes=hvg["highly_variable"]), chosen
+    else:
+        if args.hvg_theta is not None:
+            raise ValueError("--hvg-theta belongs to --n-top-genes")
+        del args.n_top_genes, args.hvg_theta         # the arguments file is what it was without the selection
     if args.write_filtered:
         print("Writing filtered data to file.....")
         _write_matrix(outprefix + "filtered.mtx", filtered)

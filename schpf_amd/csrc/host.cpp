@@ -3,7 +3,8 @@
 // (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the connected
 // components and the cluster graph (components.hip), of the shortest-path distances (geodesic.hip), of the rank sums
 // (rank_sums.hip), of the simulated doublets (doublets.hip) with the draw of their parents and of the axis statistics and
-// the submatrix (qc.hip), and the SCHPF_BACKTRACE crash handler.  Nothing here touches the device.
+// the submatrix (qc.hip), of the Pearson residual sums per gene (residual_var.hip), and the SCHPF_BACKTRACE crash handler.
+// Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
@@ -21,6 +22,7 @@
 #include "philox.h"
 #include "policy.h"
 #include "qc.h"
+#include "residual_var.h"
 #include "special.h"
 
 using namespace schpf;
@@ -1007,6 +1009,56 @@ int schpf_debug_pair_rank_sums(int ncells, int ngenes, const int64_t *indptr, co
         std::copy(expr.begin(), expr.end(), nexpr);
         if (P) std::copy(u.begin(), u.end(), u2);
         if (P) std::copy(tie.begin(), tie.end(), ties);
+    });
+}
+
+// residual_var.hip restated: the definition of include/schpf_hip.h as it stands -- every gene walks all N
+// cells, the zeros included, and knows nothing of the split into distinct totals.  The same refusals in the same order
+int schpf_debug_residual_var(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                             const float *data, double inv_theta, double clip, double *sum, double *sumsq, int64_t *cell_total,
+                             int64_t *gene_total)
+{
+    if (const char *why = hvg_bad_args(ncells, ngenes, nnz, indptr, indices, data, inv_theta, clip, sum, sumsq)) return fail("%s", why);
+    return guarded([&] {
+        const int64_t N = ncells, J = ngenes;
+        if (J == 0 && nnz != 0) throw std::invalid_argument(hvg_bad_indptr(0));
+        if (J > 0 && indptr[0] != 0) throw std::invalid_argument(hvg_bad_indptr(0));
+        for (int64_t j = 0; j < J; ++j)
+            if (indptr[j + 1] < indptr[j]) throw std::invalid_argument(hvg_bad_indptr(j));
+        if (J > 0 && indptr[J] != nnz) throw std::invalid_argument(hvg_bad_indptr(J - 1));
+        for (int64_t j = 0; j < J; ++j)
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
+                if (indices[e] < 0 || indices[e] >= N || (e > indptr[j] && indices[e - 1] >= indices[e]))
+                    throw std::invalid_argument(hvg_bad_cells(j));
+        std::vector<int64_t> n((size_t)N, 0), s((size_t)J, 0);
+        int64_t T = 0;
+        for (int64_t j = 0; j < J; ++j)
+            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e) {
+                int64_t x;
+                if (!hvg_count(data[e], x)) throw std::invalid_argument(hvg_bad_values(j));
+                n[(size_t)indices[e]] += x;
+                s[(size_t)j] += x;
+                T += x;
+            }
+        std::vector<double> s1((size_t)J, 0.0), s2((size_t)J, 0.0);
+        for (int64_t j = 0; j < J; ++j) {
+            const double q = hvg_share(s[(size_t)j], T);
+            int64_t e = indptr[j];
+            for (int64_t c = 0; c < N; ++c) {
+                int64_t x = 0;
+                if (e < indptr[j + 1] && indices[e] == c) hvg_count(data[e++], x);
+                const double mu = (double)n[(size_t)c] * q;
+                if (!(mu > 0.0)) continue;   // r = 0
+                const double r = ((double)x - mu) / std::sqrt(mu * (1.0 + mu * inv_theta));
+                const double clipped = std::min(clip, std::max(-clip, r));
+                s1[(size_t)j] += clipped;
+                s2[(size_t)j] += clipped * clipped;
+            }
+        }
+        std::copy(s1.begin(), s1.end(), sum);
+        std::copy(s2.begin(), s2.end(), sumsq);
+        if (cell_total) std::copy(n.begin(), n.end(), cell_total);
+        if (gene_total) std::copy(s.begin(), s.end(), gene_total);
     });
 }
 

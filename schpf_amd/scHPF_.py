@@ -442,6 +442,15 @@ class scHPF(BaseEstimator):
         from .qc import qc_metrics
         return qc_metrics(X, gene_sets=gene_sets, **kwargs)
 
+    @staticmethod
+    def variable_genes(X, **kwargs):
+        """The highly variable genes of the count matrix X (cells x genes) before a fit, on the GPU: the dict of
+        schpf_amd.highly_variable_genes (highly_variable, rank, residual_var, means; kwargs go there: n_top_genes, theta,
+        clip, batch, device).  `schpf_amd.submatrix(X, genes=found["highly_variable"])` is the matrix to fit.  An addition
+        to the reference's surface."""
+        from .variable_genes import highly_variable_genes
+        return highly_variable_genes(X, **kwargs)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta
