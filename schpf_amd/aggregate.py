@@ -12,15 +12,12 @@ id, a cluster) into those labels; `pseudobulk` puts the two together.
     bulk["counts"]          # groups x genes, int64: what DESeq2 takes
     bulk["groups"]          # one (sample, cluster) per row
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
-from .device_input import is_torch_tensor, on_gpu
-from .doublets import _p
-from .qc import _device_of, _gpu_input, _host, _host_arrays, _host_csr
-from .thinning import _VAL_KINDS
+from ._call import array_ptr as _p, device_of, library, stream_of, tensor_ptr as ptr
+from .device_input import (NUMPY_VALUE_KINDS, gpu_csr, host_csr, host_csr_arrays, int32_labels, is_torch_tensor, on_gpu,
+                           to_numpy as _host)
 
 __all__ = ["group_stats", "pseudobulk", "group_codes"]
 
@@ -29,12 +26,11 @@ NAMES = ("n", "nexpr", "total", "sumsq")
 
 def _group_stats_host(ncells, ngenes, indptr, indices, vals, labels, ngroups, sumsq, device):
     """schpf_group_stats on NumPy arrays: [n[G], nexpr[G, J], total[G, J], sumsq[G, J] or None]."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     out = [np.zeros(ngroups, np.int64), np.zeros((ngroups, ngenes), np.int64), np.zeros((ngroups, ngenes), np.int64),
            np.zeros((ngroups, ngenes), np.int64) if sumsq else None]
-    _lib.check(lib.schpf_group_stats(device, ncells, ngenes, len(vals), _p(indptr), _p(indices), _p(vals), _VAL_KINDS[vals.dtype],
-                                     _p(labels), ngroups, out[0].ctypes.data_as(ctypes.c_void_p), *[_p(a) for a in out[1:]]))
+    _lib.check(lib.schpf_group_stats(device, ncells, ngenes, len(vals), _p(indptr), _p(indices), _p(vals),
+                                     NUMPY_VALUE_KINDS[vals.dtype], _p(labels), ngroups, *[_p(a) for a in out]))
     return out
 
 
@@ -58,10 +54,7 @@ def _sizes(labels, ngroups, ncells, ngenes, nnz=0):
 
 def _labels_int32(labels):
     """Labels outside int32 cannot be in [-1, ngroups): the first one is named before the cast could hide it."""
-    bad = (labels < -1) | (labels > np.iinfo(np.int32).max)
-    if bad.any():
-        raise ValueError("group_stats: labels must be in [-1, ngroups); offending cell %d" % int(np.flatnonzero(bad)[0]))
-    return np.ascontiguousarray(labels, dtype=np.int32)
+    return int32_labels(labels, -1, "group_stats: labels must be in [-1, ngroups); offending cell %d")
 
 
 def group_stats(X, labels, ngroups=None, sumsq=True, device=None):
@@ -79,31 +72,29 @@ def group_stats(X, labels, ngroups=None, sumsq=True, device=None):
     row, entry or cell."""
     if on_gpu(X):
         import torch
-        lib = _lib.load()
-        _lib.require_gpu()
+        lib = library()
         lab = (labels if is_torch_tensor(labels) else torch.as_tensor(np.asarray(labels))).detach()
         N, J = int(X.shape[0]), int(X.shape[1])
         G = _sizes(lab, ngroups, N, J)
         if lab.numel() and (int(lab.min()) < -1 or int(lab.max()) > np.iinfo(np.int32).max):
             _labels_int32(lab.cpu().numpy())
-        inp, dev = _gpu_input(X, device)
+        inp, dev = gpu_csr(X, device)
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT)
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+            stream = stream_of(dev)
             lab = lab.to(device=dev, dtype=torch.int32).contiguous()
             n = torch.zeros(max(G, 1), dtype=torch.int64, device=dev)
             out = [torch.zeros((G, J), dtype=torch.int64, device=dev) for _ in range(3 if sumsq else 2)] + ([] if sumsq else [None])
             _lib.check(lib.schpf_group_stats_device(inp.device, stream, N, J, inp.nnz, ptr(inp.major), inp.major_kind, ptr(inp.minor),
-                                                    inp.minor_kind, ptr(inp.values), inp.value_kind, ptr(lab), G,
-                                                    ctypes.c_void_p(n.data_ptr()), *[ptr(t) for t in out]))
+                                                    inp.minor_kind, ptr(inp.values), inp.value_kind, ptr(lab), G, ptr(n),
+                                                    *[ptr(t) for t in out]))
         found = [n] + out
     else:
         lab = _host(labels)
         G = _sizes(lab, ngroups, int(X.shape[0]), int(X.shape[1]))
         lab = _labels_int32(lab)
-        C = _host_csr(X, canonical=True)
+        C = host_csr(X, canonical=True)
         N, J = C.shape
-        found = _group_stats_host(N, J, *(_host_arrays(C) + (lab, G, bool(sumsq), _device_of(device))))
+        found = _group_stats_host(N, J, *(host_csr_arrays(C) + (lab, G, bool(sumsq), device_of(device))))
     return {name: a for name, a in zip(NAMES, found) if a is not None}
 
 

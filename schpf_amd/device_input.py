@@ -1,13 +1,20 @@
-"""What DeviceCAVI.upload accepts, normalised: a SciPy sparse matrix, or a torch sparse COO / CSR tensor.
+"""What the library is handed, normalised: the count matrices, graphs and labels that `DeviceCAVI.upload` and the
+stateless operators accept, brought into the forms the entry points take.
 
 `classify(X, shape)` needs no GPU and does not touch one: it looks at the argument's type, layout, dtypes and shape and
 returns a `MatrixInput` that says which entry point of the library takes it -- the host upload (SciPy matrices and CPU
 tensors, the latter converted to a SciPy COO) or the device uploads of DESIGN.md 13 (tensors in GPU memory, handed over
 by pointer).  An uncoalesced COO tensor keeps its duplicates as separate observations, like a SciPy COO.
+
+Below it, one function per form an operator asks for: of a matrix in GPU memory `gpu_csr`, `gpu_coo` and
+`gpu_csc`; of a matrix anywhere else `host_csr` with `host_csr_arrays`, and `host_csc`; of a square graph `gpu_graph`, and
+`host_graph_matrix` with `host_graph`; of labels `int32_labels`.  The conversions are plumbing, done with torch where the
+tensor lives or with SciPy; the pointers, the device and the stream of the call itself are in `_call`.
 """
 import numpy as np
 
 from . import _lib
+from ._call import same_device
 
 ACCEPTED = ("a SciPy sparse matrix, a 2-d torch sparse COO tensor (torch.sparse_coo_tensor) or a 2-d torch sparse CSR "
             "tensor (torch.sparse_csr_tensor) with int32, int64, float32 or float64 values")
@@ -15,6 +22,9 @@ ACCEPTED = ("a SciPy sparse matrix, a 2-d torch sparse COO tensor (torch.sparse_
 _VALUE_KINDS = {"torch.int32": _lib.VAL_I32, "torch.int64": _lib.VAL_I64, "torch.float32": _lib.VAL_F32,
                 "torch.float64": _lib.VAL_F64}
 _INDEX_KINDS = {"torch.int32": _lib.IDX_I32, "torch.int64": _lib.IDX_I64}
+# the value kinds of NumPy arrays; values of another dtype go to the library as float64
+NUMPY_VALUE_KINDS = {np.dtype(np.int32): _lib.VAL_I32, np.dtype(np.int64): _lib.VAL_I64,
+                     np.dtype(np.float32): _lib.VAL_F32, np.dtype(np.float64): _lib.VAL_F64}
 
 
 class MatrixInput(object):
@@ -36,6 +46,21 @@ def is_torch_tensor(X):
 def on_gpu(X):
     """True for a torch tensor in GPU memory (the inputs that take the device uploads)."""
     return is_torch_tensor(X) and X.device.type == "cuda"
+
+
+def from_torch(x):
+    """Anything of torch's, with a `.layout` or without: the looser question that the neighbour, graph and path operators
+    have always asked of their arguments.  `is_torch_tensor` is the one for count matrices."""
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def from_torch_on_gpu(x):
+    return from_torch(x) and x.is_cuda
+
+
+def to_numpy(a):
+    """A tensor fetched to the host, anything else through np.asarray."""
+    return a.detach().cpu().numpy() if is_torch_tensor(a) else np.asarray(a)
 
 
 def shape_of(X):
@@ -102,3 +127,143 @@ def _to_scipy(layout, shape, major, minor, values):
     else:
         row = np.repeat(np.arange(shape[0], dtype=np.int64), np.diff(major.numpy()))
     return coo_matrix((values, (row, minor)), shape=tuple(shape))
+
+
+# ---- a count matrix in GPU memory ----
+
+def gpu_csr(X, device=None):
+    """A sparse CSR / COO tensor on a GPU -> (its MatrixInput as a CSR, its torch device).  A COO is brought to canonical
+    CSR with torch on that GPU, as plumbing: coalesce() sums the duplicates and orders the entries by row, then column.
+    `device`: the ordinal the caller asked for, refused if it names another GPU."""
+    import torch
+    with torch.cuda.device(X.device):
+        inp = classify(X)
+        if inp.kind != "csr":
+            C = X.detach().coalesce()
+            rows, cols = C.indices()[0], C.indices()[1]
+            crow = torch.zeros(inp.shape[0] + 1, dtype=torch.int64, device=X.device)
+            if inp.shape[0]:
+                crow[1:] = torch.cumsum(torch.bincount(rows, minlength=inp.shape[0]), 0)
+            inp = classify(torch.sparse_csr_tensor(crow, cols.contiguous(), C.values().contiguous(), size=inp.shape))
+    same_device(inp.device, device, "X")
+    return inp, torch.device("cuda", inp.device)
+
+
+def gpu_coo(X):
+    """A sparse COO / CSR tensor on a GPU -> (rows, cols, values) of its coalesced COO form: duplicates summed, row-major."""
+    import torch
+    if X.layout not in (torch.sparse_coo, torch.sparse_csr):
+        raise TypeError("a matrix on the GPU must be a torch sparse COO or CSR tensor, got layout %s" % X.layout)
+    if X.dim() != 2:
+        raise ValueError("X must be a 2-d cell x gene matrix, got a tensor of shape %s" % (tuple(X.shape),))
+    X = X.detach()
+    if X.layout == torch.sparse_csr:
+        crow = X.crow_indices().to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(X.shape[0], device=X.device), crow[1:] - crow[:-1])
+        X = torch.sparse_coo_tensor(torch.stack([rows, X.col_indices().to(torch.int64)]), X.values(), size=tuple(X.shape))
+    X = X.coalesce()
+    return X.indices()[0], X.indices()[1], X.values()
+
+
+def gpu_csc(X):
+    """A sparse COO / CSR tensor on a GPU -> (indptr int64, cell ids int32, values float32) of its CSC form, duplicates
+    summed, with torch on that GPU."""
+    import torch
+    rows, cols, values = gpu_coo(X)
+    N, J = int(X.shape[0]), int(X.shape[1])
+    order = torch.argsort(cols * N + rows)              # gene-major, the cells ascending within a gene
+    indptr = torch.zeros(J + 1, dtype=torch.int64, device=X.device)
+    if J:
+        indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=J), 0)
+    return indptr, rows[order].to(torch.int32).contiguous(), values[order].to(torch.float32).contiguous()
+
+
+# ---- a count matrix anywhere else ----
+
+def _host_matrix(X):
+    return classify(X).matrix if is_torch_tensor(X) else X          # a tensor in host memory: as SciPy
+
+
+def host_csr(X, canonical):
+    """Anything that is not a GPU tensor as a SciPy CSR that is the caller's no longer; canonical: duplicates summed."""
+    from scipy.sparse import csr_matrix, issparse
+    X = _host_matrix(X)
+    C = X.tocsr() if issparse(X) else csr_matrix(X)
+    if canonical:
+        if C is X:
+            C = C.copy()
+        C.sum_duplicates()                               # also sorts the columns of every row
+    return C
+
+
+def host_csr_arrays(C):
+    """(indptr int64, indices int32, values of a kind in NUMPY_VALUE_KINDS) of a SciPy CSR, C-contiguous."""
+    data = np.ascontiguousarray(C.data)
+    vals = data if data.dtype in NUMPY_VALUE_KINDS else data.astype(np.float64)
+    return np.ascontiguousarray(C.indptr, dtype=np.int64), np.ascontiguousarray(C.indices, dtype=np.int32), vals
+
+
+def host_csc(X):
+    """Anything that is not a GPU tensor -> (N, J, the C-contiguous arrays of the canonical CSC form: int64, int32, float32)."""
+    from scipy.sparse import csc_matrix, issparse
+    X = _host_matrix(X)
+    C = csc_matrix(X) if not issparse(X) else X.tocsc()
+    if C is X:
+        C = C.copy()
+    C.sum_duplicates()                    # also sorts the cells of every gene
+    N, J = C.shape
+    return (N, J, np.ascontiguousarray(C.indptr, dtype=np.int64), np.ascontiguousarray(C.indices, dtype=np.int32),
+            np.ascontiguousarray(C.data, dtype=np.float32))
+
+
+# ---- a square graph ----
+
+def gpu_graph(graph, device, values):
+    """(torch device, n, indptr int64, cols int32, data float64 or None) of a torch.sparse_csr_tensor on a GPU."""
+    import torch
+    if graph.layout != torch.sparse_csr:
+        raise ValueError("a graph on the GPU must be a torch.sparse_csr_tensor")
+    if graph.dim() != 2 or graph.shape[0] != graph.shape[1]:
+        raise ValueError("graph must be a square matrix")
+    dev = graph.device
+    same_device(dev.index, device, "graph")
+    with torch.cuda.device(dev):
+        indptr = graph.crow_indices().detach().to(torch.int64).contiguous()
+        cols = graph.col_indices().detach().to(torch.int32).contiguous()
+        data = graph.values().detach().to(torch.float64).contiguous() if values else None
+    return dev, graph.shape[0], indptr, cols, data
+
+
+def host_graph_matrix(graph):
+    """A SciPy matrix, a dense array or a torch tensor on the host as a square SciPy CSR, its entries as they are stored."""
+    from scipy.sparse import csr_matrix, issparse
+    if from_torch(graph):
+        graph = graph.to_sparse_csr()
+        graph = csr_matrix((graph.values().numpy(), graph.col_indices().numpy(), graph.crow_indices().numpy()),
+                           shape=tuple(graph.shape))
+    G = graph.tocsr() if issparse(graph) else csr_matrix(np.asarray(graph))
+    if G.shape[0] != G.shape[1]:
+        raise ValueError("graph must be a square matrix")
+    return G
+
+
+def host_graph(graph):
+    """(n, indptr int64, indices int32, data float64) of what `host_graph_matrix` takes.  The entries stay as they are
+    stored: columns need not ascend and repeats are harmless; a caller that wants them summed does so on the matrix first."""
+    G = host_graph_matrix(graph)
+    return (G.shape[0], np.ascontiguousarray(G.indptr, dtype=np.int64), np.ascontiguousarray(G.indices, dtype=np.int32),
+            np.ascontiguousarray(G.data, dtype=np.float64))
+
+
+# ---- labels ----
+
+def int32_labels(labels, lowest=None, refusal=None):
+    """Integer labels in host memory as a C-contiguous int32 array.  lowest: a label below it or above int32's largest
+    cannot be meant and is refused with `refusal` before the cast could hide it; a %d in `refusal` takes the first
+    offending position."""
+    labels = np.asarray(labels)
+    if lowest is not None:
+        bad = (labels < lowest) | (labels > np.iinfo(np.int32).max)
+        if bad.any():
+            raise ValueError(refusal % int(np.flatnonzero(bad)[0]) if "%d" in refusal else refusal)
+    return np.ascontiguousarray(labels, dtype=np.int32)

@@ -9,23 +9,18 @@ work was scheduled.  The embedding is `project()` against the frozen gene factor
 the embedding, `k_sim` -- an integer -- is in the bit contract too.  The score itself is a few lines of NumPy in float64 on
 the host (`scrublet_score`), not part of it.
 """
-import ctypes
 import math
-import os
 
 import numpy as np
 
 from . import _lib
-from .device_input import classify, is_torch_tensor, on_gpu
-from .thinning import _VAL_KINDS, _seed
+from ._call import array_ptr as _p, device_of, library, stream_of, tensor_ptr as ptr
+from .device_input import NUMPY_VALUE_KINDS, classify, gpu_csr, host_csr, host_csr_arrays, is_torch_tensor, on_gpu
+from .thinning import _seed       # one rule for a seed, whichever Philox stream it starts
 
 __all__ = ["simulate_doublets", "doublet_scores", "scrublet_score"]
 
 MAX_K = 128        # the longest neighbour list schpf_knn gives
-
-
-def _p(a):
-    return None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _n_sim(n_sim, ratio, n_obs):
@@ -40,21 +35,6 @@ def _check_parents(shape, n_obs):
         raise ValueError("parents must be an (n_sim, 2) array of rows of X, got shape %s" % (tuple(shape),))
     if n_obs >= 2 ** 31:
         raise ValueError("ncells must be in [0, 2^31), got %d" % n_obs)
-
-
-def _gpu_csr(X):
-    """A sparse CSR / COO tensor on a GPU -> its MatrixInput as a CSR.  A COO is brought to canonical CSR with torch on that
-    GPU, as plumbing: coalesce() sums the duplicates and orders the entries by row, then column."""
-    import torch
-    inp = classify(X)
-    if inp.kind == "csr":
-        return inp
-    C = X.detach().coalesce()
-    rows, cols = C.indices()[0], C.indices()[1]
-    crow = torch.zeros(inp.shape[0] + 1, dtype=torch.int64, device=X.device)
-    if inp.shape[0]:
-        crow[1:] = torch.cumsum(torch.bincount(rows, minlength=inp.shape[0]), 0)
-    return classify(torch.sparse_csr_tensor(crow, cols.contiguous(), C.values().contiguous(), size=inp.shape))
 
 
 def simulate_doublets(X, n_sim=None, ratio=2.0, seed=0, parents=None, device=None):
@@ -75,20 +55,14 @@ def simulate_doublets(X, n_sim=None, ratio=2.0, seed=0, parents=None, device=Non
     sum, columns ascending, also where the sum is 0, so the structure depends on the indices alone.  The columns of a CSR
     must be strictly ascending within a row; what the library refuses raises ValueError naming the smallest offending row,
     entry or pair."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     seed = _seed(seed)
     if on_gpu(X):
         import torch
-        with torch.cuda.device(X.device):
-            inp = _gpu_csr(X)
-        if device is not None and int(device) != inp.device:
-            raise ValueError("X is on GPU %d, device=%d was asked for" % (inp.device, int(device)))
-        dev = torch.device("cuda", inp.device)
+        inp, dev = gpu_csr(X, device)
         N, J = inp.shape
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT)
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+            stream = stream_of(dev)
             if parents is None:
                 n_pairs = _n_sim(n_sim, ratio, N)
                 if n_pairs and N < 1:
@@ -114,16 +88,9 @@ def simulate_doublets(X, n_sim=None, ratio=2.0, seed=0, parents=None, device=Non
                                             out_values[:total].to(inp.values.dtype), size=(n_pairs, J))
         return X_sim, parents
 
-    from scipy.sparse import csr_matrix, issparse
-    if is_torch_tensor(X):                # a tensor in host memory: as SciPy
-        X = classify(X).matrix
-    C = X.tocsr() if issparse(X) else csr_matrix(X)
-    if C is X:
-        C = C.copy()
-    C.sum_duplicates()                    # also sorts the columns of every row
+    from scipy.sparse import csr_matrix
+    C = host_csr(X, canonical=True)
     N, J = C.shape
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
     if parents is None:
         n_pairs = _n_sim(n_sim, ratio, N)
         parents = np.empty((n_pairs, 2), np.int32)
@@ -139,18 +106,15 @@ def simulate_doublets(X, n_sim=None, ratio=2.0, seed=0, parents=None, device=Non
                              % int(np.flatnonzero(((given < 0) | (given >= N)).any(axis=1))[0]))
         parents = np.ascontiguousarray(given, dtype=np.int32)
         n_pairs = parents.shape[0]
-    data = np.ascontiguousarray(C.data)
-    vals = data if data.dtype in _VAL_KINDS else data.astype(np.float64)
-    indptr = np.ascontiguousarray(C.indptr, dtype=np.int64)
-    indices = np.ascontiguousarray(C.indices, dtype=np.int32)
+    indptr, indices, vals = host_csr_arrays(C)
     out_indptr = np.zeros(n_pairs + 1, np.int64)
-    args = (int(device), N, J, C.nnz, _p(indptr), _p(indices), _p(vals), _VAL_KINDS[vals.dtype], n_pairs, _p(parents),
-            _p(out_indptr))
+    args = (device_of(device), N, J, C.nnz, _p(indptr), _p(indices), _p(vals), NUMPY_VALUE_KINDS[vals.dtype], n_pairs,
+            _p(parents), _p(out_indptr))
     _lib.check(lib.schpf_doublet_rows(*(args + (None, None, 0))))                          # the sizes
     total = int(out_indptr[-1])
     out_indices, out_values = np.empty(max(total, 1), np.int32), np.empty(max(total, 1), np.int32)
     _lib.check(lib.schpf_doublet_rows(*(args + (_p(out_indices), _p(out_values), total))))
-    return csr_matrix((out_values[:total].astype(data.dtype), out_indices[:total], out_indptr), shape=(n_pairs, J)), parents
+    return csr_matrix((out_values[:total].astype(C.data.dtype), out_indices[:total], out_indptr), shape=(n_pairs, J)), parents
 
 
 def scrublet_score(k_sim, k_adj, ratio, expected_rate=0.06, rate_sd=0.02):
@@ -173,7 +137,7 @@ def _stack(X, X_sim):
     """X over X_sim as one matrix `project` takes: plumbing, with torch on the GPU of X or with SciPy."""
     if on_gpu(X):
         import torch
-        inp = _gpu_csr(X)
+        inp = gpu_csr(X)[0]
         crow, sim_crow = inp.major.to(torch.int64), X_sim.crow_indices()
         return torch.sparse_csr_tensor(torch.cat([crow, sim_crow[1:] + crow[-1]]),
                                        torch.cat([inp.minor.to(torch.int64), X_sim.col_indices()]),

@@ -10,6 +10,7 @@ import functools
 
 import numpy as np
 
+from ._call import device_of
 from .hpf_hip import compute_pois_llh
 
 __all__ = ["loss_function_for_data", "projection_loss_function", "pois_llh_pointwise",
@@ -43,9 +44,7 @@ def projection_loss_function(loss_function, X, nfactors, model_kwargs={}, proj_k
     pmodel = scHPF(nfactors=nfactors, **model_kwargs)
     from .device_input import as_matrix
     X = as_matrix(X)
-    import os
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    device = device_of(device)
     held = {}    # the held-out cells stay on the device between checks: one upload, one pair of plans
 
     def _projection_loss_function(*, a, ap, bp, c, cp, dp, eta, beta, **kwargs):
@@ -118,9 +117,7 @@ def thinned_mean_negative_pois_llh(X_test, *, theta, beta, frac, device=None, **
     if not is_torch_tensor(X_test):
         return mean_negative_pois_llh(X_test, theta=scaled, beta=beta)
     from .engine import DeviceCAVI
-    import os
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    device = device_of(device)
     with DeviceCAVI(X_test.shape[0], X_test.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
         eng.upload(X_test)
         eng.set_gamma("theta", scaled.vi_shape, scaled.vi_rate)
@@ -137,9 +134,7 @@ def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=N
     device ordinal, default $SCHPF_DEVICE or 0.
     """
     from .engine import DeviceCAVI   # late import, as in projection_loss_function
-    import os
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    device = device_of(device)
     from .device_input import as_matrix
     X = as_matrix(X)          # a SciPy matrix or a torch sparse tensor (in GPU memory: uploaded from there)
     with DeviceCAVI(X.shape[0], X.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
@@ -154,9 +149,7 @@ def elbo(X, *, a, ap, bp, c, cp, dp, xi, eta, theta, beta, terms=False, device=N
 def _rowmean_on_device(X, theta, beta, by, device):
     """X uploaded once, theta / beta set, the per-row loss of axis `by` evaluated on the device."""
     from .engine import DeviceCAVI   # late import, as in projection_loss_function
-    import os
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    device = device_of(device)
     from .device_input import as_matrix
     X = as_matrix(X)          # a SciPy matrix or a torch sparse tensor (in GPU memory: uploaded from there)
     with DeviceCAVI(X.shape[0], X.shape[1], theta.dims[1], dtype=theta.dtype, device=device) as eng:
@@ -220,14 +213,12 @@ def predictive_check(X, *, theta, beta, by="gene", device=None, **kwargs):
     (duplicate coordinates are summed first); it is not uploaded.  A theta whose rate is divided by frac / (1 - frac)
     gives the check for the test part of thinned counts.  `device`: HIP device ordinal, default $SCHPF_DEVICE or 0."""
     from .engine import DeviceCAVI, predicted_moments   # late import, as in projection_loss_function
-    import os
     if by not in ("cell", "gene"):
         raise ValueError("by must be 'cell' or 'gene', got %r" % (by,))
     ncells, ngenes = theta.vi_shape.shape[0], beta.vi_shape.shape[0]
     if X is not None and tuple(int(v) for v in X.shape) != (ncells, ngenes):
         raise ValueError("X has shape %s, theta and beta describe %d cells x %d genes" % (tuple(X.shape), ncells, ngenes))
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    device = device_of(device)
     with DeviceCAVI(ncells, ngenes, theta.dims[1], dtype=theta.dtype, device=device) as eng:
         eng.set_gamma("theta", theta.vi_shape, theta.vi_rate)
         eng.set_gamma("beta", beta.vi_shape, beta.vi_rate)

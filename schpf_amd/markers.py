@@ -6,13 +6,11 @@ the counts as exact int64 sums, the same bits however the work was scheduled.  `
 `rank_genes_groups` turns the integers into z-scores, p-values, Benjamini-Hochberg adjusted p-values, fold changes and
 the fractions of expressing cells -- plain NumPy / SciPy on G x J numbers, not part of the bit contract.
 """
-import ctypes
-import os
-
 import numpy as np
 
 from . import _lib
-from .device_input import is_torch_tensor, on_gpu
+from ._call import array_ptr as _p, device_of, library, same_device, stream_of, tensor_ptr as ptr
+from .device_input import classify, gpu_coo, gpu_csc, host_csc, int32_labels, is_torch_tensor, on_gpu
 
 __all__ = ["rank_sums", "rank_genes_groups", "benjamini_hochberg", "pair_rank_sums", "rank_genes_pairs"]
 
@@ -23,19 +21,12 @@ STATISTICS = ("scores", "pvals", "pvals_adj", "logfoldchanges", "pct_in", "pct_o
 MAX_CELLS = 1 << 21
 
 
-def _p(a):
-    return None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _rank_sums_host(ncells, ngenes, indptr, indices, data, labels, ngroups, device):
     """schpf_rank_sums on the C-contiguous arrays of a CSC matrix (int64, int32, float32) and int32 labels -> the five int64
     arrays n[G], zeros[J], ties[J], nexpr[G, J], rank2[G, J]."""
-    lib = _lib.load()
-    _lib.require_gpu()
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    lib = library()
     out = _outputs(ngroups, ngenes)
-    _lib.check(lib.schpf_rank_sums(int(device), ncells, ngenes, _p(indptr), _p(indices), _p(data), _p(labels), ngroups,
+    _lib.check(lib.schpf_rank_sums(device_of(device), ncells, ngenes, _p(indptr), _p(indices), _p(data), _p(labels), ngroups,
                                    *[_p(a) for a in out]))
     return out
 
@@ -64,76 +55,34 @@ def _check_sizes(ncells, ngenes, ngroups):
         raise ValueError("ngroups * ngenes must be below 2^31, got %d * %d" % (ngroups, ngenes))
 
 
-def _gpu_coo(X):
-    """A sparse COO / CSR tensor on a GPU -> (rows, cols, values) of its coalesced COO form: duplicates summed, row-major."""
-    import torch
-    if X.layout not in (torch.sparse_coo, torch.sparse_csr):
-        raise TypeError("a matrix on the GPU must be a torch sparse COO or CSR tensor, got layout %s" % X.layout)
-    if X.dim() != 2:
-        raise ValueError("X must be a 2-d cell x gene matrix, got a tensor of shape %s" % (tuple(X.shape),))
-    X = X.detach()
-    if X.layout == torch.sparse_csr:
-        crow = X.crow_indices().to(torch.int64)
-        rows = torch.repeat_interleave(torch.arange(X.shape[0], device=X.device), crow[1:] - crow[:-1])
-        X = torch.sparse_coo_tensor(torch.stack([rows, X.col_indices().to(torch.int64)]), X.values(), size=tuple(X.shape))
-    X = X.coalesce()
-    return X.indices()[0], X.indices()[1], X.values()
-
-
-def _gpu_csc(X):
-    """A sparse COO / CSR tensor on a GPU -> (indptr int64, cell ids int32, values float32) of its CSC form, duplicates
-    summed, with torch on that GPU."""
-    import torch
-    rows, cols, values = _gpu_coo(X)
-    N, J = int(X.shape[0]), int(X.shape[1])
-    order = torch.argsort(cols * N + rows)              # gene-major, the cells ascending within a gene
-    indptr = torch.zeros(J + 1, dtype=torch.int64, device=X.device)
-    if J:
-        indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=J), 0)
-    return indptr, rows[order].to(torch.int32).contiguous(), values[order].to(torch.float32).contiguous()
-
-
 def _gpu_inputs(X, labels, ngroups, device):
-    """What a call on a matrix in GPU memory hands to the library: (torch device, N, J, G, int32 labels on that GPU, the CSC
-    arrays of `_gpu_csc`, torch's current stream there as an integer, a tensor -> its pointer)."""
+    """What a call on a matrix in GPU memory hands to the library: (the library, torch device, N, J, G, int32 labels on that
+    GPU, the CSC arrays of `gpu_csc`, torch's current stream there)."""
     import torch
-    _lib.require_gpu()
+    lib = library()
     dev = X.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError("X is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+    same_device(dev.index, device, "X")
     N, J = int(X.shape[0]), int(X.shape[1])
     with torch.cuda.device(dev):
         lab = (labels if is_torch_tensor(labels) else torch.tensor(np.asarray(labels))).detach()
         G = _groups(lab, ngroups, N)
         _check_sizes(N, J, G)
         lab = lab.to(device=dev, dtype=torch.int32).contiguous()
-        indptr, cells, values = _gpu_csc(X)
-        stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
-    return dev, N, J, G, lab, indptr, cells, values, stream, ptr
+        indptr, cells, values = gpu_csc(X)
+        stream = stream_of(dev)
+    return lib, dev, N, J, G, lab, indptr, cells, values, stream
 
 
 def _host_inputs(X, labels, ngroups):
     """What a call on a matrix in host memory hands to the library: (N, J, G, the C-contiguous arrays of the canonical CSC
     form -- int64, int32, float32 -- and the int32 labels)."""
-    from scipy.sparse import csc_matrix, issparse
-    if is_torch_tensor(X):                # a tensor in host memory: as SciPy
-        from .device_input import classify
-        X = classify(X).matrix
     if is_torch_tensor(labels):
         labels = labels.detach().cpu().numpy()
     labels = np.asarray(labels)
-    C = csc_matrix(X) if not issparse(X) else X.tocsc()
-    if C is X:
-        C = C.copy()
-    C.sum_duplicates()                    # also sorts the cells of every gene
-    N, J = C.shape
+    N, J, indptr, indices, data = host_csc(X)
     G = _groups(labels, ngroups, N)
     _check_sizes(N, J, G)
-    if labels.size and (labels.min() < np.iinfo(np.int32).min or labels.max() > np.iinfo(np.int32).max):
-        raise ValueError("labels must be in [-1, ngroups)")
-    return (N, J, G, np.ascontiguousarray(C.indptr, dtype=np.int64), np.ascontiguousarray(C.indices, dtype=np.int32),
-            np.ascontiguousarray(C.data, dtype=np.float32), np.ascontiguousarray(labels, dtype=np.int32))
+    return N, J, G, indptr, indices, data, int32_labels(labels, np.iinfo(np.int32).min, "labels must be in [-1, ngroups)")
 
 
 def rank_sums(X, labels, ngroups=None, device=None):
@@ -152,11 +101,10 @@ def rank_sums(X, labels, ngroups=None, device=None):
     raises ValueError naming the smallest offending gene or cell."""
     if on_gpu(X):
         import torch
-        lib = _lib.load()
-        dev, N, J, G, lab, indptr, cells, values, stream, ptr = _gpu_inputs(X, labels, ngroups, device)
+        lib, dev, N, J, G, lab, indptr, cells, values, stream = _gpu_inputs(X, labels, ngroups, device)
         with torch.cuda.device(dev):
             out = [torch.zeros(s, dtype=torch.int64, device=dev) for s in ((G,), (J,), (J,), (G, J), (G, J))]
-            _lib.check(lib.schpf_rank_sums_device(dev.index, ctypes.c_void_p(stream), N, J, ptr(indptr), ptr(cells), ptr(values),
+            _lib.check(lib.schpf_rank_sums_device(dev.index, stream, N, J, ptr(indptr), ptr(cells), ptr(values),
                                                   ptr(lab), G, *[ptr(t) for t in out]))
         return dict(zip(NAMES, out))
 
@@ -185,7 +133,7 @@ def _scaled(X, target_sum):
     """Every cell's counts scaled to `target_sum` ("median": the median depth of the cells), in float32."""
     if on_gpu(X):
         import torch
-        rows, cols, values = _gpu_coo(X)
+        rows, cols, values = gpu_coo(X)
         values = values.to(torch.float32)
         depth = torch.zeros(X.shape[0], dtype=torch.float32, device=X.device).index_add_(0, rows, values)
         target = float(torch.median(depth)) if isinstance(target_sum, str) and target_sum == "median" else float(target_sum)
@@ -208,7 +156,7 @@ def _group_sums(X, labels, G):
     if on_gpu(X):
         import torch
         lab = (labels if is_torch_tensor(labels) else torch.tensor(np.asarray(labels))).to(X.device).to(torch.int64)
-        rows, cols, values = _gpu_coo(X)
+        rows, cols, values = gpu_coo(X)
         values = values.to(torch.float64)
         onehot = torch.zeros((X.shape[0], G + 1), dtype=torch.float64, device=X.device)
         onehot[torch.arange(X.shape[0], device=X.device), torch.where(lab >= 0, lab, torch.full_like(lab, G))] = 1.0
@@ -244,7 +192,6 @@ def rank_genes_groups(X, labels, tie_correct=True, target_sum=None, device=None,
     if reference is not None:
         return _against_reference(X, labels, int(reference), tie_correct, target_sum, device)
     if is_torch_tensor(X) and not on_gpu(X):      # a tensor in host memory: as SciPy
-        from .device_input import classify
         X = classify(X).matrix
     if is_torch_tensor(labels) and not on_gpu(X):
         labels = labels.detach().cpu().numpy()
@@ -277,14 +224,11 @@ def rank_genes_groups(X, labels, tie_correct=True, target_sum=None, device=None,
 def _pair_rank_sums_host(ncells, ngenes, indptr, indices, data, labels, ngroups, pairs, device):
     """schpf_pair_rank_sums on the C-contiguous arrays of a CSC matrix, int32 labels and int32 pairs[P, 2] -> the four int64
     arrays n[G], nexpr[G, J], u2[P, J], ties[P, J]."""
-    lib = _lib.load()
-    _lib.require_gpu()
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    lib = library()
     P = pairs.shape[0]
     out = (np.zeros(ngroups, np.int64), np.zeros((ngroups, ngenes), np.int64), np.zeros((P, ngenes), np.int64),
            np.zeros((P, ngenes), np.int64))
-    _lib.check(lib.schpf_pair_rank_sums(int(device), ncells, ngenes, _p(indptr), _p(indices), _p(data), _p(labels), ngroups,
+    _lib.check(lib.schpf_pair_rank_sums(device_of(device), ncells, ngenes, _p(indptr), _p(indices), _p(data), _p(labels), ngroups,
                                         _p(pairs), P, *[_p(a) for a in out]))
     return out
 
@@ -324,14 +268,13 @@ def pair_rank_sums(X, labels, pairs="all", ngroups=None, device=None):
     stream and tensors come back (`pairs` too); anything else goes through SciPy and NumPy arrays come back."""
     if on_gpu(X):
         import torch
-        lib = _lib.load()
-        dev, N, J, G, lab, indptr, cells, values, stream, ptr = _gpu_inputs(X, labels, ngroups, device)
+        lib, dev, N, J, G, lab, indptr, cells, values, stream = _gpu_inputs(X, labels, ngroups, device)
         pairs = _pairs(pairs, G, J)
         P = pairs.shape[0]
         with torch.cuda.device(dev):
             d_pairs = torch.tensor(pairs, device=dev)
             out = [torch.zeros(s, dtype=torch.int64, device=dev) for s in ((G,), (G, J), (P, J), (P, J))]
-            _lib.check(lib.schpf_pair_rank_sums_device(dev.index, ctypes.c_void_p(stream), N, J, ptr(indptr), ptr(cells),
+            _lib.check(lib.schpf_pair_rank_sums_device(dev.index, stream, N, J, ptr(indptr), ptr(cells),
                                                        ptr(values), ptr(lab), G, ptr(d_pairs), P, *[ptr(t) for t in out]))
         return dict(zip(PAIR_NAMES + ("pairs",), out + [d_pairs]))
 
@@ -370,7 +313,6 @@ def rank_genes_pairs(X, labels, pairs="all", tie_correct=True, target_sum=None, 
     pairs: "all" or rows (a, b).  target_sum: scale every cell's counts to that total before ranking ("median": the median
     depth), in float32; nearly every entry is then its own value, the slowest case of the kernels."""
     if is_torch_tensor(X) and not on_gpu(X):      # a tensor in host memory: as SciPy
-        from .device_input import classify
         X = classify(X).matrix
     if is_torch_tensor(labels) and not on_gpu(X):
         labels = labels.detach().cpu().numpy()

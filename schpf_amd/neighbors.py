@@ -7,11 +7,12 @@ defined bit for bit -- squared distances by one subtraction and one fused multip
 smaller index.  Here are the argument plumbing, the two metrics and the assembly of the sparse graph.
 """
 import ctypes
-import os
 
 import numpy as np
 
 from . import _lib
+from ._call import array_ptr as _p, device_of, library, same_device, stats_ptr, stream_of, tensor_ptr as ptr
+from .device_input import from_torch, from_torch_on_gpu, gpu_graph, host_graph, host_graph_matrix
 
 __all__ = ["knn", "knn_graph", "knn_connectivities", "louvain", "modularity"]
 
@@ -20,17 +21,9 @@ GRAPH_METHODS = {"umap": _lib.GRAPH_UMAP, "jaccard": _lib.GRAPH_JACCARD}
 _DTYPES = {np.dtype(np.float32): _lib.F32, np.dtype(np.float64): _lib.F64}
 
 
-def _is_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _unit_rows(x, name):
     """Rows scaled to unit length (cosine: |a - b|^2 / 2 = 1 - cos for unit a, b); plumbing, in NumPy or torch."""
-    if _is_tensor(x):
+    if from_torch(x):
         import torch
         norm = torch.linalg.vector_norm(x, dim=1, keepdim=True)
         zero = bool((norm == 0).any())
@@ -53,13 +46,10 @@ def _check(metric, k):
 
 def _search_host(query, ref, k, self_first, device):
     """schpf_knn on two C-contiguous NumPy matrices of one dtype (float32 / float64) -> (idx, d2)."""
-    lib = _lib.load()
-    _lib.require_gpu()
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    lib = library()
     idx = np.empty((query.shape[0], k), np.int32)
     d2 = np.empty((query.shape[0], k), np.float64)
-    _lib.check(lib.schpf_knn(int(device), _DTYPES[query.dtype], query.shape[0], ref.shape[0], query.shape[1], _p(query),
+    _lib.check(lib.schpf_knn(device_of(device), _DTYPES[query.dtype], query.shape[0], ref.shape[0], query.shape[1], _p(query),
                              _p(ref), k, ctypes.c_int64(self_first), _p(idx), _p(d2)))
     return idx, d2
 
@@ -83,8 +73,8 @@ def knn(query, ref=None, k=15, metric="euclidean", exclude_self=None, device=Non
     self_graph = ref is None
     if exclude_self is None:
         exclude_self = self_graph
-    tensors = _is_tensor(query)
-    if not self_graph and _is_tensor(ref) != tensors:
+    tensors = from_torch(query)
+    if not self_graph and from_torch(ref) != tensors:
         raise ValueError("query and ref must both be NumPy arrays or both be torch tensors")
     if tensors and not query.is_cuda:      # a tensor in host memory: as NumPy, and back
         import torch
@@ -106,12 +96,10 @@ def knn(query, ref=None, k=15, metric="euclidean", exclude_self=None, device=Non
         return idx, (np.sqrt(d2) if metric == "euclidean" else d2 / 2)
 
     import torch
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     _TORCH = {torch.float32: _lib.F32, torch.float64: _lib.F64}
     dev = query.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError("query is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+    same_device(dev.index, device, "query")
     if not self_graph and ref.device != dev:
         raise ValueError("query is on %s, ref on %s" % (dev, ref.device))
     dtype = query.dtype if query.dtype in _TORCH else torch.float64
@@ -126,11 +114,8 @@ def knn(query, ref=None, k=15, metric="euclidean", exclude_self=None, device=Non
         idx = torch.empty((query.shape[0], k), dtype=torch.int32, device=dev)
         d2 = torch.empty((query.shape[0], k), dtype=torch.float64, device=dev)
         # on torch's current stream: ordered after whatever produced the scores and before whatever reads the result
-        stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
-        _lib.check(lib.schpf_knn_device(dev.index, ctypes.c_void_p(stream), _TORCH[dtype], query.shape[0], ref.shape[0],
-                                        query.shape[1], ptr(query), ptr(ref), k, ctypes.c_int64(self_first), ptr(idx),
-                                        ptr(d2)))
+        _lib.check(lib.schpf_knn_device(dev.index, stream_of(dev), _TORCH[dtype], query.shape[0], ref.shape[0], query.shape[1],
+                                        ptr(query), ptr(ref), k, ctypes.c_int64(self_first), ptr(idx), ptr(d2)))
         return idx, (torch.sqrt(d2) if metric == "euclidean" else d2 / 2)
 
 
@@ -139,7 +124,7 @@ def knn_graph(indices, distances, n_ref):
     (indices[q, j], distances[q, j]) -- the layout of scanpy's obsp["distances"] and of UMAP's precomputed input.
     A neighbour at distance 0 (a duplicated cell) is stored explicitly."""
     from scipy.sparse import csr_matrix
-    if _is_tensor(indices):
+    if from_torch(indices):
         indices, distances = indices.cpu().numpy(), distances.cpu().numpy()
     indices, distances = np.asarray(indices), np.asarray(distances)
     if indices.ndim != 2 or indices.shape != distances.shape:
@@ -154,16 +139,13 @@ def knn_graph(indices, distances, n_ref):
 def _graph_host(method, idx, dist, device):
     """schpf_knn_graph on C-contiguous NumPy lists (dist None: jaccard) -> (indptr, indices, data) of the CSR matrix, cut
     to nnz."""
-    lib = _lib.load()
-    _lib.require_gpu()
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    lib = library()
     n, k = idx.shape
     indptr = np.zeros(n + 1, np.int64)
     indices = np.empty(2 * n * k, np.int32)
     data = np.empty(2 * n * k, np.float64)
-    _lib.check(lib.schpf_knn_graph(int(device), method, n, k, _p(idx), _p(dist) if dist is not None else None, _p(indptr),
-                                   _p(indices), _p(data), None, None))
+    _lib.check(lib.schpf_knn_graph(device_of(device), method, n, k, _p(idx), _p(dist), _p(indptr), _p(indices), _p(data), None,
+                                   None))
     nnz = int(indptr[n])
     return indptr, indices[:nnz], data[:nnz]
 
@@ -187,14 +169,12 @@ def knn_connectivities(indices, distances=None, method="umap", device=None):
     if method == "umap" and distances is None:
         raise ValueError("method='umap' needs the distances of the neighbour lists")
     code = GRAPH_METHODS[method]
-    if _is_tensor(indices) and indices.is_cuda:
+    if from_torch_on_gpu(indices):
         import torch
-        lib = _lib.load()
-        _lib.require_gpu()
+        lib = library()
         dev = indices.device
-        if device is not None and int(device) != dev.index:
-            raise ValueError("indices are on GPU %d, device=%d was asked for" % (dev.index, int(device)))
-        if method == "umap" and (not _is_tensor(distances) or distances.device != dev):
+        same_device(dev.index, device, "indices", "are")
+        if method == "umap" and (not from_torch(distances) or distances.device != dev):
             raise ValueError("indices and distances must be on the same GPU")
         if indices.dim() != 2 or (method == "umap" and distances.shape != indices.shape):
             raise ValueError("indices and distances must be matrices of one shape")
@@ -205,10 +185,8 @@ def knn_connectivities(indices, distances=None, method="umap", device=None):
             indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             cols = torch.empty(2 * n * k, dtype=torch.int32, device=dev)
             data = torch.empty(2 * n * k, dtype=torch.float64, device=dev)
-            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
-            _lib.check(lib.schpf_knn_graph_device(dev.index, ctypes.c_void_p(stream), code, n, k, ptr(idx), ptr(dist),
-                                                  ptr(indptr), ptr(cols), ptr(data), None, None))
+            _lib.check(lib.schpf_knn_graph_device(dev.index, stream_of(dev), code, n, k, ptr(idx), ptr(dist), ptr(indptr),
+                                                  ptr(cols), ptr(data), None, None))
             nnz = int(indptr[n]) if n else 0
             # one index type for both, as torch's kernels expect: int32 where it holds nnz
             indptr, cols = (indptr.to(torch.int32), cols[:nnz]) if nnz < 2 ** 31 else (indptr, cols[:nnz].to(torch.int64))
@@ -218,9 +196,9 @@ def knn_connectivities(indices, distances=None, method="umap", device=None):
                 return torch.sparse_csr_tensor(indptr, cols, data[:nnz], size=(n, n))
 
     from scipy.sparse import csr_matrix
-    if _is_tensor(indices):
+    if from_torch(indices):
         indices = indices.cpu().numpy()
-    if distances is not None and _is_tensor(distances):
+    if distances is not None and from_torch(distances):
         distances = distances.cpu().numpy()
     idx = np.ascontiguousarray(indices, dtype=np.int32)
     dist = np.ascontiguousarray(distances, dtype=np.float64) if method == "umap" else None
@@ -238,15 +216,12 @@ def knn_connectivities(indices, distances=None, method="umap", device=None):
 
 def _louvain_host(indptr, indices, data, gamma, device):
     """schpf_louvain on the three C-contiguous arrays of a CSR matrix (int64, int32, float64) -> (labels, stats)."""
-    lib = _lib.load()
-    _lib.require_gpu()
-    if device is None:
-        device = int(os.environ.get("SCHPF_DEVICE", "0"))
+    lib = library()
     n = len(indptr) - 1
     labels = np.empty(n, np.int32)
     stats = np.zeros(4, np.int64)
-    _lib.check(lib.schpf_louvain(int(device), n, _p(indptr), _p(indices), _p(data), float(gamma), _p(labels),
-                                 stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+    _lib.check(lib.schpf_louvain(device_of(device), n, _p(indptr), _p(indices), _p(data), float(gamma), _p(labels),
+                                 stats_ptr(stats)))
     return labels, stats
 
 
@@ -263,7 +238,7 @@ def _connected(graph, labels, stats, device, return_stats):
     pieces, found = connected_components(graph, within=labels, device=device, return_stats=True)
     if not return_stats:
         return pieces
-    if _is_tensor(pieces):
+    if from_torch(pieces):
         import torch
         parent = torch.empty(found["components"], dtype=labels.dtype, device=pieces.device)
         parent[pieces.long()] = labels.to(pieces.device)   # every member of a piece writes the same community
@@ -293,47 +268,27 @@ def louvain(graph, resolution=1.0, device=None, return_stats=False, connected=Fa
     of first member.  return_stats then also holds "clusters", their number, and "parent", the Louvain label each came from."""
     gamma = _resolution(resolution)
     names = ("communities", "levels", "rounds", "total_weight")
-    if _is_tensor(graph) and graph.is_cuda:
+    if from_torch_on_gpu(graph):
         import torch
-        if graph.layout != torch.sparse_csr:
-            raise ValueError("a graph on the GPU must be a torch.sparse_csr_tensor")
-        if graph.dim() != 2 or graph.shape[0] != graph.shape[1]:
-            raise ValueError("graph must be a square matrix")
-        lib = _lib.load()
-        _lib.require_gpu()
-        dev = graph.device
-        if device is not None and int(device) != dev.index:
-            raise ValueError("graph is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
-        n = graph.shape[0]
+        dev, n, indptr, cols, data = gpu_graph(graph, device, values=True)
+        lib = library()
         with torch.cuda.device(dev):
-            indptr = graph.crow_indices().detach().to(torch.int64).contiguous()
-            cols = graph.col_indices().detach().to(torch.int32).contiguous()
-            data = graph.values().detach().to(torch.float64).contiguous()
             labels = torch.empty(n, dtype=torch.int32, device=dev)
             stats = np.zeros(4, np.int64)
-            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
-            _lib.check(lib.schpf_louvain_device(dev.index, ctypes.c_void_p(stream), n, ptr(indptr), ptr(cols), ptr(data), gamma,
-                                                ptr(labels), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            _lib.check(lib.schpf_louvain_device(dev.index, stream_of(dev), n, ptr(indptr), ptr(cols), ptr(data), gamma,
+                                                ptr(labels), stats_ptr(stats)))
         if connected:
             return _connected(graph, labels, dict(zip(names, stats.tolist())), device, return_stats)
         return (labels, dict(zip(names, stats.tolist()))) if return_stats else labels
 
-    from scipy.sparse import csr_matrix, issparse
-    back_to_torch = _is_tensor(graph)
+    back_to_torch = from_torch(graph)
     if back_to_torch:
         import torch
-        graph = graph.to_sparse_csr()
-        graph = csr_matrix((graph.values().numpy(), graph.col_indices().numpy(), graph.crow_indices().numpy()),
-                           shape=tuple(graph.shape))
-    G = graph.tocsr() if issparse(graph) else csr_matrix(np.asarray(graph))
-    if G.shape[0] != G.shape[1]:
-        raise ValueError("graph must be a square matrix")
+    G = host_graph_matrix(graph)
     if not G.has_canonical_format:          # columns ascending, no entry twice: on a copy
         G = G.copy()
         G.sum_duplicates()
-    labels, stats = _louvain_host(np.ascontiguousarray(G.indptr, dtype=np.int64), np.ascontiguousarray(G.indices, dtype=np.int32),
-                                  np.ascontiguousarray(G.data, dtype=np.float64), gamma, device)
+    labels, stats = _louvain_host(*(host_graph(G)[1:] + (gamma, device)))
     if connected:
         pieces = _connected(G, labels, dict(zip(names, np.asarray(stats).tolist())), device, return_stats)
         if back_to_torch:
@@ -350,9 +305,9 @@ def modularity(graph, labels, resolution=1.0):
     entries with both ends in c, tot_c the sum of the rows of c.  0 for a graph without weight."""
     from scipy.sparse import coo_matrix, issparse
     gamma = _resolution(resolution)
-    if _is_tensor(graph):
+    if from_torch(graph):
         graph = graph.cpu().to_dense().numpy()
-    if _is_tensor(labels):
+    if from_torch(labels):
         labels = labels.cpu().numpy()
     A = graph.tocoo() if issparse(graph) else coo_matrix(np.asarray(graph))
     labels = np.asarray(labels).astype(np.int64).ravel()

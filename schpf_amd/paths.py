@@ -7,13 +7,11 @@ the work was scheduled -- SciPy's `dijkstra` gives the same bits.  `pseudotime` 
 the landmarks with de Silva and Tenenbaum's triangulation of every other cell: an L x L eigendecomposition in NumPy, whose
 floats are outside the bit contract.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
-from .neighbors import _is_tensor, _p
-from .topology import _device, _device_csr, _host_csr, _i64p, _on_gpu, _ptr
+from ._call import array_ptr as _p, device_of, library, stats_ptr, stream_of, tensor_ptr as ptr
+from .device_input import from_torch, from_torch_on_gpu, gpu_graph, host_graph
 
 __all__ = ["geodesic_distances", "pseudotime", "farthest_landmarks", "landmark_isomap"]
 
@@ -22,7 +20,7 @@ GEODESIC_STATS = ("finite", "rounds", "lowering_writes")
 
 
 def _as_numpy(a):
-    return a.cpu().numpy() if _is_tensor(a) else np.asarray(a)
+    return a.cpu().numpy() if from_torch(a) else np.asarray(a)
 
 
 def _one_set(root, n):
@@ -71,30 +69,28 @@ def geodesic_distances(graph, roots, directed=False, device=None, return_stats=F
 
     Every distance is a sum of IEEE additions along one path and the same bits on every run; return_stats=True: also
     {"finite", "rounds", "lowering_writes"}, of which the last two depend on how the GPU scheduled the work."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     stats = np.zeros(3, np.int64)
-    if _on_gpu(graph):
+    if from_torch_on_gpu(graph):
         import torch
-        dev, n, indptr, cols, data = _device_csr(graph, device, values=True)
+        dev, n, indptr, cols, data = gpu_graph(graph, device, values=True)
         set_ptr, members = _root_sets(roots, n)
         nsets = len(set_ptr) - 1
         with torch.cuda.device(dev):
             d_set_ptr = torch.from_numpy(set_ptr).to(dev)
             d_members = torch.from_numpy(members).to(dev)
             dist = torch.empty((nsets, n), dtype=torch.float64, device=dev)
-            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-            _lib.check(lib.schpf_geodesic_device(dev.index, ctypes.c_void_p(stream), n, _ptr(indptr), _ptr(cols), _ptr(data),
-                                                 int(bool(directed)), nsets, _ptr(d_set_ptr), _ptr(d_members), _ptr(dist),
-                                                 _i64p(stats)))
+            _lib.check(lib.schpf_geodesic_device(dev.index, stream_of(dev), n, ptr(indptr), ptr(cols), ptr(data),
+                                                 int(bool(directed)), nsets, ptr(d_set_ptr), ptr(d_members), ptr(dist),
+                                                 stats_ptr(stats)))
     else:
-        back_to_torch = _is_tensor(graph)
-        n, indptr, indices, data = _host_csr(graph)
+        back_to_torch = from_torch(graph)
+        n, indptr, indices, data = host_graph(graph)
         set_ptr, members = _root_sets(roots, n)
         nsets = len(set_ptr) - 1
         dist = np.empty((nsets, n), np.float64)
-        _lib.check(lib.schpf_geodesic(_device(device), n, _p(indptr), _p(indices), _p(data), int(bool(directed)), nsets,
-                                      _p(set_ptr), _p(members), _p(dist), _i64p(stats)))
+        _lib.check(lib.schpf_geodesic(device_of(device), n, _p(indptr), _p(indices), _p(data), int(bool(directed)), nsets,
+                                      _p(set_ptr), _p(members), _p(dist), stats_ptr(stats)))
         if back_to_torch:
             import torch
             dist = torch.from_numpy(dist)
@@ -111,7 +107,7 @@ def pseudotime(graph, root, directed=False, device=None):
     where the largest finite distance is 0, every reachable row is 0.  The scaling is plain NumPy or torch on the exact
     distances of `geodesic_distances`."""
     dist = geodesic_distances(graph, [_one_set(root, _n_rows(graph))], directed=directed, device=device)[0]
-    if _is_tensor(dist):
+    if from_torch(dist):
         import torch
         finite = torch.isfinite(dist)
         top = dist[finite].max() if bool(finite.any()) else dist.new_zeros(())
@@ -138,11 +134,11 @@ def farthest_landmarks(graph, n_landmarks, first=0, directed=False, device=None)
     for step in range(L):
         d = geodesic_distances(graph, landmarks[-1], directed=directed, device=device)[0]
         rows.append(d)
-        nearest = d if nearest is None else (nearest.minimum(d) if _is_tensor(d) else np.minimum(nearest, d))
+        nearest = d if nearest is None else (nearest.minimum(d) if from_torch(d) else np.minimum(nearest, d))
         if step + 1 < L:
             at_top = nearest == nearest.max()         # inf == inf: the rows no landmark reaches come first
-            landmarks.append(int(at_top.nonzero()[0][0]) if _is_tensor(d) else int(np.flatnonzero(at_top)[0]))
-    if _is_tensor(rows[0]):
+            landmarks.append(int(at_top.nonzero()[0][0]) if from_torch(d) else int(np.flatnonzero(at_top)[0]))
+    if from_torch(rows[0]):
         import torch
         return torch.tensor(landmarks, dtype=torch.int32, device=rows[0].device), torch.stack(rows)
     return np.array(landmarks, np.int32), np.stack(rows)

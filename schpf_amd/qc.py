@@ -14,22 +14,17 @@ Removing called doublets and refitting:
     model = scHPF(K).fit(X_clean)
 """
 import ctypes
-import os
 
 import numpy as np
 
 from . import _lib
-from .device_input import classify, is_torch_tensor, on_gpu
-from .doublets import _gpu_csr, _p
-from .thinning import _VAL_KINDS
+from ._call import array_ptr as _p, device_of, library, stream_of, tensor_ptr as ptr
+from .device_input import (NUMPY_VALUE_KINDS, gpu_csr, host_csr, host_csr_arrays, is_torch_tensor, on_gpu,
+                           to_numpy as _host)
 
 __all__ = ["qc_metrics", "submatrix", "filter_counts"]
 
 MAX_SETS = 32      # one bit of a gene's flag word per gene set (qc.h QC_MAX_SETS)
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if is_torch_tensor(a) else np.asarray(a)
 
 
 def _mask(sel, n, what, ascending=False):
@@ -76,66 +71,30 @@ def _rows(cells, ncells):
     return np.ascontiguousarray(cells, dtype=np.int32)
 
 
-def _host_csr(X, canonical):
-    """Anything that is not a GPU tensor as a SciPy CSR that is the caller's no longer; canonical: duplicates summed."""
-    from scipy.sparse import csr_matrix, issparse
-    if is_torch_tensor(X):
-        X = classify(X).matrix
-    C = X.tocsr() if issparse(X) else csr_matrix(X)
-    if canonical:
-        if C is X:
-            C = C.copy()
-        C.sum_duplicates()                               # also sorts the columns of every row
-    return C
-
-
-def _host_arrays(C):
-    data = np.ascontiguousarray(C.data)
-    vals = data if data.dtype in _VAL_KINDS else data.astype(np.float64)
-    return np.ascontiguousarray(C.indptr, dtype=np.int64), np.ascontiguousarray(C.indices, dtype=np.int32), vals
-
-
-def _device_of(device):
-    return int(os.environ.get("SCHPF_DEVICE", "0")) if device is None else int(device)
-
-
 def _axis_stats_host(ncells, ngenes, indptr, indices, vals, n_sets, flags, device):
     """schpf_axis_stats on NumPy arrays: (cell_n, cell_total, cell_set_total[n_sets, ncells], gene_n, gene_total, gene_sumsq)."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     out = [np.zeros(ncells, np.int64), np.zeros(ncells, np.int64), np.zeros((n_sets, ncells), np.int64),
            np.zeros(ngenes, np.int64), np.zeros(ngenes, np.int64), np.zeros(ngenes, np.int64)]
-    _lib.check(lib.schpf_axis_stats(device, ncells, ngenes, len(vals), _p(indptr), _p(indices), _p(vals), _VAL_KINDS[vals.dtype],
-                                    n_sets, _p(flags), *[_p(a) for a in out]))
+    _lib.check(lib.schpf_axis_stats(device, ncells, ngenes, len(vals), _p(indptr), _p(indices), _p(vals),
+                                    NUMPY_VALUE_KINDS[vals.dtype], n_sets, _p(flags), *[_p(a) for a in out]))
     return out
 
 
 def _submatrix_host(ncells, ngenes, indptr, indices, vals, rows, keep, device):
     """schpf_submatrix on NumPy arrays, the sizing call and the filling call: (out_ngenes, out_indptr, out_indices, out_values)."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     n_rows = ncells if rows is None else len(rows)
     if rows is not None and n_rows == 0:                  # an empty list is still a list: NULL would ask for all rows
         rows = np.zeros(1, np.int32)
     kept, out_indptr = ctypes.c_int64(0), np.zeros(n_rows + 1, np.int64)
-    args = (device, ncells, ngenes, len(vals), _p(indptr), _p(indices), _p(vals), _VAL_KINDS[vals.dtype], n_rows,
-            None if rows is None else rows.ctypes.data_as(ctypes.c_void_p),
-            None if keep is None else keep.ctypes.data_as(ctypes.c_void_p), ctypes.byref(kept),
-            out_indptr.ctypes.data_as(ctypes.c_void_p))
+    args = (device, ncells, ngenes, len(vals), _p(indptr), _p(indices), _p(vals), NUMPY_VALUE_KINDS[vals.dtype], n_rows,
+            _p(rows), _p(keep), ctypes.byref(kept), _p(out_indptr))
     _lib.check(lib.schpf_submatrix(*(args + (None, None, 0))))                               # the sizes
     total = int(out_indptr[-1])
     out_indices, out_values = np.empty(max(total, 1), np.int32), np.empty(max(total, 1), vals.dtype)
     _lib.check(lib.schpf_submatrix(*(args + (_p(out_indices), _p(out_values), total))))
     return int(kept.value), out_indptr, out_indices[:total], out_values[:total]
-
-
-def _gpu_input(X, device):
-    import torch
-    with torch.cuda.device(X.device):
-        inp = _gpu_csr(X)
-    if device is not None and int(device) != inp.device:
-        raise ValueError("X is on GPU %d, device=%d was asked for" % (inp.device, int(device)))
-    return inp, torch.device("cuda", inp.device)
 
 
 def _moments(out, ncells):
@@ -162,14 +121,12 @@ def qc_metrics(X, gene_sets=None, device=None):
     naming the smallest offending row or entry."""
     if on_gpu(X):
         import torch
-        lib = _lib.load()
-        _lib.require_gpu()
-        inp, dev = _gpu_input(X, device)
+        lib = library()
+        inp, dev = gpu_csr(X, device)
         N, J = inp.shape
         names, flags = _flags(gene_sets, J)
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT)
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+            stream = stream_of(dev)
             d_flags = torch.from_numpy(flags.view(np.int32)).to(dev)
             cell = torch.zeros((2 + len(names), N), dtype=torch.int64, device=dev)
             gene = torch.zeros((3, J), dtype=torch.int64, device=dev)
@@ -179,10 +136,10 @@ def qc_metrics(X, gene_sets=None, device=None):
                                                    ptr(gene[2])))
         found = [cell[0], cell[1], cell[2:], gene[0], gene[1], gene[2]]
     else:
-        C = _host_csr(X, canonical=True)
+        C = host_csr(X, canonical=True)
         N, J = C.shape
         names, flags = _flags(gene_sets, J)
-        found = _axis_stats_host(N, J, *(_host_arrays(C) + (len(names), flags, _device_of(device))))
+        found = _axis_stats_host(N, J, *(host_csr_arrays(C) + (len(names), flags, device_of(device))))
     out = {"cell_n_genes": found[0], "cell_total": found[1],
            "cell_set_total": {name: found[2][s] for s, name in enumerate(names)},
            "gene_n_cells": found[3], "gene_total": found[4], "gene_sumsq": found[5]}
@@ -200,9 +157,8 @@ def submatrix(X, cells=None, genes=None, device=None):
     a row the entries keep their stored order, and the values are copied byte for byte in their own dtype."""
     if on_gpu(X):
         import torch
-        lib = _lib.load()
-        _lib.require_gpu()
-        inp, dev = _gpu_input(X, device)
+        lib = library()
+        inp, dev = gpu_csr(X, device)
         N, J = inp.shape
         if is_torch_tensor(cells) and cells.device == dev and cells.dtype in (torch.bool, torch.int32) and cells.dim() == 1:
             if cells.dtype == torch.bool and cells.shape[0] != N:
@@ -214,8 +170,7 @@ def submatrix(X, cells=None, genes=None, device=None):
         keep = None if genes is None else torch.from_numpy(_mask(genes, J, "gene", ascending=True).view(np.uint8)).to(dev)
         n_rows = N if rows is None else int(rows.shape[0])
         with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT)
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+            stream = stream_of(dev)
             if rows is not None and n_rows == 0:          # an empty list is still a list: NULL would ask for all rows
                 rows = torch.zeros(1, dtype=torch.int32, device=dev)
             kept, out_indptr = ctypes.c_int64(0), torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
@@ -229,12 +184,12 @@ def submatrix(X, cells=None, genes=None, device=None):
             return torch.sparse_csr_tensor(out_indptr, out_indices[:total].to(torch.int64), out_values[:total],
                                            size=(n_rows, int(kept.value)))
     from scipy.sparse import csr_matrix
-    C = _host_csr(X, canonical=False)
+    C = host_csr(X, canonical=False)
     N, J = C.shape
     rows = _rows(cells, N)
     keep = None if genes is None or J == 0 else np.ascontiguousarray(_mask(genes, J, "gene", ascending=True)).view(np.uint8)
-    indptr, indices, vals = _host_arrays(C)
-    kept, out_indptr, out_indices, out_values = _submatrix_host(N, J, indptr, indices, vals, rows, keep, _device_of(device))
+    indptr, indices, vals = host_csr_arrays(C)
+    kept, out_indptr, out_indices, out_values = _submatrix_host(N, J, indptr, indices, vals, rows, keep, device_of(device))
     return csr_matrix((out_values.astype(C.data.dtype, copy=False), out_indices, out_indptr), shape=(len(out_indptr) - 1, kept))
 
 

@@ -7,21 +7,14 @@ has not seen and without giving up whole cells.  The split runs in the library (
 the argument plumbing and the assembly of the two matrices.
 """
 import ctypes
-import os
 
 import numpy as np
 
 from . import _lib
-from .device_input import classify
+from ._call import array_ptr as _p, device_of, library, same_device, stream_of, tensor_ptr as ptr
+from .device_input import NUMPY_VALUE_KINDS, classify
 
 __all__ = ["thin_counts"]
-
-_VAL_KINDS = {np.dtype(np.int32): _lib.VAL_I32, np.dtype(np.int64): _lib.VAL_I64,
-              np.dtype(np.float32): _lib.VAL_F32, np.dtype(np.float64): _lib.VAL_F64}
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _seed(seed):
@@ -51,30 +44,26 @@ def thin_counts(X, frac, seed=0, device=None):
     offending entry).  `device`: HIP device ordinal, default the tensor's GPU, else $SCHPF_DEVICE or 0.  A model fitted
     to X_train has seen (1 - frac) of the counts: the scale of its theta is reduced by that factor.
     """
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     inp = classify(X)
     frac, seed = float(frac), _seed(seed)
     stats = (ctypes.c_int64 * 4)()
     if inp.kind == "host":
         from scipy.sparse import coo_matrix
         M = inp.matrix
-        if device is None:
-            device = int(os.environ.get("SCHPF_DEVICE", "0"))
         data = np.ascontiguousarray(M.data)
-        vals = data if data.dtype in _VAL_KINDS else data.astype(np.float64)
+        vals = data if data.dtype in NUMPY_VALUE_KINDS else data.astype(np.float64)
         row = np.ascontiguousarray(M.row, dtype=np.int32)
         col = np.ascontiguousarray(M.col, dtype=np.int32)
         train, test = np.empty(inp.nnz, np.int32), np.empty(inp.nnz, np.int32)
-        _lib.check(lib.schpf_thin_counts(int(device), inp.nnz, _p(row), _p(col), _p(vals), _VAL_KINDS[vals.dtype], frac,
-                                         seed, _p(train), _p(test), stats))
+        _lib.check(lib.schpf_thin_counts(device_of(device), inp.nnz, _p(row), _p(col), _p(vals),
+                                         NUMPY_VALUE_KINDS[vals.dtype], frac, seed, _p(train), _p(test), stats))
         keep = train > 0
         return (coo_matrix((train[keep].astype(data.dtype), (row[keep], col[keep])), shape=inp.shape),
                 coo_matrix((test.astype(data.dtype), (row, col)), shape=inp.shape))
 
     import torch
-    if device is not None and int(device) != inp.device:
-        raise ValueError("X is on GPU %d, device=%d was asked for" % (inp.device, int(device)))
+    same_device(inp.device, device, "X")
     dev = torch.device("cuda", inp.device)
     col = inp.minor
     if inp.kind == "coo":
@@ -87,9 +76,7 @@ def thin_counts(X, frac, seed=0, device=None):
         train = torch.empty(inp.nnz, dtype=torch.int32, device=dev)
         test = torch.empty(inp.nnz, dtype=torch.int32, device=dev)
         # on torch's current stream: ordered after whatever produced X and before whatever reads the result
-        stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
-        _lib.check(lib.schpf_thin_counts_device(inp.device, ctypes.c_void_p(stream), inp.nnz, ptr(row), ptr(col),
+        _lib.check(lib.schpf_thin_counts_device(inp.device, stream_of(dev), inp.nnz, ptr(row), ptr(col),
                                                 inp.minor_kind, ptr(inp.values), inp.value_kind, frac, seed, ptr(train),
                                                 ptr(test), stats))
         index = torch.stack([row, col]).to(torch.int64)

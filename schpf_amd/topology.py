@@ -7,75 +7,28 @@ connectivities of a PAGA plot and `absorb_small` merges splinters into the clust
 computes here is an integer, equal bit for bit however the work was scheduled; the floats of `paga` are plain NumPy.
 """
 import ctypes
-import os
 
 import numpy as np
 
 from . import _lib
-from .neighbors import _is_tensor, _p
+from ._call import array_ptr as _p, device_of, library, stats_ptr, stream_of, tensor_ptr as ptr
+from .device_input import from_torch, from_torch_on_gpu, gpu_graph, host_graph, int32_labels
 
 __all__ = ["connected_components", "cluster_graph", "absorb_small", "paga"]
 
 COMPONENT_STATS = ("components", "largest", "singletons", "edges", "hook_rounds", "shortcut_passes")
 
 
-def _device(device):
-    return int(os.environ.get("SCHPF_DEVICE", "0")) if device is None else int(device)
-
-
-def _i64p(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-
-
-def _on_gpu(graph):
-    return _is_tensor(graph) and graph.is_cuda
-
-
-def _device_csr(graph, device, values):
-    """(torch device, n, indptr int64, cols int32, data float64 or None) of a torch.sparse_csr_tensor on a GPU."""
-    import torch
-    if graph.layout != torch.sparse_csr:
-        raise ValueError("a graph on the GPU must be a torch.sparse_csr_tensor")
-    if graph.dim() != 2 or graph.shape[0] != graph.shape[1]:
-        raise ValueError("graph must be a square matrix")
-    dev = graph.device
-    if device is not None and int(device) != dev.index:
-        raise ValueError("graph is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
-    with torch.cuda.device(dev):
-        indptr = graph.crow_indices().detach().to(torch.int64).contiguous()
-        cols = graph.col_indices().detach().to(torch.int32).contiguous()
-        data = graph.values().detach().to(torch.float64).contiguous() if values else None
-    return dev, graph.shape[0], indptr, cols, data
-
-
-def _host_csr(graph):
-    """(n, indptr int64, indices int32, data float64) of a SciPy matrix, a dense array or a torch tensor on the host.  The
-    entries stay as they are stored: columns need not ascend and repeats are harmless."""
-    from scipy.sparse import csr_matrix, issparse
-    if _is_tensor(graph):
-        graph = graph.to_sparse_csr()
-        graph = csr_matrix((graph.values().numpy(), graph.col_indices().numpy(), graph.crow_indices().numpy()),
-                           shape=tuple(graph.shape))
-    G = graph.tocsr() if issparse(graph) else csr_matrix(np.asarray(graph))
-    if G.shape[0] != G.shape[1]:
-        raise ValueError("graph must be a square matrix")
-    return (G.shape[0], np.ascontiguousarray(G.indptr, dtype=np.int64), np.ascontiguousarray(G.indices, dtype=np.int32),
-            np.ascontiguousarray(G.data, dtype=np.float64))
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
-
-
-def _int32_labels(labels, n, name):
-    if _is_tensor(labels):
+def _row_labels(labels, n, name):
+    """One integer per row of the graph, from NumPy or a tensor, as int32 in host memory."""
+    if from_torch(labels):
         labels = labels.cpu().numpy()
     labels = np.asarray(labels)
     if labels.shape != (n,):
         raise ValueError("%s must hold one integer per row of the graph" % name)
     if not np.issubdtype(labels.dtype, np.integer):
         raise ValueError("%s must be integers" % name)
-    return np.ascontiguousarray(labels, dtype=np.int32)
+    return int32_labels(labels)
 
 
 def connected_components(graph, within=None, device=None, return_stats=False):
@@ -90,30 +43,27 @@ def connected_components(graph, within=None, device=None, return_stats=False):
     there, runs on torch's current stream and gives a tensor.  return_stats=True: also {"components", "largest",
     "singletons", "edges", "hook_rounds", "shortcut_passes"}; the last two depend on how the GPU scheduled the work, the
     labels and the other four do not."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     stats = np.zeros(6, np.int64)
-    if _on_gpu(graph):
+    if from_torch_on_gpu(graph):
         import torch
-        dev, n, indptr, cols, _ = _device_csr(graph, device, values=False)
+        dev, n, indptr, cols, _ = gpu_graph(graph, device, values=False)
         with torch.cuda.device(dev):
             w = None
             if within is not None:
-                w = torch.as_tensor(within if _is_tensor(within) else _int32_labels(within, n, "within"))
+                w = torch.as_tensor(within if from_torch(within) else _row_labels(within, n, "within"))
                 if tuple(w.shape) != (n,) or w.is_floating_point():
                     raise ValueError("within must hold one integer per row of the graph")
                 w = w.to(device=dev, dtype=torch.int32).contiguous()
             comp = torch.empty(n, dtype=torch.int32, device=dev)
-            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-            _lib.check(lib.schpf_components_device(dev.index, ctypes.c_void_p(stream), n, _ptr(indptr), _ptr(cols), _ptr(w),
-                                                   _ptr(comp), _i64p(stats)))
+            _lib.check(lib.schpf_components_device(dev.index, stream_of(dev), n, ptr(indptr), ptr(cols), ptr(w), ptr(comp),
+                                                   stats_ptr(stats)))
     else:
-        back_to_torch = _is_tensor(graph)
-        n, indptr, indices, _ = _host_csr(graph)
-        w = None if within is None else _int32_labels(within, n, "within")
+        back_to_torch = from_torch(graph)
+        n, indptr, indices, _ = host_graph(graph)
+        w = None if within is None else _row_labels(within, n, "within")
         comp = np.empty(n, np.int32)
-        _lib.check(lib.schpf_components(_device(device), n, _p(indptr), _p(indices), None if w is None else _p(w), _p(comp),
-                                        _i64p(stats)))
+        _lib.check(lib.schpf_components(device_of(device), n, _p(indptr), _p(indices), _p(w), _p(comp), stats_ptr(stats)))
         if back_to_torch:
             import torch
             comp = torch.from_numpy(comp)
@@ -128,14 +78,13 @@ def cluster_graph(graph, labels, ngroups=None, weights=True, device=None):
     the largest stored value.  labels: one integer per row in [-1, G), -1 for a row in no cluster; ngroups=None: G =
     max(labels) + 1.  The graph may be directed: count is then not symmetric.  A torch.sparse_csr_tensor on a GPU gives
     tensors on that GPU."""
-    lib = _lib.load()
-    _lib.require_gpu()
+    lib = library()
     wmax = ctypes.c_double(0.0)
-    if _on_gpu(graph):
+    if from_torch_on_gpu(graph):
         import torch
-        dev, n, indptr, cols, data = _device_csr(graph, device, values=bool(weights))
+        dev, n, indptr, cols, data = gpu_graph(graph, device, values=bool(weights))
         with torch.cuda.device(dev):
-            lab = torch.as_tensor(labels if _is_tensor(labels) else _int32_labels(labels, n, "labels"))
+            lab = torch.as_tensor(labels if from_torch(labels) else _row_labels(labels, n, "labels"))
             if tuple(lab.shape) != (n,) or lab.is_floating_point():
                 raise ValueError("labels must hold one integer per row of the graph")
             lab = lab.to(device=dev, dtype=torch.int32).contiguous()
@@ -143,18 +92,17 @@ def cluster_graph(graph, labels, ngroups=None, weights=True, device=None):
             cells = torch.empty(G, dtype=torch.int64, device=dev)
             count = torch.empty((G, G), dtype=torch.int64, device=dev)
             weight = torch.empty((G, G), dtype=torch.int64, device=dev) if weights else None
-            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-            _lib.check(lib.schpf_cluster_graph_device(dev.index, ctypes.c_void_p(stream), n, _ptr(indptr), _ptr(cols), _ptr(data),
-                                                      _ptr(lab), G, _ptr(cells), _ptr(count), _ptr(weight), ctypes.byref(wmax)))
+            _lib.check(lib.schpf_cluster_graph_device(dev.index, stream_of(dev), n, ptr(indptr), ptr(cols), ptr(data), ptr(lab), G,
+                                                      ptr(cells), ptr(count), ptr(weight), ctypes.byref(wmax)))
     else:
-        n, indptr, indices, data = _host_csr(graph)
-        lab = _int32_labels(labels, n, "labels")
+        n, indptr, indices, data = host_graph(graph)
+        lab = _row_labels(labels, n, "labels")
         G = _ngroups(ngroups, int(lab.max()) if n else -1)
         cells = np.empty(G, np.int64)
         count = np.empty((G, G), np.int64)
         weight = np.empty((G, G), np.int64) if weights else None
-        _lib.check(lib.schpf_cluster_graph(_device(device), n, _p(indptr), _p(indices), _p(data) if weights else None, _p(lab), G,
-                                           _p(cells), _p(count), None if weight is None else _p(weight), ctypes.byref(wmax)))
+        _lib.check(lib.schpf_cluster_graph(device_of(device), n, _p(indptr), _p(indices), _p(data) if weights else None, _p(lab),
+                                           G, _p(cells), _p(count), _p(weight), ctypes.byref(wmax)))
     return {"n_cells": cells, "count": count, "weight": weight, "wmax": wmax.value}
 
 
@@ -218,7 +166,7 @@ def paga(graph, labels, ngroups=None, device=None):
     elsewhere both are 0.  The integers are exact; the two float tables are NumPy's."""
     found = cluster_graph(graph, labels, ngroups=ngroups, weights=False, device=device)
     count, ns = found["count"], found["n_cells"]
-    if _is_tensor(count):
+    if from_torch(count):
         count, ns = count.cpu().numpy(), ns.cpu().numpy()
     connectivities, expected = paga_tables(count, ns)
     return {"connectivities": connectivities, "expected": expected, "count": count, "n_cells": ns}

@@ -10,22 +10,17 @@ matrix over; `highly_variable_genes` ranks the genes and returns the mask that `
     found = highly_variable_genes(X, n_top_genes=2000)
     model = scHPF(K).fit(submatrix(X, genes=found["highly_variable"]))
 """
-import ctypes
 import math
-import os
 
 import numpy as np
 
 from . import _lib
-from .device_input import is_torch_tensor, on_gpu
+from ._call import array_ptr as _p, device_of, library, same_device, stream_of, tensor_ptr as ptr
+from .device_input import gpu_csc, host_csc, on_gpu, to_numpy as host
 
 __all__ = ["residual_variance", "highly_variable_genes"]
 
 NAMES = ("residual_sum", "residual_sumsq", "residual_var", "gene_total", "cell_total", "n_distinct_totals")
-
-
-def _p(a):
-    return None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _parameters(theta, clip, ncells):
@@ -37,21 +32,6 @@ def _parameters(theta, clip, ncells):
     if ncells and not clip > 0:
         raise ValueError("clip must be in (0, inf], got %r" % (clip,))
     return (0.0 if math.isinf(theta) else 1.0 / theta), (clip if clip > 0 else 1.0)   # no cells: any clip gives zeros
-
-
-def _host_csc(X):
-    """Anything that is not a GPU tensor -> (N, J, the C-contiguous arrays of the canonical CSC form: int64, int32, float32)."""
-    from scipy.sparse import csc_matrix, issparse
-    if is_torch_tensor(X):                # a tensor in host memory: as SciPy
-        from .device_input import classify
-        X = classify(X).matrix
-    C = csc_matrix(X) if not issparse(X) else X.tocsc()
-    if C is X:
-        C = C.copy()
-    C.sum_duplicates()                    # also sorts the cells of every gene
-    N, J = C.shape
-    return (N, J, np.ascontiguousarray(C.indptr, dtype=np.int64), np.ascontiguousarray(C.indices, dtype=np.int32),
-            np.ascontiguousarray(C.data, dtype=np.float32))
 
 
 def residual_variance(X, theta=100.0, clip=None, device=None):
@@ -71,36 +51,29 @@ def residual_variance(X, theta=100.0, clip=None, device=None):
     offending gene."""
     if on_gpu(X):
         import torch
-        from .markers import _gpu_csc
-        lib = _lib.load()
-        _lib.require_gpu()
+        lib = library()
         dev = X.device
-        if device is not None and int(device) != dev.index:
-            raise ValueError("X is on GPU %d, device=%d was asked for" % (dev.index, int(device)))
+        same_device(dev.index, device, "X")
         N, J = int(X.shape[0]), int(X.shape[1])
         inv_theta, clip = _parameters(theta, clip, N)
         with torch.cuda.device(dev):
-            indptr, cells, values = _gpu_csc(X)
-            stream = int(torch.cuda.current_stream(dev).cuda_stream) or _lib.STREAM_DEFAULT
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
+            indptr, cells, values = gpu_csc(X)
             s1, s2 = torch.zeros(J, dtype=torch.float64, device=dev), torch.zeros(J, dtype=torch.float64, device=dev)
             cell_total = torch.zeros(N, dtype=torch.int64, device=dev)
             gene_total = torch.zeros(J, dtype=torch.int64, device=dev)
-            _lib.check(lib.schpf_residual_var_device(dev.index, ctypes.c_void_p(stream), N, J, int(values.shape[0]), ptr(indptr),
+            _lib.check(lib.schpf_residual_var_device(dev.index, stream_of(dev), N, J, int(values.shape[0]), ptr(indptr),
                                                      ptr(cells), ptr(values), inv_theta, clip, ptr(s1), ptr(s2), ptr(cell_total),
                                                      ptr(gene_total)))
             var = s2 / N - (s1 / N) ** 2 if N else torch.zeros_like(s2)
             distinct = int(torch.unique(cell_total).numel())
         return dict(zip(NAMES, (s1, s2, var, gene_total, cell_total, distinct)))
 
-    N, J, indptr, indices, data = _host_csc(X)
+    N, J, indptr, indices, data = host_csc(X)
     inv_theta, clip = _parameters(theta, clip, N)
-    lib = _lib.load()
-    _lib.require_gpu()
-    device = int(os.environ.get("SCHPF_DEVICE", "0")) if device is None else int(device)
+    lib = library()
     s1, s2 = np.zeros(J, np.float64), np.zeros(J, np.float64)
     cell_total, gene_total = np.zeros(N, np.int64), np.zeros(J, np.int64)
-    _lib.check(lib.schpf_residual_var(device, N, J, len(data), indptr.ctypes.data_as(ctypes.c_void_p), _p(indices), _p(data),
+    _lib.check(lib.schpf_residual_var(device_of(device), N, J, len(data), _p(indptr), _p(indices), _p(data),
                                       inv_theta, clip, _p(s1), _p(s2), _p(cell_total), _p(gene_total)))
     var = s2 / N - (s1 / N) ** 2 if N else np.zeros(J)
     return dict(zip(NAMES, (s1, s2, var, gene_total, cell_total, int(np.unique(cell_total).size))))
@@ -132,7 +105,6 @@ def highly_variable_genes(X, n_top_genes=2000, theta=100.0, clip=None, batch=Non
     n_top_genes = int(n_top_genes)
     if n_top_genes < 0:
         raise ValueError("n_top_genes must be >= 0, got %d" % n_top_genes)
-    host = lambda a: a.detach().cpu().numpy() if is_torch_tensor(a) else np.asarray(a)  # noqa: E731
     N, J = int(X.shape[0]), int(X.shape[1])
     if batch is None:
         found = residual_variance(X, theta=theta, clip=clip, device=device)

@@ -33,7 +33,7 @@ def child(kv):
     from _ranksum_reference import random_labels, sparse_entries
     from knn_time import event_ms
     from schpf_amd import _lib
-    from schpf_amd.markers import _gpu_csc
+    from schpf_amd.device_input import gpu_csc
 
     n, K, k, calls = int(kv.get("n", 100000)), int(kv.get("K", 20)), int(kv.get("k", 15)), int(kv.get("calls", 10))
     N, J = (int(s) for s in kv.get("shape", "100000x20000").split("x"))
@@ -83,7 +83,7 @@ def child(kv):
     h_cells, h_genes, h_values = sparse_entries(N, J, per_cell, seed=0)
     X = torch.sparse_coo_tensor(torch.stack([torch.tensor(h_cells, device="cuda:0").long(), torch.tensor(h_genes, device="cuda:0").long()]),
                                 torch.tensor(h_values, device="cuda:0"), size=(N, J))
-    m_indptr, cell_ids, values = _gpu_csc(X)
+    m_indptr, cell_ids, values = gpu_csc(X)
     del X
     m_labels = torch.tensor(random_labels(N, G, seed=1), device="cuda:0")
     outs = [torch.zeros(s, dtype=torch.int64, device="cuda:0") for s in ((G,), (J,), (J,), (G, J), (G, J))]

@@ -33,7 +33,7 @@ from _pair_ranksum_reference import all_pairs, debug_pair_rank_sums  # noqa: E40
 from _ranksum_reference import random_labels, sparse_entries  # noqa: E402
 from knn_time import event_ms  # noqa: E402
 from schpf_amd import _lib  # noqa: E402
-from schpf_amd.markers import _gpu_csc  # noqa: E402
+from schpf_amd.device_input import gpu_csc  # noqa: E402
 from schpf_amd.qc import submatrix  # noqa: E402
 
 p = lambda t: ctypes.c_void_p(t.data_ptr() if t.numel() else None)  # noqa: E731
@@ -100,7 +100,7 @@ def one_shape(lib, N, J, per_cell, G, calls, loop_calls, few, scaled, n_slice, s
     X = torch.sparse_coo_tensor(torch.stack([torch.tensor(cells, device="cuda:0").long(), torch.tensor(genes, device="cuda:0").long()]),
                                 torch.tensor(values, device="cuda:0"), size=(N, J))
     del cells, genes, values
-    indptr, cell_ids, data = _gpu_csc(X)
+    indptr, cell_ids, data = gpu_csc(X)
     del X
     h_labels = random_labels(N, G, seed=1)
     rec = {"ncells": N, "ngenes": J, "per_cell": per_cell, "ngroups": G, "calls": calls, "loop_calls": loop_calls}

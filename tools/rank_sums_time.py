@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from _ranksum_reference import debug_rank_sums, random_labels, sparse_entries  # noqa: E402
 from knn_time import event_ms  # noqa: E402
 from schpf_amd import _lib  # noqa: E402
-from schpf_amd.markers import _gpu_csc  # noqa: E402
+from schpf_amd.device_input import gpu_csc  # noqa: E402
 
 
 def one_shape(lib, N, J, per_cell, G, calls, n_slice, host):
@@ -35,7 +35,7 @@ def one_shape(lib, N, J, per_cell, G, calls, n_slice, host):
     X = torch.sparse_coo_tensor(torch.stack([torch.tensor(cells, device="cuda:0").long(), torch.tensor(genes, device="cuda:0").long()]),
                                 torch.tensor(values, device="cuda:0"), size=(N, J))
     del cells, genes, values
-    indptr, cell_ids, data = _gpu_csc(X)
+    indptr, cell_ids, data = gpu_csc(X)
     del X
     h_labels = random_labels(N, G, seed=1)
     labels = torch.tensor(h_labels, device="cuda:0")

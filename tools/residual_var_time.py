@@ -8,7 +8,7 @@ draws, skewed gene popularity), as a coalesced COO tensor and a CSR tensor on th
 Timed with HIP events on torch's current stream, the median of `calls` after one untimed call:
   * schpf_residual_var_device, the whole call -- checks, totals, the sort of the cell totals, both passes, the call's own
     allocations -- on the gene-major arrays, with the default clip sqrt(N);
-  * markers._gpu_csc, the sort to gene-major in torch that residual_variance runs first on a CSR tensor, and
+  * device_input.gpu_csc, the sort to gene-major in torch that residual_variance runs first on a CSR tensor, and
     residual_variance end to end on that tensor.
 Recorded beside them: U, the number of distinct cell totals the dense pass walks, and the 12 nnz bytes the sparse pass reads
 with their time at the HBM peak of 8 TB/s.
@@ -32,7 +32,7 @@ from _ranksum_reference import sparse_entries  # noqa: E402
 from _residual_var_reference import tolerance  # noqa: E402
 from knn_time import event_ms  # noqa: E402
 from schpf_amd import _lib, variable_genes  # noqa: E402
-from schpf_amd.markers import _gpu_csc  # noqa: E402
+from schpf_amd.device_input import gpu_csc  # noqa: E402
 
 HBM_PEAK = 8.0e12      # bytes per second, MI355X
 
@@ -47,7 +47,7 @@ def one_shape(lib, N, J, draws, calls, with_torch, torch_calls, chunk, theta):
     crow = torch.zeros(N + 1, dtype=torch.int64, device=dev)
     crow[1:] = torch.cumsum(torch.bincount(rows, minlength=N), 0)
     csr = torch.sparse_csr_tensor(crow, cols, vals, size=(N, J))
-    indptr, cell_ids, data = _gpu_csc(X)
+    indptr, cell_ids, data = gpu_csc(X)
     nnz = int(data.numel())
     inv_theta, clip = (0.0 if math.isinf(theta) else 1.0 / theta), math.sqrt(N)
     stream = ctypes.c_void_p(int(torch.cuda.current_stream().cuda_stream) or _lib.STREAM_DEFAULT)
@@ -68,7 +68,7 @@ def one_shape(lib, N, J, draws, calls, with_torch, torch_calls, chunk, theta):
     rec["entries_per_second"] = round(nnz / (rec["residual_var_device"]["median_ms"] * 1e-3))
     print("%d x %d @ %d: the call %s, U = %d" % (N, J, draws, rec["residual_var_device"], rec["n_distinct_totals"]),
           file=sys.stderr, flush=True)
-    rec["gpu_csc_of_a_csr_tensor"] = event_ms(lambda: _gpu_csc(csr), 3, warm=1)
+    rec["gpu_csc_of_a_csr_tensor"] = event_ms(lambda: gpu_csc(csr), 3, warm=1)
     rec["residual_variance_on_a_csr_tensor"] = event_ms(lambda: variable_genes.residual_variance(csr, theta=theta), 3, warm=1)
     print("%d x %d @ %d: to gene-major %s, end to end %s" % (N, J, draws, rec["gpu_csc_of_a_csr_tensor"],
                                                             rec["residual_variance_on_a_csr_tensor"]), file=sys.stderr, flush=True)
