@@ -844,6 +844,42 @@ int schpf_debug_group_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const i
                             const void *val, int val_kind, const int32_t *labels, int64_t ngroups, int64_t *group_cells,
                             int64_t *nexpr, int64_t *total, int64_t *sumsq);
 
+/* Gene-major form of a count matrix: an exact sparse transpose, the CSC arrays that schpf_rank_sums,
+ * schpf_pair_rank_sums and schpf_residual_var take, from the CSR that everything upstream produces.  Integer work whose
+ * result is fully determined: every schedule gives the same bits.
+ * Input: a CSR matrix of ncells x ngenes with nnz stored entries, as schpf_axis_stats takes it: indptr 0 at row 0,
+ *   non-decreasing, ending at nnz; the columns in [0, ngenes) and strictly ascending within a row.  The values are not
+ *   interpreted.  out_val_kind is val_kind -- the bytes of every value are moved unchanged (-0.0, NaN payloads and stored
+ *   zeros survive, as in schpf_submatrix) -- or SCHPF_VAL_F32: the value is (float) of the double that the input value
+ *   converts to, exact for counts up to 2^24.
+ * Output: out_indptr int64[ngenes + 1], out_cells int32[nnz], out_values [nnz] of out_val_kind: the CSC form of the same
+ *   matrix.  Gene j's entries lie at [out_indptr[j], out_indptr[j + 1]), the cells ascending: entry (i, j) stands at
+ *   out_indptr[j] + #{stored (i', j) : i' < i}.  out_source int64[nnz], skipped when NULL: the stored position in the input
+ *   of every output entry, with which a caller carries a second value array across without a second transpose.
+ *   Refused before anything is written, M the smallest offender, in this order:
+ *     "transpose: indptr must be 0 at row 0, must be non-decreasing and must end at nnz; offending row M"
+ *     "transpose: column index out of range at entry M"
+ *     "transpose: columns must be strictly ascending within a row; offending row M"
+ *   nnz == 0, ncells == 0 or ngenes == 0 succeeds without reading the matrix: out_indptr is zeros.  Sizes outside [0, 2^31),
+ *   unknown kinds, an out_val_kind that is neither val_kind nor SCHPF_VAL_F32 and NULL pointers otherwise (out_indptr
+ *   always) are refused before anything is read.
+ * _device: indptr (of indptr_kind), indices (of idx_kind: SCHPF_IDX_*), val (of val_kind) and the outputs are DEVICE pointers
+ *   on `device`, read and written in place; stream as in schpf_thin_counts_device; synchronised before the call returns.
+ *   Scratch: a table of 4 ngenes bytes per slab of 2048 rows (4 ngenes ceil(ncells / 2048) bytes: 49 MB at 1M x 25 000),
+ *   8 (ngenes + 1) bytes, the scan's own and a few words.
+ * schpf_transpose: host pointers (int64 indptr, int32 indices), staged through the device; the same result.
+ * schpf_debug_transpose: test hook (host only, no GPU needed): a serial counting transpose, one entry after the other, which
+ *   the others must match bit for bit. */
+int schpf_transpose_device(int device, void *stream, int64_t ncells, int64_t ngenes, int64_t nnz, const void *indptr,
+                           int indptr_kind, const void *indices, int idx_kind, const void *val, int val_kind, int out_val_kind,
+                           int64_t *out_indptr, int32_t *out_cells, void *out_values, int64_t *out_source);
+int schpf_transpose(int device, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                    const void *val, int val_kind, int out_val_kind, int64_t *out_indptr, int32_t *out_cells, void *out_values,
+                    int64_t *out_source);
+int schpf_debug_transpose(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                          const void *val, int val_kind, int out_val_kind, int64_t *out_indptr, int32_t *out_cells,
+                          void *out_values, int64_t *out_source);
+
 /* Test hooks of the fused Gamma update (kernels.hip gamma_update_kernel; both need a GPU).
  * schpf_debug_special: one function of csrc/special.h per element, evaluated on the DEVICE by one thread per element
  *   through the inline bodies the update kernel calls: out[i] = fast_rcp(x[i]), fast_log(x[i]), fast_exp(x[i]),

@@ -14,6 +14,7 @@ from schpf_amd.paths import geodesic_distances, pseudotime, farthest_landmarks, 
 from schpf_amd.markers import rank_sums, rank_genes_groups, pair_rank_sums, rank_genes_pairs  # noqa: F401
 from schpf_amd.aggregate import group_stats, pseudobulk, group_codes  # noqa: F401
 from schpf_amd.variable_genes import residual_variance, highly_variable_genes  # noqa: F401
+from schpf_amd.gene_major import GeneMajor, gene_major  # noqa: F401
 from schpf_amd.util import *  # noqa: F401,F403
 from schpf_amd._version import __version__  # noqa: F401
 from schpf_amd import loss, hpf_hip  # noqa: F401

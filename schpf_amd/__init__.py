@@ -18,6 +18,7 @@ from .doublets import simulate_doublets, doublet_scores
 from .qc import qc_metrics, submatrix, filter_counts
 from .aggregate import group_stats, pseudobulk, group_codes
 from .variable_genes import residual_variance, highly_variable_genes
+from .gene_major import GeneMajor, gene_major
 
 # make the pickle module path of the classes (schpf.scHPF_) resolvable
 import schpf.scHPF_  # noqa: E402,F401
@@ -27,4 +28,5 @@ __all__ = ["__version__", "hpf_hip", "loss", "preprocessing", "DeviceCAVI", "HPF
            "knn_connectivities", "louvain", "modularity", "rank_sums", "rank_genes_groups", "pair_rank_sums", "rank_genes_pairs", "simulate_doublets",
            "doublet_scores", "qc_metrics", "submatrix", "filter_counts", "group_stats", "pseudobulk", "group_codes",
            "connected_components", "cluster_graph", "absorb_small", "paga", "geodesic_distances", "pseudotime",
-           "farthest_landmarks", "landmark_isomap", "residual_variance", "highly_variable_genes"]
+           "farthest_landmarks", "landmark_isomap", "residual_variance", "highly_variable_genes", "GeneMajor",
+           "gene_major"]

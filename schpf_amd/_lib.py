@@ -124,6 +124,9 @@ SIGNATURES = {
     "schpf_group_stats_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp],
     "schpf_group_stats": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp],
     "schpf_debug_group_stats": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp],
+    "schpf_transpose_device": [_int, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp, _int, _int, _vp, _vp, _vp, _vp],
+    "schpf_transpose": [_int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp],
+    "schpf_debug_transpose": [_i64, _i64, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp],
     "schpf_debug_special": [_int, _i64, _vp, _vp, _vp],
     "schpf_debug_tables": [_vp, _int, _vp, _vp, _vp],
     "schpf_debug_choose_config": [_int, _int, _int, ctypes.POINTER(_int)],

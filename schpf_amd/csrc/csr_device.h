@@ -1,7 +1,8 @@
-// What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip, group_stats.hip) on
-// top of the scaffold of device_call.h: the loaders for the index and value kinds of include/schpf_hip.h, the matrix record,
-// the bisection of a row, and -- in csr_checks, for qc.hip and group_stats.hip -- the validation of a count CSR: the two
-// kernels and the words of their smallest offenders.
+// What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip, group_stats.hip,
+// transpose.hip) on top of the scaffold of device_call.h: the loaders for the index and value kinds of include/schpf_hip.h,
+// the matrix record, the bisection of a row, and -- in csr_checks, for qc.hip, group_stats.hip and transpose.hip -- the
+// validation of a CSR: the kernels (of a count CSR csr_entries_kernel, of one whose values mean nothing csr_order_kernel) and
+// the words of their smallest offenders.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 
@@ -107,6 +108,25 @@ template <bool counts> __global__ __launch_bounds__(CSR_THREADS) void csr_entrie
     if (lane == 0 && vmax > __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMax(words + W_VMAX, vmax);
 }
 
+// A wavefront per row, as above, for a matrix whose values mean nothing to the caller (the transpose): every column in
+// [0, ngenes) and above its left neighbour, and no more
+static __global__ __launch_bounds__(CSR_THREADS) void csr_order_kernel(Matrix m, unsigned long long *__restrict__ words)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (CSR_THREADS / 64);
+    unsigned long long bad_index = NONE, bad_order = NONE;
+    for (int64_t r = blockIdx.x * (int64_t)(CSR_THREADS / 64) + (threadIdx.x >> 6); r < m.ncells; r += waves) {
+        const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
+        for (int64_t e = from + lane; e < to; e += 64) {
+            const long long c = load_index(m.indices, m.idx_kind, e);
+            if (c < 0 || c >= m.ngenes) offends(bad_index, e);
+            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c) offends(bad_order, r);
+        }
+    }
+    report_min(words + W_BAD_INDEX, bad_index);
+    report_min(words + W_BAD_ORDER, bad_order);
+}
+
 #define CSR_LAUNCH(kernel, n, per_block, st, ...)                                                                          \
     do {                                                                                                                   \
         hipLaunchKernelGGL(kernel, dim3(grid_for(n, per_block)), dim3(schpf::csr_checks::CSR_THREADS), 0, st, __VA_ARGS__); \
@@ -131,6 +151,12 @@ template <bool counts> inline void launch_entries_check(hipStream_t st, const Ma
 {
     const int per_wave = CSR_THREADS / 64;
     CSR_LAUNCH(csr_entries_kernel<counts>, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
+}
+
+inline void launch_order_check(hipStream_t st, const Matrix &m, Words &w)
+{
+    const int per_wave = CSR_THREADS / 64;
+    CSR_LAUNCH(csr_order_kernel, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
 }
 
 // out[i] = in[0] + .. + in[i - 1] (rocPRIM)

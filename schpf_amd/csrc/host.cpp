@@ -3,7 +3,8 @@
 // (knn.hip), of the neighbour graphs (knn_graph.hip), of the Louvain clustering (louvain.hip), of the connected
 // components and the cluster graph (components.hip), of the shortest-path distances (geodesic.hip), of the rank sums
 // (rank_sums.hip), of the simulated doublets (doublets.hip) with the draw of their parents and of the axis statistics and
-// the submatrix (qc.hip), of the Pearson residual sums per gene (residual_var.hip), and the SCHPF_BACKTRACE crash handler.
+// the submatrix (qc.hip), of the Pearson residual sums per gene (residual_var.hip), of the transpose to gene-major
+// (transpose.hip), and the SCHPF_BACKTRACE crash handler.
 // Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
@@ -24,6 +25,7 @@
 #include "qc.h"
 #include "residual_var.h"
 #include "special.h"
+#include "transpose.h"
 
 using namespace schpf;
 
@@ -1288,6 +1290,49 @@ int schpf_debug_group_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const i
                 if (sumsq) sumsq[at] += v * v;
             }
         }
+    });
+}
+
+
+// transpose.hip restated: the same refusals in the same order, then a serial counting transpose, one entry
+// after the other in stored order
+int schpf_debug_transpose(int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                          const void *val, int val_kind, int out_val_kind, int64_t *out_indptr, int32_t *out_cells,
+                          void *out_values, int64_t *out_source)
+{
+    if (const char *why = transpose_bad_args(ncells, ngenes, nnz, indptr, SCHPF_IDX_I64, indices, SCHPF_IDX_I32, val, val_kind,
+                                             out_val_kind, out_indptr, out_cells, out_values))
+        return fail("%s", why);
+    return guarded([&] {
+        const size_t J = (size_t)ngenes;
+        if (transpose_empty(ncells, ngenes, nnz)) {
+            std::fill(out_indptr, out_indptr + J + 1, (int64_t)0);
+            return;
+        }
+        for (int64_t r = 0; r <= ncells; ++r)
+            if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
+                throw std::invalid_argument(transpose_bad_indptr(r));
+        int64_t bad_index = -1, bad_order = -1;
+        for (int64_t r = 0; r < ncells; ++r)
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
+                if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
+            }
+        if (bad_index >= 0) throw std::invalid_argument(transpose_bad_index(bad_index));
+        if (bad_order >= 0) throw std::invalid_argument(transpose_bad_order(bad_order));
+        std::vector<int64_t> next(J + 1, 0);   // next[j + 1]: the entries of gene j, then where its next entry goes
+        for (int64_t e = 0; e < nnz; ++e) ++next[(size_t)indices[e] + 1];
+        for (size_t j = 0; j < J; ++j) next[j + 1] += next[j];
+        std::copy(next.begin(), next.end(), out_indptr);
+        const size_t width = transpose_value_size(val_kind);
+        for (int64_t r = 0; r < ncells; ++r)
+            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+                const int64_t o = next[(size_t)indices[e]]++;
+                out_cells[o] = (int32_t)r;
+                if (out_val_kind != val_kind) static_cast<float *>(out_values)[o] = transpose_value(read_count(val, val_kind, e));
+                else std::memcpy((char *)out_values + (size_t)o * width, (const char *)val + (size_t)e * width, width);   // the bytes as they are
+                if (out_source) out_source[o] = e;
+            }
     });
 }
 

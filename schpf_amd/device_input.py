@@ -167,15 +167,10 @@ def gpu_coo(X):
 
 def gpu_csc(X):
     """A sparse COO / CSR tensor on a GPU -> (indptr int64, cell ids int32, values float32) of its CSC form, duplicates
-    summed, with torch on that GPU."""
-    import torch
-    rows, cols, values = gpu_coo(X)
-    N, J = int(X.shape[0]), int(X.shape[1])
-    order = torch.argsort(cols * N + rows)              # gene-major, the cells ascending within a gene
-    indptr = torch.zeros(J + 1, dtype=torch.int64, device=X.device)
-    if J:
-        indptr[1:] = torch.cumsum(torch.bincount(cols, minlength=J), 0)
-    return indptr, rows[order].to(torch.int32).contiguous(), values[order].to(torch.float32).contiguous()
+    summed: what `gene_major(X)` holds.  A CSR tensor with canonical rows goes through the library's exact transpose
+     and meets no sort; anything else is coalesced with torch on that GPU first."""
+    from .gene_major import gene_major
+    return gene_major(X).float32()
 
 
 # ---- a count matrix anywhere else ----

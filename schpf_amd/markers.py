@@ -10,7 +10,8 @@ import numpy as np
 
 from . import _lib
 from ._call import array_ptr as _p, device_of, library, same_device, stream_of, tensor_ptr as ptr
-from .device_input import classify, gpu_coo, gpu_csc, host_csc, int32_labels, is_torch_tensor, on_gpu
+from .device_input import classify, gpu_coo, int32_labels, is_torch_tensor, on_gpu
+from .gene_major import gpu_arrays, held_on_gpu, host_arrays, refuse_gene_major
 
 __all__ = ["rank_sums", "rank_genes_groups", "benjamini_hochberg", "pair_rank_sums", "rank_genes_pairs"]
 
@@ -57,7 +58,7 @@ def _check_sizes(ncells, ngenes, ngroups):
 
 def _gpu_inputs(X, labels, ngroups, device):
     """What a call on a matrix in GPU memory hands to the library: (the library, torch device, N, J, G, int32 labels on that
-    GPU, the CSC arrays of `gpu_csc`, torch's current stream there)."""
+    GPU, the CSC arrays of `gene_major`, torch's current stream there)."""
     import torch
     lib = library()
     dev = X.device
@@ -68,7 +69,7 @@ def _gpu_inputs(X, labels, ngroups, device):
         G = _groups(lab, ngroups, N)
         _check_sizes(N, J, G)
         lab = lab.to(device=dev, dtype=torch.int32).contiguous()
-        indptr, cells, values = gpu_csc(X)
+        indptr, cells, values = gpu_arrays(X)
         stream = stream_of(dev)
     return lib, dev, N, J, G, lab, indptr, cells, values, stream
 
@@ -79,7 +80,7 @@ def _host_inputs(X, labels, ngroups):
     if is_torch_tensor(labels):
         labels = labels.detach().cpu().numpy()
     labels = np.asarray(labels)
-    N, J, indptr, indices, data = host_csc(X)
+    N, J, indptr, indices, data = host_arrays(X)
     G = _groups(labels, ngroups, N)
     _check_sizes(N, J, G)
     return N, J, G, indptr, indices, data, int32_labels(labels, np.iinfo(np.int32).min, "labels must be in [-1, ngroups)")
@@ -94,12 +95,12 @@ def rank_sums(X, labels, ngroups=None, device=None):
     X: cells x genes.  A SciPy sparse matrix is converted with tocsc() on a copy, duplicates summed; NumPy arrays come back.
     A torch sparse COO or CSR tensor on a GPU is converted to CSC with torch on that GPU and ranked on torch's current
     stream; tensors on that GPU come back.  Values are ranked as float32 (counts up to 2^24 are exact), must be finite and
-    >= 0; stored zeros are zeros like the implicit ones.
+    >= 0; stored zeros are zeros like the implicit ones.  A `GeneMajor` (`gene_major(X)`) in place of X skips the conversion.
 
     labels: one integer per cell in [-1, G), NumPy or a tensor; -1 ranks the cell with all the others but puts it in no
     group.  ngroups: G, default the largest label + 1.  Fewer than 2^21 cells, and G * J < 2^31.  What the library refuses
     raises ValueError naming the smallest offending gene or cell."""
-    if on_gpu(X):
+    if held_on_gpu(X):
         import torch
         lib, dev, N, J, G, lab, indptr, cells, values, stream = _gpu_inputs(X, labels, ngroups, device)
         with torch.cuda.device(dev):
@@ -189,6 +190,7 @@ def rank_genes_groups(X, labels, tie_correct=True, target_sum=None, device=None,
     reference: None, or a group r: every other group is then tested against group r alone (scanpy's `reference=`) -- the
     result of `rank_genes_pairs` for the pairs (g, r), g != r, laid out as (G, J) with NaN in row r; the keys are those of
     `rank_genes_pairs` (pct_a, pct_b, mean_a, mean_b: a is the row's group, b the reference), `n` the cells per group."""
+    refuse_gene_major(X, "rank_genes_groups")
     if reference is not None:
         return _against_reference(X, labels, int(reference), tie_correct, target_sum, device)
     if is_torch_tensor(X) and not on_gpu(X):      # a tensor in host memory: as SciPy
@@ -265,8 +267,9 @@ def pair_rank_sums(X, labels, pairs="all", ngroups=None, device=None):
 
     pairs: "all" -- every a < b -- or rows (a, b) of two different groups; a row may be repeated or reversed.  X, labels,
     ngroups and device as for `rank_sums`: a torch sparse COO or CSR tensor on a GPU is ranked there on torch's current
-    stream and tensors come back (`pairs` too); anything else goes through SciPy and NumPy arrays come back."""
-    if on_gpu(X):
+    stream and tensors come back (`pairs` too); anything else goes through SciPy and NumPy arrays come back.  A `GeneMajor`
+    (`gene_major(X)`) in place of X skips the conversion."""
+    if held_on_gpu(X):
         import torch
         lib, dev, N, J, G, lab, indptr, cells, values, stream = _gpu_inputs(X, labels, ngroups, device)
         pairs = _pairs(pairs, G, J)
@@ -312,6 +315,7 @@ def rank_genes_pairs(X, labels, pairs="all", tie_correct=True, target_sum=None, 
 
     pairs: "all" or rows (a, b).  target_sum: scale every cell's counts to that total before ranking ("median": the median
     depth), in float32; nearly every entry is then its own value, the slowest case of the kernels."""
+    refuse_gene_major(X, "rank_genes_pairs")
     if is_torch_tensor(X) and not on_gpu(X):      # a tensor in host memory: as SciPy
         X = classify(X).matrix
     if is_torch_tensor(labels) and not on_gpu(X):

@@ -451,6 +451,14 @@ class scHPF(BaseEstimator):
         from .variable_genes import highly_variable_genes
         return highly_variable_genes(X, **kwargs)
 
+    @staticmethod
+    def gene_major(X, **kwargs):
+        """The count matrix X (cells x genes) gene-major, converted once: the `GeneMajor` of schpf_amd.gene_major (kwargs go
+        there: values, device), which `rank_sums`, `pair_rank_sums` and `residual_variance` take in place of X.  An addition
+        to the reference's surface."""
+        from .gene_major import gene_major
+        return gene_major(X, **kwargs)
+
     def mean_negative_pois_llh(self, X, theta=None, beta=None, **kwargs):
         """Mean negative llh over the nonzeros of X (scHPF_.py:416-422)."""
         theta = self.theta if theta is None else theta

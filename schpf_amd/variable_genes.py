@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._call import array_ptr as _p, device_of, library, same_device, stream_of, tensor_ptr as ptr
-from .device_input import gpu_csc, host_csc, on_gpu, to_numpy as host
+from .device_input import to_numpy as host
+from .gene_major import gpu_arrays, held_on_gpu, host_arrays, refuse_gene_major
 
 __all__ = ["residual_variance", "highly_variable_genes"]
 
@@ -48,8 +49,8 @@ def residual_variance(X, theta=100.0, clip=None, device=None):
     r^2 per gene, the library's outputs, the same bits on every call), `residual_var` = sumsq / N - (sum / N)^2 (ddof = 0,
     as NumPy's var and scanpy), `gene_total` and `cell_total` (int64, exact) and `n_distinct_totals`, the number of
     different cell totals the dense part of the sum walked.  What the library refuses raises ValueError naming the smallest
-    offending gene."""
-    if on_gpu(X):
+    offending gene.  A `GeneMajor` (`gene_major(X)`) in place of X skips the conversion."""
+    if held_on_gpu(X):
         import torch
         lib = library()
         dev = X.device
@@ -57,7 +58,7 @@ def residual_variance(X, theta=100.0, clip=None, device=None):
         N, J = int(X.shape[0]), int(X.shape[1])
         inv_theta, clip = _parameters(theta, clip, N)
         with torch.cuda.device(dev):
-            indptr, cells, values = gpu_csc(X)
+            indptr, cells, values = gpu_arrays(X)
             s1, s2 = torch.zeros(J, dtype=torch.float64, device=dev), torch.zeros(J, dtype=torch.float64, device=dev)
             cell_total = torch.zeros(N, dtype=torch.int64, device=dev)
             gene_total = torch.zeros(J, dtype=torch.int64, device=dev)
@@ -68,7 +69,7 @@ def residual_variance(X, theta=100.0, clip=None, device=None):
             distinct = int(torch.unique(cell_total).numel())
         return dict(zip(NAMES, (s1, s2, var, gene_total, cell_total, distinct)))
 
-    N, J, indptr, indices, data = host_csc(X)
+    N, J, indptr, indices, data = host_arrays(X)
     inv_theta, clip = _parameters(theta, clip, N)
     lib = library()
     s1, s2 = np.zeros(J, np.float64), np.zeros(J, np.float64)
@@ -114,6 +115,7 @@ def highly_variable_genes(X, n_top_genes=2000, theta=100.0, clip=None, batch=Non
                "means": host(found["gene_total"]) / float(N) if N else np.zeros(J)}
     else:
         from .qc import submatrix
+        refuse_gene_major(X, "highly_variable_genes(batch=...)")
         batch = host(batch)
         if batch.shape != (N,):
             raise ValueError("batch must hold one label per cell: %d, got shape %s" % (N, tuple(batch.shape)))
@@ -136,7 +138,7 @@ def highly_variable_genes(X, n_top_genes=2000, theta=100.0, clip=None, batch=Non
         rank[order] = np.arange(J)
         out = {"highly_variable": rank < n_top_genes, "rank": rank, "residual_var": var / max(len(labels), 1),
                "means": total / float(N) if N else np.zeros(J), "n_batches": n_batches.astype(np.int64), "median_rank": median}
-    if on_gpu(X):
+    if held_on_gpu(X):
         import torch
         out = {name: torch.from_numpy(np.ascontiguousarray(a)).to(X.device) for name, a in out.items()}
     return out
