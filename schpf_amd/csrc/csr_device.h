@@ -1,11 +1,11 @@
 // What the translation units that read a caller's CSR in device memory share (doublets.hip, qc.hip, group_stats.hip,
 // transpose.hip) on top of the scaffold of device_call.h: the loaders for the index and value kinds of include/schpf_hip.h,
-// the matrix record, the bisection of a row, and -- in csr_checks, for qc.hip, group_stats.hip and transpose.hip -- the
-// validation of a CSR: the kernels (of a count CSR csr_entries_kernel, of one whose values mean nothing csr_order_kernel) and
-// the words of their smallest offenders.
+// the matrix record, the bisection of a row, and -- in csr_checks -- the validation of a CSR to a level of csr_words.h: the
+// two kernels, the words of their smallest offenders and the refusals in the words of csr_words.h.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 
+#include "csr_words.h"
 #include "device_call.h"
 #include "philox.h"
 
@@ -41,8 +41,6 @@ __device__ __forceinline__ Row row_of(const Matrix &m, int64_t r)
     return Row{from, load_index(m.indptr, m.indptr_kind, r + 1) - from};
 }
 
-inline size_t value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
-
 // the first of the n ascending columns at p that is not below `key`
 template <typename I> __device__ __forceinline__ int64_t lower_bound(const I *__restrict__ p, int64_t n, long long key)
 {
@@ -76,9 +74,10 @@ static __global__ __launch_bounds__(CSR_THREADS) void csr_indptr_kernel(const vo
     report_min(words + W_BAD_INDPTR, bad);
 }
 
-// A wavefront per row.  counts: the matrix must be canonical and hold counts (the statistics): every column above its left
-// neighbour, every value a count thinning accepts, and the largest value; else only the column range is asked (the submatrix)
-template <bool counts> __global__ __launch_bounds__(CSR_THREADS) void csr_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
+// A wavefront per row checks the entries to `level` (csr_words.h): every column in [0, ngenes); from CSR_ORDER on every
+// column above its left neighbour; at CSR_COUNTS every value a count thinning accepts, and the largest value.  W_VMAX takes
+// the largest value as the smallest complement: it starts at NONE like the offenders, and NONE is a largest value of 0
+template <int level> __global__ __launch_bounds__(CSR_THREADS) void csr_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
 {
     const int lane = threadIdx.x & 63;
     const int64_t waves = (int64_t)gridDim.x * (CSR_THREADS / 64);
@@ -87,44 +86,21 @@ template <bool counts> __global__ __launch_bounds__(CSR_THREADS) void csr_entrie
         const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
         for (int64_t e = from + lane; e < to; e += 64) {
             const long long c = load_index(m.indices, m.idx_kind, e);
-            if ((c < 0 || c >= m.ngenes) && (unsigned long long)e < bad_index) bad_index = (unsigned long long)e;
-            if (!counts) continue;
-            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c && (unsigned long long)r < bad_order)
-                bad_order = (unsigned long long)r;
-            const double v = load_value(m.val, m.val_kind, e);
-            if (thin_value_bad(v)) {
-                if ((unsigned long long)e < bad_value) bad_value = (unsigned long long)e;
-            } else if ((unsigned long long)v > vmax) {
-                vmax = (unsigned long long)v;
-            }
-        }
-    }
-    report_min(words + W_BAD_INDEX, bad_index);
-    if (!counts) return;
-    report_min(words + W_BAD_ORDER, bad_order);
-    report_min(words + W_BAD_VALUE, bad_value);
-    vmax = ~wave_min(~vmax);
-    // a million wavefronts on one address is what this kernel would wait for: only a value above the one seen goes there
-    if (lane == 0 && vmax > __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMax(words + W_VMAX, vmax);
-}
-
-// A wavefront per row, as above, for a matrix whose values mean nothing to the caller (the transpose): every column in
-// [0, ngenes) and above its left neighbour, and no more
-static __global__ __launch_bounds__(CSR_THREADS) void csr_order_kernel(Matrix m, unsigned long long *__restrict__ words)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (CSR_THREADS / 64);
-    unsigned long long bad_index = NONE, bad_order = NONE;
-    for (int64_t r = blockIdx.x * (int64_t)(CSR_THREADS / 64) + (threadIdx.x >> 6); r < m.ncells; r += waves) {
-        const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
-        for (int64_t e = from + lane; e < to; e += 64) {
-            const long long c = load_index(m.indices, m.idx_kind, e);
             if (c < 0 || c >= m.ngenes) offends(bad_index, e);
-            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c) offends(bad_order, r);
+            if (level >= CSR_ORDER && e > from && load_index(m.indices, m.idx_kind, e - 1) >= c) offends(bad_order, r);
+            if (level < CSR_COUNTS) continue;
+            const double v = load_value(m.val, m.val_kind, e);
+            if (thin_value_bad(v)) offends(bad_value, e);
+            else if ((unsigned long long)v > vmax) vmax = (unsigned long long)v;
         }
     }
     report_min(words + W_BAD_INDEX, bad_index);
-    report_min(words + W_BAD_ORDER, bad_order);
+    if (level >= CSR_ORDER) report_min(words + W_BAD_ORDER, bad_order);
+    if (level < CSR_COUNTS) return;
+    report_min(words + W_BAD_VALUE, bad_value);
+    const unsigned long long least = wave_min(~vmax);
+    // a million wavefronts on one address is what this kernel would wait for: only a value above the one seen goes there
+    if (lane == 0 && least < __atomic_load_n(words + W_VMAX, __ATOMIC_RELAXED)) atomicMin(words + W_VMAX, least);
 }
 
 #define CSR_LAUNCH(kernel, n, per_block, st, ...)                                                                          \
@@ -133,30 +109,30 @@ static __global__ __launch_bounds__(CSR_THREADS) void csr_order_kernel(Matrix m,
         HIPCHK(hipGetLastError());                                                                                         \
     } while (0)
 
-struct Words : Offenders<W_COUNT> {   // the smallest offenders, and the running maximum, which starts at 0
-    void reset(hipStream_t st)
+struct Words : Offenders<W_COUNT> {   // the smallest offenders and the largest value, and the refusals of operator `op`
+    uint64_t vmax() const { return ~h[W_VMAX]; }
+    void refuse_indptr(const char *op) const
     {
-        Offenders<W_COUNT>::reset(st);
-        HIPCHK(hipMemsetAsync(dev() + W_VMAX, 0, sizeof(unsigned long long), st));
+        refuse(W_BAD_INDPTR, [op](int64_t row) { return csr_bad_indptr(op, row); });
+    }
+    void refuse_entries(const char *op) const   // a word that the level of the check left alone refuses nothing
+    {
+        refuse(W_BAD_INDEX, [op](int64_t entry) { return csr_bad_index(op, entry); });
+        refuse(W_BAD_ORDER, [op](int64_t row) { return csr_bad_order(op, row); });
+        refuse(W_BAD_VALUE, [op](int64_t entry) { return csr_bad_value(op, entry); });
     }
 };
 
-// The two launches; the caller fetches the words and words its own refusals.  The indptr comes first and is fetched before
-// anything follows it into the entries.  A bounded grid for the entries: a wavefront walks many rows and reports once
+// The two launches; the caller fetches the words and refuses.  The indptr comes first and is fetched before anything follows
+// it into the entries.  A bounded grid for the entries: a wavefront walks many rows and reports once
 inline void launch_indptr_check(hipStream_t st, const Matrix &m, int64_t nnz, Words &w)
 {
     CSR_LAUNCH(csr_indptr_kernel, m.ncells + 1, CSR_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, w.dev());
 }
-template <bool counts> inline void launch_entries_check(hipStream_t st, const Matrix &m, Words &w)
+template <int level> inline void launch_entries_check(hipStream_t st, const Matrix &m, Words &w)
 {
     const int per_wave = CSR_THREADS / 64;
-    CSR_LAUNCH(csr_entries_kernel<counts>, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
-}
-
-inline void launch_order_check(hipStream_t st, const Matrix &m, Words &w)
-{
-    const int per_wave = CSR_THREADS / 64;
-    CSR_LAUNCH(csr_order_kernel, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
+    CSR_LAUNCH(csr_entries_kernel<level>, std::min<int64_t>(m.ncells, CSR_CHECK_BLOCKS * per_wave), per_wave, st, m, w.dev());
 }
 
 // out[i] = in[0] + .. + in[i - 1] (rocPRIM)

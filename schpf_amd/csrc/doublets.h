@@ -1,10 +1,12 @@
 // Simulated doublets: what the kernels of doublets.hip and the serial restatement of host.cpp share -- the
-// draw of a simulated row's parents on the generator of philox.h, the refusals of the entry points and their messages.
+// draw of a simulated row's parents on the generator of philox.h, the refusals of the entry points and their messages
+// (those of the matrix itself: csr_words.h).
 // Like philox.h, plain C++ that compiles for the host and for the device.
 #pragma once
 #include <cstdint>
 #include <string>
 
+#include "csr_words.h"
 #include "philox.h"
 
 namespace schpf {
@@ -46,29 +48,7 @@ inline const char *doublet_rows_bad_args(int64_t ncells, int64_t ngenes, int64_t
         return "indptr, indices, val, parents and out_indptr must not be NULL";
     return nullptr;
 }
-inline bool doublet_kinds_bad(int indptr_kind, int idx_kind, int val_kind)
-{
-    return (indptr_kind != SCHPF_IDX_I32 && indptr_kind != SCHPF_IDX_I64) || (idx_kind != SCHPF_IDX_I32 && idx_kind != SCHPF_IDX_I64) ||
-           val_kind < SCHPF_VAL_I32 || val_kind > SCHPF_VAL_F64;
-}
-// The refusals of the matrix and the pairs, in the order they are looked for; each names its smallest offender
-inline std::string doublet_bad_indptr(int64_t row)
-{
-    return "doublets: indptr must be 0 at row 0, must be non-decreasing and must end at nnz; offending row " + std::to_string(row);
-}
-inline std::string doublet_bad_index(int64_t entry) { return "doublets: column index out of range at entry " + std::to_string(entry); }
-inline std::string doublet_bad_order(int64_t row)
-{
-    return "doublets: columns must be strictly ascending within a row; offending row " + std::to_string(row);
-}
-inline std::string doublet_bad_value(int64_t entry)
-{
-    return "doublets: values must be integer counts in [0, 2^24]; offending entry " + std::to_string(entry);
-}
+// The refusals of the matrix are those of csr_words.h under the prefix "doublets"; the pairs come behind them
 inline std::string doublet_bad_parent(int64_t pair) { return "doublets: parents must be in [0, ncells); offending pair " + std::to_string(pair); }
-inline std::string doublet_bad_capacity(int64_t capacity, int64_t total)
-{
-    return "capacity must be at least the " + std::to_string(total) + " entries of the result, got " + std::to_string(capacity);
-}
 
 }  // namespace schpf

@@ -3,10 +3,12 @@
 // every output entry written by exactly one lane: host.cpp's serial restatement gives the same bits, whatever the grid.
 //
 //   doublet_parents_kernel   one simulated row per thread: the draw of doublets.h
-//   doublet_indptr_kernel    indptr starts at 0, does not decrease and ends at nnz: the smallest offending row
-//   doublet_entries_kernel   a wavefront per row of the matrix: every column in [0, ngenes) and above its left neighbour,
+//   csr_indptr_kernel        indptr starts at 0, does not decrease and ends at nnz: the smallest offending row
+//   csr_entries_kernel       a wavefront per row of the matrix: every column in [0, ngenes) and above its left neighbour,
 //                            every value a count thinning accepts: the smallest offending entry / row
-//   doublet_pairs_kernel     one pair per thread: both parents in [0, ncells)
+//                            (both in csr_device.h, shared with qc.hip, group_stats.hip and transpose.hip, as is the
+//                            bisection of a row)
+//   doublet_pairs_kernel     one pair per thread: both parents in [0, ncells); reports into the spare word W_BAD_ROW
 //   doublet_length_kernel    a wavefront per pair: |A| + |B| - the columns they share, which the lanes find by bisection
 //   (rocPRIM exclusive scan of the lengths: out_indptr)
 //   doublet_fill_kernel      a wavefront per pair walks A, then B, in pieces of DOUBLET_PIECE = 64 entries.  A lane bisects
@@ -31,10 +33,10 @@
 namespace schpf {
 namespace {
 
-constexpr int DB_THREADS = 256;
+using namespace csr_checks;
+
+constexpr int DB_THREADS = CSR_THREADS;
 constexpr int DOUBLET_PIECE = 64;   // entries of a parent per pass of a wavefront: one per lane
-// the smallest offenders, in device memory, in the order they are reported
-enum { W_BAD_INDPTR = 0, W_BAD_INDEX, W_BAD_ORDER, W_BAD_VALUE, W_BAD_PARENT, W_COUNT };
 
 __global__ __launch_bounds__(DB_THREADS) void doublet_parents_kernel(uint64_t first, int64_t n_sim, uint32_t N, uint32_t k0,
                                                                      uint32_t k1, int32_t *__restrict__ parents)
@@ -48,37 +50,6 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_parents_kernel(uint64_t fi
 }
 
 // Every lane of a wavefront leaves the loop before the reduction: no early return
-__global__ __launch_bounds__(DB_THREADS) void doublet_indptr_kernel(const void *__restrict__ indptr, int indptr_kind, int64_t ncells,
-                                                                    int64_t nnz, unsigned long long *__restrict__ words)
-{
-    unsigned long long bad = NONE;
-    for (int64_t r = blockIdx.x * (int64_t)DB_THREADS + threadIdx.x; r <= ncells; r += (int64_t)gridDim.x * DB_THREADS) {
-        const long long here = load_index(indptr, indptr_kind, r);
-        const bool wrong = (r == 0 && here != 0) || (r == ncells ? here != nnz : load_index(indptr, indptr_kind, r + 1) < here);
-        if (wrong) offends(bad, r);
-    }
-    report_min(words + W_BAD_INDPTR, bad);
-}
-
-__global__ __launch_bounds__(DB_THREADS) void doublet_entries_kernel(Matrix m, unsigned long long *__restrict__ words)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t waves = (int64_t)gridDim.x * (DB_THREADS / 64);
-    unsigned long long bad_index = NONE, bad_order = NONE, bad_value = NONE;
-    for (int64_t r = blockIdx.x * (int64_t)(DB_THREADS / 64) + (threadIdx.x >> 6); r < m.ncells; r += waves) {
-        const int64_t from = load_index(m.indptr, m.indptr_kind, r), to = load_index(m.indptr, m.indptr_kind, r + 1);
-        for (int64_t e = from + lane; e < to; e += 64) {
-            const long long c = load_index(m.indices, m.idx_kind, e);
-            if (c < 0 || c >= m.ngenes) offends(bad_index, e);
-            if (e > from && load_index(m.indices, m.idx_kind, e - 1) >= c) offends(bad_order, r);
-            if (thin_value_bad(load_value(m.val, m.val_kind, e))) offends(bad_value, e);
-        }
-    }
-    report_min(words + W_BAD_INDEX, bad_index);
-    report_min(words + W_BAD_ORDER, bad_order);
-    report_min(words + W_BAD_VALUE, bad_value);
-}
-
 __global__ __launch_bounds__(DB_THREADS) void doublet_pairs_kernel(const int32_t *__restrict__ parents, int64_t n_pairs, int64_t ncells,
                                                                    unsigned long long *__restrict__ words)
 {
@@ -87,19 +58,7 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_pairs_kernel(const int32_t
         const int64_t a = parents[2 * s], b = parents[2 * s + 1];
         if (a < 0 || a >= ncells || b < 0 || b >= ncells) offends(bad, s);
     }
-    report_min(words + W_BAD_PARENT, bad);
-}
-
-// how many of the n ascending columns at p are below `key`
-template <typename I> __device__ __forceinline__ int64_t rank_in(const I *__restrict__ p, int64_t n, long long key)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((long long)p[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    report_min(words + W_BAD_ROW, bad);
 }
 
 // len[s] = the stored columns of parent a or parent b; len[n_pairs] = 0, the scan's last input.  The shorter parent is
@@ -124,7 +83,7 @@ __global__ __launch_bounds__(DB_THREADS) void doublet_length_kernel(Matrix m, co
             bool match = false;
             if (i < A.len) {
                 const long long c = (long long)indices[A.from + i];
-                const int64_t pos = rank_in(indices + B.from, B.len, c);
+                const int64_t pos = lower_bound(indices + B.from, B.len, c);
                 match = pos < B.len && (long long)indices[B.from + pos] == c;
             }
             shared += __popcll(__ballot(match));
@@ -151,7 +110,7 @@ __device__ __forceinline__ void doublet_place(const Matrix &m, const I *__restri
         if (active) {
             c = (long long)indices[home.from + i];
             v = (int32_t)load_value(m.val, m.val_kind, home.from + i);   // asked for before the search, not behind it
-            pos = rank_in(indices + other.from, other.len, c);
+            pos = lower_bound(indices + other.from, other.len, c);
             match = pos < other.len && (long long)indices[other.from + pos] == c;
         }
         const unsigned long long mask = __ballot(match);
@@ -198,29 +157,27 @@ int64_t rows_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_t n_p
     const int per_wave = DB_THREADS / 64;
     DevBuf len;
     Scratch temp;
-    Offenders<W_COUNT> w;
+    Words w;
     w.reset(st);
-    CSR_LAUNCH(doublet_indptr_kernel, m.ncells + 1, DB_THREADS, st, m.indptr, m.indptr_kind, m.ncells, nnz, w.dev());
+    launch_indptr_check(st, m, nnz, w);
     w.fetch(st);
-    w.refuse(W_BAD_INDPTR, doublet_bad_indptr);
-    CSR_LAUNCH(doublet_entries_kernel, m.ncells, per_wave, st, m, w.dev());
+    w.refuse_indptr("doublets");
+    launch_entries_check<CSR_COUNTS>(st, m, w);
     CSR_LAUNCH(doublet_pairs_kernel, n_pairs, DB_THREADS, st, parents, n_pairs, m.ncells, w.dev());
     w.fetch(st);
-    w.refuse(W_BAD_INDEX, doublet_bad_index);
-    w.refuse(W_BAD_ORDER, doublet_bad_order);
-    w.refuse(W_BAD_VALUE, doublet_bad_value);
-    w.refuse(W_BAD_PARENT, doublet_bad_parent);
+    w.refuse_entries("doublets");
+    w.refuse(W_BAD_ROW, doublet_bad_parent);
 
     const bool wide = m.idx_kind == SCHPF_IDX_I64;
     len.alloc((size_t)(n_pairs + 1) * sizeof(int64_t));
     if (wide) CSR_LAUNCH(doublet_length_kernel<long long>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
     else CSR_LAUNCH(doublet_length_kernel<int>, n_pairs + 1, per_wave, st, m, parents, n_pairs, len.as<int64_t>());
-    csr_checks::exclusive_scan(st, temp, len.as<int64_t>(), out_indptr, (size_t)(n_pairs + 1));
+    exclusive_scan(st, temp, len.as<int64_t>(), out_indptr, (size_t)(n_pairs + 1));
     int64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, out_indptr + n_pairs, sizeof total, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (!out_indices) return total;
-    if (capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+    if (capacity < total) throw std::invalid_argument(csr_bad_capacity(capacity, total));
     if (total > 0) {
         if (wide) CSR_LAUNCH(doublet_fill_kernel<long long>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
         else CSR_LAUNCH(doublet_fill_kernel<int>, n_pairs, per_wave, st, m, parents, n_pairs, out_indptr, out_indices, out_values);
@@ -257,7 +214,7 @@ int schpf_doublet_rows_device(int device, void *stream, int64_t ncells, int64_t 
                                                 out_values, capacity))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         std::unique_ptr<TempStream> own;
         if (n_pairs == 0 || nnz == 0) {   // every row of the result is empty: no input is read
@@ -280,7 +237,7 @@ int schpf_doublet_rows(int device, int64_t ncells, int64_t ngenes, int64_t nnz, 
                                                 out_values, capacity))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         if (n_pairs == 0 || nnz == 0) {
             if (out_indptr) std::fill(out_indptr, out_indptr + n_pairs + 1, (int64_t)0);

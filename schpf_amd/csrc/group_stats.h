@@ -24,18 +24,11 @@ inline const char *group_stats_bad_args(int64_t ncells, int64_t ngenes, int64_t 
     return nullptr;
 }
 
-// The refusals of the matrix and the labels, in the order they are looked for; each names its smallest offender.  The
-// wording is that of doublets.h and qc.h under the prefix of this section
-inline std::string group_stats_from(const std::string &message, size_t old_prefix) { return "group_stats" + message.substr(old_prefix); }
-inline std::string group_stats_bad_indptr(int64_t row) { return group_stats_from(doublet_bad_indptr(row), sizeof("doublets") - 1); }
-inline std::string group_stats_bad_index(int64_t entry) { return group_stats_from(doublet_bad_index(entry), sizeof("doublets") - 1); }
-inline std::string group_stats_bad_order(int64_t row) { return group_stats_from(doublet_bad_order(row), sizeof("doublets") - 1); }
-inline std::string group_stats_bad_value(int64_t entry) { return group_stats_from(doublet_bad_value(entry), sizeof("doublets") - 1); }
+// The refusals of the matrix and of the sum of squares are those of csr_words.h under the prefix "group_stats" (a group
+// holds at most ncells cells: the rule of qc_sumsq_overflows); the labels come behind the matrix
 inline std::string group_stats_bad_labels(int64_t cell)
 {
     return "group_stats: labels must be in [-1, ngroups); offending cell " + std::to_string(cell);
 }
-// the rule of qc_sumsq_overflows: a group holds at most ncells cells
-inline std::string group_stats_bad_sumsq(uint64_t vmax, int64_t ncells) { return group_stats_from(qc_bad_sumsq(vmax, ncells), sizeof("qc") - 1); }
 
 }  // namespace schpf

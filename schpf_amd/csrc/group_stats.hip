@@ -95,7 +95,7 @@ __global__ __launch_bounds__(GS_THREADS) void gs_slabs_kernel(const int64_t *__r
 
 // blockIdx.x: the window of columns; blockIdx.y, and every gridDim.y-th after it: the slab.  G lanes share a row, as in
 // qc_gene_kernel: a row's columns ascend, so the lanes of a row never meet in a bin, and a bin is touched only by a column
-// inside the window.  The matrix has passed csr_entries_kernel<true>: columns in [0, ngenes), values integers in [0, 2^24];
+// inside the window.  The matrix has passed csr_entries_kernel<CSR_COUNTS>: columns in [0, ngenes), values integers in [0, 2^24];
 // order[p] is a cell, in [0, ncells); g * ngenes + column stays below 2^31.  SQ: the sum of squares is asked for
 template <typename I, int G, bool SQ>
 __global__ __launch_bounds__(GS_SUM_THREADS) void gs_sum_kernel(Matrix m, const int32_t *__restrict__ order, const Slab *__restrict__ slabs,
@@ -170,16 +170,14 @@ void group_stats_on_device(hipStream_t st, const Matrix &m, int64_t nnz, const i
     if (nnz > 0) {
         launch_indptr_check(st, m, nnz, w);
         w.fetch(st);
-        w.refuse(W_BAD_INDPTR, group_stats_bad_indptr);
-        launch_entries_check<true>(st, m, w);
+        w.refuse_indptr("group_stats");
+        launch_entries_check<CSR_COUNTS>(st, m, w);
     }
     if (N > 0) CSR_LAUNCH(gs_keys_kernel, N, GS_THREADS, st, labels, N, ngroups, key_a.as<int32_t>(), cell_a.as<int32_t>(), w.dev());
     w.fetch(st);
-    w.refuse(W_BAD_INDEX, group_stats_bad_index);
-    w.refuse(W_BAD_ORDER, group_stats_bad_order);
-    w.refuse(W_BAD_VALUE, group_stats_bad_value);
+    w.refuse_entries("group_stats");
     w.refuse(W_BAD_LABEL, group_stats_bad_labels);
-    if (sumsq && qc_sumsq_overflows(w.h[W_VMAX], N)) throw std::invalid_argument(group_stats_bad_sumsq(w.h[W_VMAX], N));
+    if (sumsq && qc_sumsq_overflows(w.vmax(), N)) throw std::invalid_argument(csr_bad_sumsq("group_stats", w.vmax(), N));
 
     if (N > 0)
         temp.run([&](void *t, size_t &b) {
@@ -225,7 +223,7 @@ int schpf_group_stats_device(int device, void *stream, int64_t ncells, int64_t n
     if (const char *why = group_stats_bad_args(ncells, ngenes, nnz, indptr, indices, val, labels, ngroups, group_cells, nexpr, total))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         std::unique_ptr<TempStream> own;
         const Matrix m{ncells, ngenes, indptr, indices, val, indptr_kind, idx_kind, val_kind};
@@ -240,7 +238,7 @@ int schpf_group_stats(int device, int64_t ncells, int64_t ngenes, int64_t nnz, c
     if (const char *why = group_stats_bad_args(ncells, ngenes, nnz, indptr, indices, val, labels, ngroups, group_cells, nexpr, total))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         const size_t N = (size_t)ncells, G = (size_t)ngroups, GJ = G * (size_t)ngenes;
         TempStream ts;

@@ -4,7 +4,8 @@
 // components and the cluster graph (components.hip), of the shortest-path distances (geodesic.hip), of the rank sums
 // (rank_sums.hip), of the simulated doublets (doublets.hip) with the draw of their parents and of the axis statistics and
 // the submatrix (qc.hip), of the Pearson residual sums per gene (residual_var.hip), of the transpose to gene-major
-// (transpose.hip), and the SCHPF_BACKTRACE crash handler.
+// (transpose.hip), and the SCHPF_BACKTRACE crash handler.  The restatements that read a caller's CSR validate it with
+// check_count_csr or check_graph_csr and check_labels, below, and then do their arithmetic.
 // Nothing here touches the device.
 #include <execinfo.h>
 #include <signal.h>
@@ -18,6 +19,7 @@
 #include <thread>
 
 #include "common.h"
+#include "csr_words.h"
 #include "doublets.h"
 #include "group_stats.h"
 #include "philox.h"
@@ -62,6 +64,86 @@ struct CrashTraceInstaller {
         sigaction(SIGABRT, &sa, &g_prev_abrt);
     }
 } g_crash_trace_installer;
+}  // namespace
+
+// The validation every restatement of a CSR consumer shares, one routine per family: the rule the kernels of
+// csr_device.h and graph_device.h check, as serial loops that throw the refusal of the smallest offender
+namespace {
+
+// A count CSR (int64 indptr, int32 columns) to `level` under the prefix of operator `op`.  The indptr first: the walk over
+// the entries relies on it, as the device fetches its verdict before the entry check is launched.  Then one pass finds the
+// smallest offending entry, row and entry of the column range, the column order and the values, refused in that order.
+// Returns the largest value (0 below CSR_COUNTS)
+uint64_t check_count_csr(const char *op, int64_t ncells, int64_t ngenes, int64_t nnz, const int64_t *indptr, const int32_t *indices,
+                         const void *val, int val_kind, CsrLevel level)
+{
+    for (int64_t r = 0; r <= ncells; ++r)
+        if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
+            throw std::invalid_argument(csr_bad_indptr(op, r));
+    int64_t bad_index = -1, bad_order = -1, bad_value = -1;
+    uint64_t vmax = 0;
+    for (int64_t r = 0; r < ncells; ++r)
+        for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+            if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
+            if (level >= CSR_ORDER && e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
+            if (level < CSR_COUNTS) continue;
+            const double v = read_count(val, val_kind, e);
+            if (schpf::thin_value_bad(v)) {
+                if (bad_value < 0) bad_value = e;
+            } else {
+                vmax = std::max(vmax, (uint64_t)v);
+            }
+        }
+    if (bad_index >= 0) throw std::invalid_argument(csr_bad_index(op, bad_index));
+    if (bad_order >= 0) throw std::invalid_argument(csr_bad_order(op, bad_order));
+    if (bad_value >= 0) throw std::invalid_argument(csr_bad_value(op, bad_value));
+    return vmax;
+}
+
+// How an operator of the graph and gene-major family words the refusals of its matrix, and whether it asks for ascending
+// columns (the wording of `columns` says so)
+struct GraphWords {
+    std::string (*indptr)(int64_t), (*columns)(int64_t), (*values)(int64_t);
+    bool ascending;
+};
+const GraphWords LOUVAIN_WORDS{louvain_bad_indptr, louvain_bad_columns, louvain_bad_values, true};
+const GraphWords GRAPH_WORDS{louvain_bad_indptr, graph_bad_columns, louvain_bad_values, false};
+const GraphWords RANK_SUMS_WORDS{rank_sums_bad_indptr, rank_sums_bad_cells, rank_sums_bad_values, true};
+const GraphWords HVG_WORDS{hvg_bad_indptr, hvg_bad_cells, hvg_bad_values, true};
+
+// A CSR of n rows with int64 indptr, int32 columns in [0, bound) and values that are finite and >= 0 (data == nullptr: none
+// are asked).  In this order: indptr starts at 0 and does not decrease; refuse_nnz(indptr[n]), the operator's own refusal
+// of the entries' number and pointers; the columns; the values.  Each names its smallest offending row.  Returns indptr[n]
+template <typename V, typename RefuseNnz>
+int64_t check_graph_csr(const GraphWords &words, int64_t n, int64_t bound, const int64_t *indptr, const int32_t *indices, const V *data,
+                        RefuseNnz &&refuse_nnz)
+{
+    if (n == 0) return 0;
+    if (indptr[0] != 0) throw std::invalid_argument(words.indptr(0));
+    for (int64_t i = 0; i < n; ++i)
+        if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(words.indptr(i));
+    refuse_nnz(indptr[n]);
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+            if (indices[e] < 0 || indices[e] >= bound || (words.ascending && e > indptr[i] && indices[e - 1] >= indices[e]))
+                throw std::invalid_argument(words.columns(i));
+    for (int64_t i = 0; data && i < n; ++i)
+        for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
+            if (!(data[e] >= V(0) && std::isfinite(data[e]))) throw std::invalid_argument(words.values(i));
+    return indptr[n];
+}
+void refuse_if(const char *why)
+{
+    if (why) throw std::invalid_argument(why);
+}
+
+// every label in [-1, ngroups): the smallest offender in the operator's words
+void check_labels(int64_t n, const int32_t *labels, int64_t ngroups, std::string (*words)(int64_t))
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (labels[i] < -1 || labels[i] >= ngroups) throw std::invalid_argument(words(i));
+}
+
 }  // namespace
 
 extern "C" {
@@ -540,21 +622,10 @@ int schpf_debug_louvain(int n, const int64_t *indptr, const int32_t *indices, co
             std::fill(stats, stats + 4, (int64_t)0);
             return;
         }
-        if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
-        for (int i = 0; i < n; ++i)
-            if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
-        const int64_t nnz = indptr[n];
-        if (const char *why = louvain_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
-        for (int i = 0; i < n; ++i)
-            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= n || (e > indptr[i] && indices[e - 1] >= indices[e]))
-                    throw std::invalid_argument(louvain_bad_columns(i));
+        const int64_t nnz = check_graph_csr(LOUVAIN_WORDS, n, n, indptr, indices, data,
+                                            [&](int64_t entries) { refuse_if(louvain_bad_nnz(entries, indices, data)); });
         double wmax = 0.0;
-        for (int i = 0; i < n; ++i)
-            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
-                if (!(data[e] >= 0.0 && std::isfinite(data[e]))) throw std::invalid_argument(louvain_bad_values(i));
-                wmax = data[e] > wmax ? data[e] : wmax;
-            }
+        for (int64_t e = 0; e < nnz; ++e) wmax = data[e] > wmax ? data[e] : wmax;
         std::vector<int32_t> lab((size_t)n);
         for (int i = 0; i < n; ++i) lab[(size_t)i] = i;
         int64_t n_comm = n, levels = 0, rounds = 0, w2_first = 0;
@@ -678,14 +749,8 @@ int schpf_debug_components(int n, const int64_t *indptr, const int32_t *indices,
             std::fill(stats, stats + 6, (int64_t)0);
             return;
         }
-        if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
-        for (int i = 0; i < n; ++i)
-            if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
-        const int64_t nnz = indptr[n];
-        if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
-        for (int i = 0; i < n; ++i)
-            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= n) throw std::invalid_argument(graph_bad_columns(i));
+        check_graph_csr(GRAPH_WORDS, n, n, indptr, indices, (const double *)nullptr,
+                        [&](int64_t entries) { refuse_if(components_bad_nnz(entries, indices)); });
         if (within)
             for (int i = 0; i < n; ++i)
                 if (within[i] < -1) throw std::invalid_argument(components_bad_within(i));
@@ -738,25 +803,11 @@ int schpf_debug_cluster_graph(int n, const int64_t *indptr, const int32_t *indic
     if (const char *why = cluster_graph_bad_args(n, indptr, labels, ngroups, group_cells, count, wmax)) return fail("%s", why);
     return guarded([&] {
         const int64_t G = ngroups;
-        if (n > 0) {
-            if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
-            for (int i = 0; i < n; ++i)
-                if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
-        }
-        const int64_t nnz = n > 0 ? indptr[n] : 0;
-        if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
-        for (int i = 0; i < n; ++i)
-            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= n) throw std::invalid_argument(graph_bad_columns(i));
+        const int64_t nnz = check_graph_csr(GRAPH_WORDS, n, n, indptr, indices, data,
+                                            [&](int64_t entries) { refuse_if(components_bad_nnz(entries, indices)); });
+        check_labels(n, labels, G, cluster_graph_bad_labels);
         double largest = data || nnz == 0 ? 0.0 : 1.0;
-        if (data)
-            for (int i = 0; i < n; ++i)
-                for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
-                    if (!(data[e] >= 0.0 && std::isfinite(data[e]))) throw std::invalid_argument(louvain_bad_values(i));
-                    largest = data[e] > largest ? data[e] : largest;
-                }
-        for (int i = 0; i < n; ++i)
-            if (labels[i] < -1 || labels[i] >= G) throw std::invalid_argument(cluster_graph_bad_labels(i));
+        for (int64_t e = 0; data && e < nnz; ++e) largest = data[e] > largest ? data[e] : largest;
         std::fill(group_cells, group_cells + G, (int64_t)0);
         std::fill(count, count + G * G, (int64_t)0);
         if (weight) std::fill(weight, weight + G * G, (int64_t)0);
@@ -787,18 +838,7 @@ int schpf_debug_geodesic(int n, const int64_t *indptr, const int32_t *indices, c
             std::fill(stats, stats + 3, (int64_t)0);
             return;
         }
-        if (indptr[0] != 0) throw std::invalid_argument(louvain_bad_indptr(0));
-        for (int i = 0; i < n; ++i)
-            if (indptr[i + 1] < indptr[i]) throw std::invalid_argument(louvain_bad_indptr(i));
-        const int64_t nnz = indptr[n];
-        if (const char *why = components_bad_nnz(nnz, indices)) throw std::invalid_argument(why);
-        for (int i = 0; i < n; ++i)
-            for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= n) throw std::invalid_argument(graph_bad_columns(i));
-        if (data)
-            for (int i = 0; i < n; ++i)
-                for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e)
-                    if (!(data[e] >= 0.0 && std::isfinite(data[e]))) throw std::invalid_argument(louvain_bad_values(i));
+        check_graph_csr(GRAPH_WORDS, n, n, indptr, indices, data, [&](int64_t entries) { refuse_if(components_bad_nnz(entries, indices)); });
         if (set_ptr[0] != 0) throw std::invalid_argument(geodesic_bad_set_ptr(0));
         for (int r = 0; r < nsets; ++r)
             if (set_ptr[r + 1] < set_ptr[r]) throw std::invalid_argument(geodesic_bad_set_ptr(r));
@@ -883,20 +923,8 @@ int schpf_debug_rank_sums(int ncells, int ngenes, const int64_t *indptr, const i
             if (rank2) std::fill(rank2, rank2 + G * J, (int64_t)0);
             return;
         }
-        if (indptr[0] != 0) throw std::invalid_argument(rank_sums_bad_indptr(0));
-        for (int64_t j = 0; j < J; ++j)
-            if (indptr[j + 1] < indptr[j]) throw std::invalid_argument(rank_sums_bad_indptr(j));
-        const int64_t nnz = indptr[J];
-        if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
-        for (int64_t j = 0; j < J; ++j)
-            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= N || (e > indptr[j] && indices[e - 1] >= indices[e]))
-                    throw std::invalid_argument(rank_sums_bad_cells(j));
-        for (int64_t j = 0; j < J; ++j)
-            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
-                if (!(data[e] >= 0.0f && std::isfinite(data[e]))) throw std::invalid_argument(rank_sums_bad_values(j));
-        for (int64_t i = 0; i < N; ++i)
-            if (labels[i] < -1 || labels[i] >= G) throw std::invalid_argument(rank_sums_bad_labels(i));
+        check_graph_csr(RANK_SUMS_WORDS, J, N, indptr, indices, data, [&](int64_t entries) { refuse_if(rank_sums_bad_nnz(entries, indices, data)); });
+        check_labels(N, labels, G, rank_sums_bad_labels);
 
         std::vector<int64_t> cnt((size_t)G, 0), z((size_t)J), tie((size_t)J), expr((size_t)(G * J), 0), r((size_t)(G * J), 0);
         for (int64_t i = 0; i < N; ++i)
@@ -950,20 +978,8 @@ int schpf_debug_pair_rank_sums(int ncells, int ngenes, const int64_t *indptr, co
             if (ties) std::fill(ties, ties + P * J, (int64_t)0);
             return;
         }
-        if (indptr[0] != 0) throw std::invalid_argument(rank_sums_bad_indptr(0));
-        for (int64_t j = 0; j < J; ++j)
-            if (indptr[j + 1] < indptr[j]) throw std::invalid_argument(rank_sums_bad_indptr(j));
-        const int64_t nnz = indptr[J];
-        if (const char *why = rank_sums_bad_nnz(nnz, indices, data)) throw std::invalid_argument(why);
-        for (int64_t j = 0; j < J; ++j)
-            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= N || (e > indptr[j] && indices[e - 1] >= indices[e]))
-                    throw std::invalid_argument(rank_sums_bad_cells(j));
-        for (int64_t j = 0; j < J; ++j)
-            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
-                if (!(data[e] >= 0.0f && std::isfinite(data[e]))) throw std::invalid_argument(rank_sums_bad_values(j));
-        for (int64_t i = 0; i < N; ++i)
-            if (labels[i] < -1 || labels[i] >= G) throw std::invalid_argument(rank_sums_bad_labels(i));
+        check_graph_csr(RANK_SUMS_WORDS, J, N, indptr, indices, data, [&](int64_t entries) { refuse_if(rank_sums_bad_nnz(entries, indices, data)); });
+        check_labels(N, labels, G, rank_sums_bad_labels);
         for (int64_t p = 0; p < P; ++p) {
             const int64_t a = pairs[2 * p], b = pairs[2 * p + 1];
             if (a < 0 || a >= G || b < 0 || b >= G || a == b) throw std::invalid_argument(pair_rank_sums_bad_pairs(p));
@@ -1024,14 +1040,10 @@ int schpf_debug_residual_var(int64_t ncells, int64_t ngenes, int64_t nnz, const 
     return guarded([&] {
         const int64_t N = ncells, J = ngenes;
         if (J == 0 && nnz != 0) throw std::invalid_argument(hvg_bad_indptr(0));
-        if (J > 0 && indptr[0] != 0) throw std::invalid_argument(hvg_bad_indptr(0));
-        for (int64_t j = 0; j < J; ++j)
-            if (indptr[j + 1] < indptr[j]) throw std::invalid_argument(hvg_bad_indptr(j));
-        if (J > 0 && indptr[J] != nnz) throw std::invalid_argument(hvg_bad_indptr(J - 1));
-        for (int64_t j = 0; j < J; ++j)
-            for (int64_t e = indptr[j]; e < indptr[j + 1]; ++e)
-                if (indices[e] < 0 || indices[e] >= N || (e > indptr[j] && indices[e - 1] >= indices[e]))
-                    throw std::invalid_argument(hvg_bad_cells(j));
+        // the values are judged by hvg_count below, while they are summed
+        check_graph_csr(HVG_WORDS, J, N, indptr, indices, (const float *)nullptr, [&](int64_t last) {
+            if (last != nnz) throw std::invalid_argument(hvg_bad_indptr(J - 1));
+        });
         std::vector<int64_t> n((size_t)N, 0), s((size_t)J, 0);
         int64_t T = 0;
         for (int64_t j = 0; j < J; ++j)
@@ -1083,24 +1095,12 @@ int schpf_debug_doublet_rows(int64_t ncells, int64_t ngenes, int64_t nnz, const 
                                                 out_values, capacity))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         if (n_pairs == 0 || nnz == 0) {
             if (out_indptr) std::fill(out_indptr, out_indptr + n_pairs + 1, (int64_t)0);
             return;
         }
-        for (int64_t r = 0; r <= ncells; ++r)
-            if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
-                throw std::invalid_argument(doublet_bad_indptr(r));
-        int64_t bad_index = -1, bad_order = -1, bad_value = -1;
-        for (int64_t r = 0; r < ncells; ++r)
-            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-                if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
-                if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
-                if (schpf::thin_value_bad(read_count(val, val_kind, e)) && bad_value < 0) bad_value = e;
-            }
-        if (bad_index >= 0) throw std::invalid_argument(doublet_bad_index(bad_index));
-        if (bad_order >= 0) throw std::invalid_argument(doublet_bad_order(bad_order));
-        if (bad_value >= 0) throw std::invalid_argument(doublet_bad_value(bad_value));
+        check_count_csr("doublets", ncells, ngenes, nnz, indptr, indices, val, val_kind, CSR_COUNTS);
         for (int64_t s = 0; s < n_pairs; ++s)
             if (parents[2 * s] < 0 || parents[2 * s] >= ncells || parents[2 * s + 1] < 0 || parents[2 * s + 1] >= ncells)
                 throw std::invalid_argument(doublet_bad_parent(s));
@@ -1120,7 +1120,7 @@ int schpf_debug_doublet_rows(int64_t ncells, int64_t ngenes, int64_t nnz, const 
         }
         const int64_t total = ptr[(size_t)n_pairs];
         std::copy(ptr.begin(), ptr.end(), out_indptr);
-        if (out_indices && capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+        if (out_indices && capacity < total) throw std::invalid_argument(csr_bad_capacity(capacity, total));
         if (!out_indices) return;
         for (int64_t s = 0; s < n_pairs; ++s) {
             int64_t i = indptr[parents[2 * s]], j = indptr[parents[2 * s + 1]], o = ptr[(size_t)s];
@@ -1147,29 +1147,11 @@ int schpf_debug_axis_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const in
                                             cell_set_total, gene_n, gene_total, gene_sumsq))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         const size_t N = (size_t)ncells, J = (size_t)ngenes, S = (size_t)n_sets;
         if (nnz > 0) {
-            for (int64_t r = 0; r <= ncells; ++r)
-                if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
-                    throw std::invalid_argument(qc_bad_indptr(r));
-            int64_t bad_index = -1, bad_order = -1, bad_value = -1;
-            uint64_t vmax = 0;
-            for (int64_t r = 0; r < ncells; ++r)
-                for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-                    if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
-                    if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
-                    const double v = read_count(val, val_kind, e);
-                    if (schpf::thin_value_bad(v)) {
-                        if (bad_value < 0) bad_value = e;
-                    } else {
-                        vmax = std::max(vmax, (uint64_t)v);
-                    }
-                }
-            if (bad_index >= 0) throw std::invalid_argument(qc_bad_index(bad_index));
-            if (bad_order >= 0) throw std::invalid_argument(qc_bad_order(bad_order));
-            if (bad_value >= 0) throw std::invalid_argument(qc_bad_value(bad_value));
-            if (qc_sumsq_overflows(vmax, ncells)) throw std::invalid_argument(qc_bad_sumsq(vmax, ncells));
+            const uint64_t vmax = check_count_csr("qc", ncells, ngenes, nnz, indptr, indices, val, val_kind, CSR_COUNTS);
+            if (qc_sumsq_overflows(vmax, ncells)) throw std::invalid_argument(csr_bad_sumsq("qc", vmax, ncells));
         }
         for (int64_t *p : {cell_n, cell_total}) std::fill(p, p + N, (int64_t)0);
         if (N && S) std::fill(cell_set_total, cell_set_total + N * S, (int64_t)0);
@@ -1198,15 +1180,9 @@ int schpf_debug_submatrix(int64_t ncells, int64_t ngenes, int64_t nnz, const int
                                                 out_indices, out_values, capacity))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         const bool empty = nnz == 0 || n_rows == 0;
-        if (!empty) {
-            for (int64_t r = 0; r <= ncells; ++r)
-                if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
-                    throw std::invalid_argument(qc_bad_indptr(r));
-            for (int64_t e = 0; e < nnz; ++e)
-                if (indices[e] < 0 || indices[e] >= ngenes) throw std::invalid_argument(qc_bad_index(e));
-        }
+        if (!empty) check_count_csr("qc", ncells, ngenes, nnz, indptr, indices, val, val_kind, CSR_RANGE);
         for (int64_t s = 0; rows && s < n_rows; ++s)
             if (rows[s] < 0 || rows[s] >= ncells) throw std::invalid_argument(qc_bad_rows(s));
         std::vector<int32_t> colmap((size_t)ngenes + 1, 0);   // the kept genes before gene j
@@ -1219,11 +1195,11 @@ int schpf_debug_submatrix(int64_t ncells, int64_t ngenes, int64_t nnz, const int
             ptr[(size_t)s + 1] = ptr[(size_t)s] + n;
         }
         const int64_t total = ptr[(size_t)n_rows];
-        if (out_indices && capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+        if (out_indices && capacity < total) throw std::invalid_argument(csr_bad_capacity(capacity, total));
         *out_ngenes = colmap[(size_t)ngenes];
         std::copy(ptr.begin(), ptr.end(), out_indptr);
         if (!out_indices || total == 0) return;
-        const size_t width = val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8;
+        const size_t width = value_size(val_kind);
         for (int64_t s = 0, o = 0; s < n_rows; ++s) {
             const int64_t r = rows ? rows[s] : s;
             for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
@@ -1246,32 +1222,12 @@ int schpf_debug_group_stats(int64_t ncells, int64_t ngenes, int64_t nnz, const i
     if (const char *why = group_stats_bad_args(ncells, ngenes, nnz, indptr, indices, val, labels, ngroups, group_cells, nexpr, total))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         const size_t G = (size_t)ngroups, J = (size_t)ngenes;
         uint64_t vmax = 0;
-        if (nnz > 0) {
-            for (int64_t r = 0; r <= ncells; ++r)
-                if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
-                    throw std::invalid_argument(group_stats_bad_indptr(r));
-            int64_t bad_index = -1, bad_order = -1, bad_value = -1;
-            for (int64_t r = 0; r < ncells; ++r)
-                for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-                    if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
-                    if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
-                    const double v = read_count(val, val_kind, e);
-                    if (schpf::thin_value_bad(v)) {
-                        if (bad_value < 0) bad_value = e;
-                    } else {
-                        vmax = std::max(vmax, (uint64_t)v);
-                    }
-                }
-            if (bad_index >= 0) throw std::invalid_argument(group_stats_bad_index(bad_index));
-            if (bad_order >= 0) throw std::invalid_argument(group_stats_bad_order(bad_order));
-            if (bad_value >= 0) throw std::invalid_argument(group_stats_bad_value(bad_value));
-        }
-        for (int64_t i = 0; i < ncells; ++i)
-            if (labels[i] < -1 || labels[i] >= ngroups) throw std::invalid_argument(group_stats_bad_labels(i));
-        if (sumsq && qc_sumsq_overflows(vmax, ncells)) throw std::invalid_argument(group_stats_bad_sumsq(vmax, ncells));
+        if (nnz > 0) vmax = check_count_csr("group_stats", ncells, ngenes, nnz, indptr, indices, val, val_kind, CSR_COUNTS);
+        check_labels(ncells, labels, ngroups, group_stats_bad_labels);
+        if (sumsq && qc_sumsq_overflows(vmax, ncells)) throw std::invalid_argument(csr_bad_sumsq("group_stats", vmax, ncells));
         std::fill(group_cells, group_cells + G, (int64_t)0);
         for (int64_t *p : {nexpr, total, sumsq})
             if (p && J) std::fill(p, p + G * J, (int64_t)0);
@@ -1309,22 +1265,12 @@ int schpf_debug_transpose(int64_t ncells, int64_t ngenes, int64_t nnz, const int
             std::fill(out_indptr, out_indptr + J + 1, (int64_t)0);
             return;
         }
-        for (int64_t r = 0; r <= ncells; ++r)
-            if ((r == 0 && indptr[0] != 0) || (r == ncells ? indptr[r] != nnz : indptr[r + 1] < indptr[r]))
-                throw std::invalid_argument(transpose_bad_indptr(r));
-        int64_t bad_index = -1, bad_order = -1;
-        for (int64_t r = 0; r < ncells; ++r)
-            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-                if ((indices[e] < 0 || indices[e] >= ngenes) && bad_index < 0) bad_index = e;
-                if (e > indptr[r] && indices[e - 1] >= indices[e] && bad_order < 0) bad_order = r;
-            }
-        if (bad_index >= 0) throw std::invalid_argument(transpose_bad_index(bad_index));
-        if (bad_order >= 0) throw std::invalid_argument(transpose_bad_order(bad_order));
+        check_count_csr("transpose", ncells, ngenes, nnz, indptr, indices, val, val_kind, CSR_ORDER);
         std::vector<int64_t> next(J + 1, 0);   // next[j + 1]: the entries of gene j, then where its next entry goes
         for (int64_t e = 0; e < nnz; ++e) ++next[(size_t)indices[e] + 1];
         for (size_t j = 0; j < J; ++j) next[j + 1] += next[j];
         std::copy(next.begin(), next.end(), out_indptr);
-        const size_t width = transpose_value_size(val_kind);
+        const size_t width = value_size(val_kind);
         for (int64_t r = 0; r < ncells; ++r)
             for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
                 const int64_t o = next[(size_t)indices[e]]++;

@@ -1,11 +1,11 @@
 // Cell and gene filtering: what the kernels of qc.hip and the serial restatement of host.cpp share -- the
-// refusals of the entry points and their messages, and the overflow rule of the sum of squares.  Like doublets.h, plain
-// C++ that compiles for the host and for the device.
+// refusals of the entry points and their messages (those of the matrix itself: csr_words.h), and the overflow rule of the
+// sum of squares.  Like doublets.h, plain C++ that compiles for the host and for the device.
 #pragma once
 #include <cstdint>
 #include <string>
 
-#include "doublets.h"
+#include "csr_words.h"
 
 namespace schpf {
 
@@ -52,23 +52,14 @@ inline const char *qc_submatrix_bad_args(int64_t ncells, int64_t ngenes, int64_t
     return nullptr;
 }
 
-// The refusals of the matrix and the row list, in the order they are looked for; each names its smallest offender.  The
-// wording is that of doublets.h under the prefix of this section
-inline std::string qc_from_doublets(const std::string &message) { return "qc" + message.substr(sizeof("doublets") - 1); }
-inline std::string qc_bad_indptr(int64_t row) { return qc_from_doublets(doublet_bad_indptr(row)); }
-inline std::string qc_bad_index(int64_t entry) { return qc_from_doublets(doublet_bad_index(entry)); }
-inline std::string qc_bad_order(int64_t row) { return qc_from_doublets(doublet_bad_order(row)); }
-inline std::string qc_bad_value(int64_t entry) { return qc_from_doublets(doublet_bad_value(entry)); }
+// The refusals of the matrix are those of csr_words.h under the prefix "qc"; the row list comes behind them
 inline std::string qc_bad_rows(int64_t position) { return "qc: rows must be in [0, ncells); offending position " + std::to_string(position); }
 
-// gene_sumsq[j] <= vmax^2 * ncells must stay below 2^63.  vmax <= 2^24 and ncells < 2^31: the product is below 2^79
+// gene_sumsq[j] <= vmax^2 * ncells must stay below 2^63, or the call is refused in the words of csr_bad_sumsq.  vmax <= 2^24
+// and ncells < 2^31: the product is below 2^79
 inline bool qc_sumsq_overflows(uint64_t vmax, int64_t ncells)
 {
     return (unsigned __int128)(vmax * vmax) * (unsigned __int128)ncells >= (unsigned __int128)1 << 63;
-}
-inline std::string qc_bad_sumsq(uint64_t vmax, int64_t ncells)
-{
-    return "qc: sum of squares may overflow: largest value " + std::to_string(vmax) + " over " + std::to_string(ncells) + " cells";
 }
 
 }  // namespace schpf

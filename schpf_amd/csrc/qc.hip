@@ -232,13 +232,11 @@ void stats_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int n_sets, c
     w.reset(st);
     launch_indptr_check(st, m, nnz, w);
     w.fetch(st);
-    w.refuse(W_BAD_INDPTR, qc_bad_indptr);
-    launch_entries_check<true>(st, m, w);
+    w.refuse_indptr("qc");
+    launch_entries_check<CSR_COUNTS>(st, m, w);
     w.fetch(st);
-    w.refuse(W_BAD_INDEX, qc_bad_index);
-    w.refuse(W_BAD_ORDER, qc_bad_order);
-    w.refuse(W_BAD_VALUE, qc_bad_value);
-    if (qc_sumsq_overflows(w.h[W_VMAX], m.ncells)) throw std::invalid_argument(qc_bad_sumsq(w.h[W_VMAX], m.ncells));
+    w.refuse_entries("qc");
+    if (qc_sumsq_overflows(w.vmax(), m.ncells)) throw std::invalid_argument(csr_bad_sumsq("qc", w.vmax(), m.ncells));
 
     CSR_LAUNCH(qc_cell_kernel, m.ncells, per_wave, st, m, n_sets, gene_flags, cell_n, cell_total, cell_set_total);
     for (int64_t *p : {gene_n, gene_total, gene_sumsq}) HIPCHK(hipMemsetAsync(p, 0, (size_t)m.ngenes * sizeof(int64_t), st));
@@ -269,12 +267,12 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
     if (!empty) {
         launch_indptr_check(st, m, nnz, w);
         w.fetch(st);
-        w.refuse(W_BAD_INDPTR, qc_bad_indptr);
-        launch_entries_check<false>(st, m, w);
+        w.refuse_indptr("qc");
+        launch_entries_check<CSR_RANGE>(st, m, w);
     }
     if (rows && n_rows > 0) CSR_LAUNCH(qc_rows_kernel, n_rows, QC_THREADS, st, rows, n_rows, m.ncells, w.dev());
     w.fetch(st);
-    w.refuse(W_BAD_INDEX, qc_bad_index);
+    w.refuse_entries("qc");
     w.refuse(W_BAD_ROW, qc_bad_rows);
 
     DevBuf kept, colmap, len, indptr;
@@ -303,7 +301,7 @@ int64_t submatrix_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int64_
         HIPCHK(hipMemcpyAsync(&total, indptr.as<int64_t>() + n_rows, sizeof total, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
-    if (out_indices && capacity < total) throw std::invalid_argument(doublet_bad_capacity(capacity, total));
+    if (out_indices && capacity < total) throw std::invalid_argument(csr_bad_capacity(capacity, total));
     *out_ngenes = ngenes_kept;
     if (empty) HIPCHK(hipMemsetAsync(out_indptr, 0, (size_t)(n_rows + 1) * sizeof(int64_t), st));
     else HIPCHK(hipMemcpyAsync(out_indptr, indptr.p, (size_t)(n_rows + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -346,7 +344,7 @@ int schpf_axis_stats_device(int device, void *stream, int64_t ncells, int64_t ng
                                             cell_set_total, gene_n, gene_total, gene_sumsq))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         std::unique_ptr<TempStream> own;
         hipStream_t st = pick_stream(stream, own);
@@ -367,7 +365,7 @@ int schpf_axis_stats(int device, int64_t ncells, int64_t ngenes, int64_t nnz, co
                                             cell_set_total, gene_n, gene_total, gene_sumsq))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         const size_t N = (size_t)ncells, J = (size_t)ngenes, S = (size_t)n_sets;
         if (nnz == 0) {
@@ -409,7 +407,7 @@ int schpf_submatrix_device(int device, void *stream, int64_t ncells, int64_t nge
                                                 out_indices, out_values, capacity))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(indptr_kind, idx_kind, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         std::unique_ptr<TempStream> own;
         const Matrix m{ncells, ngenes, indptr, indices, val, indptr_kind, idx_kind, val_kind};
@@ -426,7 +424,7 @@ int schpf_submatrix(int device, int64_t ncells, int64_t ngenes, int64_t nnz, con
                                                 out_indices, out_values, capacity))
         return fail("%s", why);
     return guarded([&] {
-        if (doublet_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
+        if (csr_kinds_bad(SCHPF_IDX_I64, SCHPF_IDX_I32, val_kind)) throw std::invalid_argument("unknown index or value kind");
         use_device(device);
         const bool empty = nnz == 0 || n_rows == 0;
         const size_t width = value_size(val_kind);

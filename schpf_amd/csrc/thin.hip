@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <memory>
 
+#include "csr_words.h"
 #include "device_call.h"
 #include "philox.h"
 
@@ -202,7 +203,6 @@ void throw_offender(int64_t first_bad_index, int64_t first_bad_value)
                                     std::to_string(first_bad_value));
 }
 
-size_t value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
 
 }  // namespace
 }  // namespace schpf

@@ -1,19 +1,18 @@
 // The gene-major form of a count matrix: what the kernels of transpose.hip and the serial restatement of
-// host.cpp share -- the refusals of the entry points and their messages, and the one expression of the value conversion.
+// host.cpp share -- the refusals of the entry points and their messages (those of the matrix itself: csr_words.h), and the
+// one expression of the value conversion.
 // Like doublets.h, plain C++ that compiles for the host and for the device.
 #pragma once
 #include <cstdint>
 #include <string>
 
-#include "doublets.h"
+#include "philox.h"
 #include "qc.h"
 
 namespace schpf {
 
 // out_values[o] where out_val_kind is SCHPF_VAL_F32 and val_kind is not: v is what load_value / read_count read
 SCHPF_PX float transpose_value(double v) { return (float)v; }
-
-inline size_t transpose_value_size(int val_kind) { return val_kind == SCHPF_VAL_I32 || val_kind == SCHPF_VAL_F32 ? 4 : 8; }
 
 // nothing to transpose: out_indptr is zeros and nothing else is read
 inline bool transpose_empty(int64_t ncells, int64_t ngenes, int64_t nnz) { return nnz == 0 || ncells == 0 || ngenes == 0; }
@@ -25,7 +24,7 @@ inline const char *transpose_bad_args(int64_t ncells, int64_t ngenes, int64_t nn
                                       const void *out_indptr, const void *out_cells, const void *out_values)
 {
     if (const char *why = qc_bad_sizes(ncells, ngenes, nnz)) return why;
-    if (doublet_kinds_bad(indptr_kind, idx_kind, val_kind)) return "unknown index or value kind";
+    if (csr_kinds_bad(indptr_kind, idx_kind, val_kind)) return "unknown index or value kind";
     if (out_val_kind != val_kind && out_val_kind != SCHPF_VAL_F32) return "out_val_kind must be val_kind or SCHPF_VAL_F32";
     if (!out_indptr) return "out_indptr must not be NULL";
     if (transpose_empty(ncells, ngenes, nnz)) return nullptr;
@@ -34,11 +33,6 @@ inline const char *transpose_bad_args(int64_t ncells, int64_t ngenes, int64_t nn
     return nullptr;
 }
 
-// The refusals of the matrix, in the order they are looked for; each names its smallest offender.  The wording is that of
-// doublets.h under the prefix of this section
-inline std::string transpose_from_doublets(const std::string &message) { return "transpose" + message.substr(sizeof("doublets") - 1); }
-inline std::string transpose_bad_indptr(int64_t row) { return transpose_from_doublets(doublet_bad_indptr(row)); }
-inline std::string transpose_bad_index(int64_t entry) { return transpose_from_doublets(doublet_bad_index(entry)); }
-inline std::string transpose_bad_order(int64_t row) { return transpose_from_doublets(doublet_bad_order(row)); }
+// The refusals of the matrix are those of csr_words.h under the prefix "transpose"
 
 }  // namespace schpf

@@ -4,8 +4,8 @@
 // serial restatement gives the same bits, whatever the grid.
 //
 //   csr_indptr_kernel      indptr starts at 0, does not decrease and ends at nnz: the smallest offending row
-//   csr_order_kernel       a wavefront per row: every column in [0, ngenes) and above its left neighbour: the smallest
-//                          offenders (both in csr_device.h).  The values are not looked at
+//   csr_entries_kernel     at CSR_ORDER, a wavefront per row: every column in [0, ngenes) and above its left neighbour: the
+//                          smallest offenders (both in csr_device.h).  The values are not looked at
 //   transpose_count_kernel a workgroup per (window of TR_BINS columns, slab of TR_SLAB rows), as qc_gene_kernel cuts the
 //                          matrix: TR_LANES lanes per row bisect the row for the window's first column and count its entries
 //                          into the window's bins in LDS -- a row's columns ascend, so the lanes of a row never meet in a bin
@@ -187,11 +187,10 @@ void transpose_on_device(hipStream_t st, const Matrix &m, int64_t nnz, int out_v
     w.reset(st);
     launch_indptr_check(st, m, nnz, w);
     w.fetch(st);
-    w.refuse(W_BAD_INDPTR, transpose_bad_indptr);
-    launch_order_check(st, m, w);
+    w.refuse_indptr("transpose");
+    launch_entries_check<CSR_ORDER>(st, m, w);
     w.fetch(st);
-    w.refuse(W_BAD_INDEX, transpose_bad_index);
-    w.refuse(W_BAD_ORDER, transpose_bad_order);
+    w.refuse_entries("transpose");
 
     const int64_t slabs = (m.ncells + TR_SLAB - 1) / TR_SLAB, windows = (m.ngenes + TR_BINS - 1) / TR_BINS, tasks = slabs * windows;
     DevBuf table, count;

@@ -4,7 +4,9 @@ wavefronts and workgroups is never asked.  Here every check gets three offenders
 middle workgroup at a lane of its second or third wavefront, one a few items above that one -- and the middle one must be
 named, in the words of the library's serial restatement (schpf_debug_*), by the device entry and by its host-pointer twin,
 with every output still holding the -7 it was filled with.  Each entry also runs once on the same shape with valid input
-and must equal the restatement bit for bit.
+and must equal the restatement bit for bit.  The operators that read a count CSR (doublet_rows, axis_stats, submatrix,
+group_stats, transpose) get the same treatment for the four refusals of the matrix they share: indptr, column range,
+column order and, where the operator looks at values, a value that is no count.
 
 The shape: 1 000 rows of 3 entries, so the kernels with a thread per entry span 12 workgroups of 256 and the ones with a
 thread per row span 4; 640 root sets and 640 pairs (3 workgroups); a k-NN table of 128 padded rows x 16 factors (8
@@ -59,10 +61,17 @@ class HostOut(Out):
     """An output that is host memory for every entry (stats, wmax)."""
 
 
+class Dev:
+    """An argument that the device entry alone takes (the kinds of the index arrays of a count CSR)."""
+    def __init__(self, value):
+        self.value = value
+
+
 def call(lib, name, how, spec):
     """schpf_debug_<name> / schpf_<name> / schpf_<name>_device on `spec` -> (status, message, the outputs as NumPy)."""
     fn = getattr(lib, {"debug": "schpf_debug_%s", "host": "schpf_%s", "device": "schpf_%s_device"}[how] % name)
     args = {"debug": [], "host": [0], "device": [0, None]}[how]
+    spec = [item.value if isinstance(item, Dev) else item for item in spec if how == "device" or not isinstance(item, Dev)]
     kinds = fn.argtypes[len(args):]
     assert len(kinds) == len(spec)
     keep, outs = [], []
@@ -258,3 +267,65 @@ def test_knn_graph(lib):
         nnz = int(outs[0][-1])
         return [outs[0], outs[1][:nnz], outs[2][:nnz], outs[3], outs[4]]
     accepted(lib, "knn_graph", knn_graph(idx, dist), cut=stored)
+
+
+# ------------------------------------------------------------------------------------------------------- the count CSR family
+VAL_F32, IDX_I32, IDX_I64 = 2, 0, 1             # SCHPF_VAL_F32, SCHPF_IDX_*
+NNZ = PER_ROW * N
+COUNTS = (1 + (np.repeat(np.arange(N), PER_ROW) + INDICES) % 7).astype(np.float32)
+BAD_ORDER = spoilt(INDICES, FIRST + 1, INDICES[FIRST])     # a column twice: in range, not above its left neighbour
+BAD_COUNTS = spoilt(COUNTS, FIRST + 1, 2.5)
+WORDS_INDPTR = ": indptr must be 0 at row 0, must be non-decreasing and must end at nnz; offending row 370"
+WORDS_INDEX = ": column index out of range at entry 1110"
+WORDS_ORDER = ": columns must be strictly ascending within a row; offending row 370"
+WORDS_VALUE = ": values must be integer counts in [0, 2^24]; offending entry 1111"
+PARENTS = np.stack([(np.arange(SETS) * 7) % N, (np.arange(SETS) * 11 + 3) % N], axis=1).astype(np.int32)
+
+
+def counts_csr(indptr, indices, val):
+    """The leading arguments of the family: the ring graph as a square count matrix, float32 values."""
+    return [N, N, NNZ, In(indptr), Dev(IDX_I64), In(indices), Dev(IDX_I32), In(val), VAL_F32]
+
+
+def refused_matrix(lib, name, tail, prefix, order=True, values=True):
+    """The refusals of the matrix, each with three offenders; `tail`: the operator's arguments behind the matrix."""
+    spoilt_by = [(BAD_INDPTR, INDICES, COUNTS, WORDS_INDPTR), (INDPTR, BAD_COLUMNS, COUNTS, WORDS_INDEX)]
+    if order:
+        spoilt_by.append((INDPTR, BAD_ORDER, COUNTS, WORDS_ORDER))
+    if values:
+        spoilt_by.append((INDPTR, INDICES, BAD_COUNTS, WORDS_VALUE))
+    for indptr, indices, val, words in spoilt_by:
+        refused(lib, name, counts_csr(indptr, indices, val) + tail, prefix + words)
+    accepted(lib, name, counts_csr(INDPTR, INDICES, COUNTS) + tail)
+
+
+def test_doublet_rows(lib):
+    capacity = 2 * PER_ROW * SETS
+    tail = [SETS, In(PARENTS), Out(SETS + 1, np.int64), Out(capacity, np.int32), Out(capacity, np.int32), capacity]
+    refused_matrix(lib, "doublet_rows", tail, "doublets")
+
+
+def test_axis_stats(lib):
+    flags = (np.arange(N) % 4).astype(np.uint32)
+    tail = [2, In(flags), Out(N, np.int64), Out(N, np.int64), Out((2, N), np.int64), Out(N, np.int64), Out(N, np.int64),
+            Out(N, np.int64)]
+    refused_matrix(lib, "axis_stats", tail, "qc")
+
+
+def test_submatrix(lib):
+    """The submatrix asks the column range alone: neither the order nor the values."""
+    rows = ((np.arange(SETS) * 7) % N).astype(np.int32)
+    keep = (np.arange(N) % 3 != 0).astype(np.uint8)
+    tail = [SETS, In(rows), In(keep), HostOut(1, np.int64), Out(SETS + 1, np.int64), Out(NNZ, np.int32), Out(NNZ, np.float32), NNZ]
+    refused_matrix(lib, "submatrix", tail, "qc", order=False, values=False)
+
+
+def test_group_stats(lib):
+    tail = [In(LABELS), G, Out(G, np.int64), Out((G, N), np.int64), Out((G, N), np.int64), Out((G, N), np.int64)]
+    refused_matrix(lib, "group_stats", tail, "group_stats")
+
+
+def test_transpose(lib):
+    """The values of a transposed matrix mean nothing to the operator: they move as they are."""
+    tail = [VAL_F32, Out(N + 1, np.int64), Out(NNZ, np.int32), Out(NNZ, np.float32), Out(NNZ, np.int64)]
+    refused_matrix(lib, "transpose", tail, "transpose", values=False)
